@@ -9,8 +9,12 @@ the output tonemap are excluded there and excluded here). Inputs (scene, BVH,
 environment) are resident in HBM before timing starts; the camera orbits by a
 fixed step each frame only with --moving.
 
+A plain run sets up, warms up, times --steps frames, writes the last timed frame's
+planes with --dump-outputs DIR, and prints the line with `value` and `ms_per_step`.
+Everything below that is not the headline figure runs only with --full.
+
 `value` is the pipelined rate (frames_in_flight front ends overlap, DESIGN.md);
-the line also carries the serial rate (one frame at a time: camera-to-display
+with --full the line also carries the serial rate (one frame at a time: camera-to-display
 latency of one frame), 1080p (configs[1]), the path tracer's rays/s and BVH
 visits/s, a surface-dominated view, the a-trous roofline three ways (SURVEY.md's
 52 B/px convention, PMC traffic, background-weighted bytes), the CPU oracle on
@@ -53,6 +57,10 @@ ATROUS_KERNEL = "atrous_tile_kernel"
 EXCHANGE_STAGES = ("history", "reproject", "variance", "atrous0", "atrous1", "atrous2", "atrous3", "atrous4", "taa")
 # planes compared bitwise between the gathered bands and the one-GPU frame (--gpus N > 1)
 PARITY_PLANES = ("color", "albedo", "reproj_illum", "variance", "history_illum", "atrous", "modulate")
+# planes --dump-outputs writes (the path tracer's colour and albedo, the filtered illumination, the modulated frame)
+# and the bytes they may take together: a plane above its equal share is sampled (seeded pixel choice)
+DUMP_PLANES = ("color", "albedo", "atrous", "modulate")
+DUMP_BUDGET = 48 << 20
 # HBM bytes per a-trous launch measured with rocprofv3 PMC passes (tools/gpu_profile.sh), committed under profiles/,
 # one file per camera view (the surface view's bytes are its own, not the default view's)
 TRAFFIC_FILE = os.path.join(REPO, "profiles", "atrous_traffic_{view}.json")
@@ -97,6 +105,13 @@ def parse():
     ap.add_argument("--scene", default="table_clock_plant")
     ap.add_argument("--view", default="default", choices=sorted(VIEWS), help="camera of the headline run")
     ap.add_argument("--moving", action="store_true", help="orbit the camera 1 deg/frame (configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure and check everything else the line can carry (probes of "
+                         "the headline run, serial rate, 1080p, surface view, moving camera, dynamic BVH, CPU baseline, "
+                         "configs[0], multi-GPU band parity); the --no-* switches below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the planes the last timed frame produced as DIR/<name>.npy "
+                         "(float32; a fixed seeded pixel sample of a plane too large for its share of 48 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", default="960x540", help="oracle sample frame size for cpu_baseline (all cores)")
     ap.add_argument("--cpu-sample-1core", default="480x270", help="oracle sample frame size on 1 core")
@@ -396,11 +411,34 @@ def main():
         dist.all_reduce(t)
         return t.tolist()
 
-    def run(W, H, K, view="default", probes=True, parity=False, moving=None):
+    def dump_outputs(r, path):
+        """The planes of the last frame drawn (its pending back end issued first), as path/<name>.npy float32 rows
+        of pixels: the whole plane, or the same seeded choice of pixels in every run where the plane is above its
+        share of DUMP_BUDGET. On N ranks every rank's owned rows are gathered on rank 0, which writes."""
+        pl = r.planes()
+        planes = {k: gl.readback(pl[k]) for k in DUMP_PLANES}
+        if world > 1:
+            from ptsvgf.dist import gather_bands
+            p = r.plan
+            planes = gather_bands({k: v[p.y0 - p.row0:p.y1 - p.row0] for k, v in planes.items()}, p, dist)
+        if rank == 0:
+            os.makedirs(path, exist_ok=True)
+            for k in DUMP_PLANES:
+                px = np.ascontiguousarray(planes[k], np.float32).reshape(-1, planes[k].shape[-1])
+                keep = (DUMP_BUDGET // len(DUMP_PLANES)) // (4 * px.shape[1])
+                if px.shape[0] > keep:
+                    px = px[np.sort(np.random.default_rng(0).choice(px.shape[0], keep, replace=False))]
+                np.save(os.path.join(path, k + ".npy"), px)
+            log(f"  wrote {', '.join(DUMP_PLANES)} of the last timed frame to {path}")
+        if dist:
+            dist.barrier()
+
+    def run(W, H, K, view="default", probes=True, parity=False, moving=None, dump=None):
         """Warm up, time exactly args.steps frames (barrier + sync on both sides, max over ranks); then, untimed:
-        one frame with the traversal counters on, one profiled frame (per-pass HIP events), the a-trous launches
-        replayed between HIP events, and the surface fraction of the frame. moving: orbit the camera 1 deg per
-        frame (configs[4]; default --moving), the profiled frame included."""
+        the last timed frame's planes written to `dump`; with probes, one frame with the traversal counters on, one
+        profiled frame (per-pass HIP events), the a-trous launches replayed between HIP events, and the surface
+        fraction of the frame. moving: orbit the camera 1 deg per frame (configs[4]; default --moving), the profiled
+        frame included."""
         moving = args.moving if moving is None else moving
         check(pt().pt_set_stream(torch.cuda.current_stream().cuda_stream))  # a previous renderer's streams are gone
         log(f"run {W}x{H} K={K} view={view}")
@@ -472,6 +510,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         out = {"dt": dt, "rows": r.rows_rendered() if hasattr(r, "rows_rendered") else H}
+        if dump:
+            dump_outputs(r, dump)
         rr = getattr(r, "r", r)
         if K > 1 and probes:
             # camera-to-modulate latency (untimed frames): from a frame's camera reaching the GPU to the end of its
@@ -661,7 +701,10 @@ def main():
 
     W, H = args.width, args.height
     K = args.frames_in_flight
-    res = run(W, H, K, args.view, parity=world > 1 and not args.no_band_parity)
+    full = args.full
+    if not full:  # a plain run: the headline figure only (no probes, no further runs, no baselines, no parity check)
+        args.no_extras = args.no_1080p = args.no_cpu_baseline = args.no_band_parity = True
+    res = run(W, H, K, args.view, probes=full, parity=world > 1 and not args.no_band_parity, dump=args.dump_outputs)
     ms = res["dt"] / args.steps * 1e3
     fps = args.steps / res["dt"]  # whole frames per second (all ranks together render one frame)
     extra = {}
@@ -746,9 +789,11 @@ def main():
                                            if world > 1 and args.shard in ("frames", "tiles") else f"bands{world}"),
                            "frames_in_flight": K,
                            "trace_batch": min(args.trace_batch, K)},
-                "roofline": atrous_roofline(res, W, res["rows"], args.view), "cpu_baseline": cpu,
-                "path_tracer": pt_rates(res, fps), **extra,
-                "passes_ms": {k: round(v, 4) for k, v in res["per_pass"].items()}}
+                "full": full}
+        if full:  # what the headline run's probes measured, and the further runs
+            line.update({"roofline": atrous_roofline(res, W, res["rows"], args.view), "cpu_baseline": cpu,
+                         "path_tracer": pt_rates(res, fps), **extra,
+                         "passes_ms": {k: round(v, 4) for k, v in res["per_pass"].items()}})
         if "max_history_rows" in res:
             line["max_history_rows"] = res["max_history_rows"]
         if "latency" in res:

@@ -1,16 +1,17 @@
 """Reference citations (``file:line`` / ``file:a-b``) in the product, oracle, tests and docs point inside the cited
 reference file, and the anchors the oracle's fidelity rests on name the function they claim.
 
-Runs where the reference tree is present (this container); skipped on the GPU box, which has no /root/reference.
-The reference is read as text only."""
+The reference is not read here: tests/golden/reference_index.json records, per reference source file name, its line
+count and, per anchor, the lines that name the function (tools/make_reference_index.py writes it from a reference
+checkout; numbers and names only)."""
+import json
 import os
 import re
-from collections import defaultdict
 
 import pytest
 
-REF = "/root/reference"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INDEX = os.path.join(REPO, "tests", "golden", "reference_index.json")
 SCAN = ["path-tracing-svgf_amd", "oracle", "include", "tests", "tools", "bench.py", "__graft_entry__.py", "DESIGN.md",
         "INTEGRATION.md", "README.md"]
 CITE = re.compile(r"([A-Za-z_][\w.\-/]*\.(?:frag|vert|h|cpp|hpp|c))(:\d+(?:-\d+)?(?:,\s*:?\d+(?:-\d+)?)*)")
@@ -28,33 +29,14 @@ ANCHORS = [
     ("hdrloader.cpp", 118, "decrunch"), ("hdrloader.cpp", 161, "oldDecrunch"),
 ]
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 
-
-def _ref_files():
-    files = defaultdict(list)
-    for dp, _, fn in os.walk(REF):
-        if "/.git" in dp:
-            continue
-        for f in fn:
-            files[f].append(os.path.join(dp, f))
-    return files
-
-
-def _lines(path):
-    """Lines as editors number them (split on LF only: the reference's GBK comments hold bytes str.splitlines
-    would also break on)."""
-    with open(path, "rb") as fh:
-        data = fh.read()
-    lines = data.split(b"\n")
-    if lines and lines[-1] == b"":
-        lines.pop()
-    return [ln.decode("latin-1") for ln in lines]
+def _index():
+    with open(INDEX) as fh:
+        return json.load(fh)
 
 
 def test_citations_lie_inside_the_cited_files():
-    files = _ref_files()
-    nlines = {name: max(len(_lines(p)) for p in paths) for name, paths in files.items()}
+    nlines = _index()["lines"]
     bad, seen = [], 0
     for root in SCAN:
         top = os.path.join(REPO, root)
@@ -79,6 +61,6 @@ def test_citations_lie_inside_the_cited_files():
 
 @pytest.mark.parametrize("name,line,text", ANCHORS)
 def test_anchor_lines_name_their_function(name, line, text):
-    paths = _ref_files()[name]
-    assert paths, name
-    assert any(text in _lines(p)[line - 1] for p in paths), (name, line, text)
+    named = _index()["anchors"].get(name, {})
+    assert text in named, (name, text)
+    assert line in named[text], (name, line, text, named[text])

@@ -45,7 +45,7 @@ def test_bench_band_parity_gloo(world, moving, balance, shard):
     shard = "frames" if ship or w1 or b2 else "tiles" if tb3 else shard
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", f"--master-port={_port()}", os.path.join(REPO, "bench.py"),
-           "--gpus", str(world), "--backend", "gloo", "--width", "320", "--height", "256", "--steps", "4",
+           "--full", "--gpus", str(world), "--backend", "gloo", "--width", "320", "--height", "256", "--steps", "4",
            "--warmup", "2", "--no-extras", "--no-1080p", "--no-cpu-baseline", "--shard", shard,
            "--ship-gbuffer", "1" if ship else "0"]
     cmd += ["--moving"] if moving else []
@@ -92,7 +92,7 @@ def test_bench_frame_shard_8_ranks_gloo(W, H, balance):
     world = 8
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", f"--master-port={_port()}", os.path.join(REPO, "bench.py"),
-           "--gpus", str(world), "--backend", "gloo", "--width", str(W), "--height", str(H), "--steps", "16",
+           "--full", "--gpus", str(world), "--backend", "gloo", "--width", str(W), "--height", str(H), "--steps", "16",
            "--warmup", "2", "--no-extras", "--no-1080p", "--no-cpu-baseline", "--shard", "frames", "--moving"]
     cmd += ["--equal-bands", "0" if balance else "1"]
     p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=850)
@@ -123,7 +123,7 @@ def test_bench_moving_extra_on_ranks_gloo():
     world = 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", f"--master-port={_port()}", os.path.join(REPO, "bench.py"),
-           "--gpus", str(world), "--backend", "gloo", "--width", "320", "--height", "256", "--steps", "4",
+           "--full", "--gpus", str(world), "--backend", "gloo", "--width", "320", "--height", "256", "--steps", "4",
            "--warmup", "2", "--no-1080p", "--no-cpu-baseline", "--equal-bands", "1"]
     p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]

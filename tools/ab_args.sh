@@ -15,7 +15,7 @@ for rep in $(seq 1 "${REPS:-2}"); do
     for V in ${VIEWS:-default surface}; do
       N=v${i}_${V}_$rep
       # shellcheck disable=SC2086
-      timeout -k 10 300 python3 "$R/bench.py" --no-cpu-baseline --no-1080p --no-extras --view "$V" $A \
+      timeout -k 10 300 python3 "$R/bench.py" --full --no-cpu-baseline --no-1080p --no-extras --view "$V" $A \
         > "$OUT/$N.json" 2> "$OUT/$N.err" || { echo "$N failed"; exit 1; }
       python3 -c "
 import json; d = json.loads(open('$OUT/$N.json').read()); pm = d['passes_ms']

@@ -11,7 +11,7 @@ for rep in $(seq 1 "${REPS:-2}"); do
   for L in "$@"; do
     for V in ${VIEWS:-default surface}; do
       N=$(echo "$L" | tr '/' '_')_${V}_$rep
-      PTSVGF_LIB_DIR="$R/path-tracing-svgf_amd/$L" timeout -k 10 300 python3 "$R/bench.py" --no-cpu-baseline --no-1080p \
+      PTSVGF_LIB_DIR="$R/path-tracing-svgf_amd/$L" timeout -k 10 300 python3 "$R/bench.py" --full --no-cpu-baseline --no-1080p \
         --no-extras --view "$V" $BENCH_ARGS > "$OUT/$N.json" 2> "$OUT/$N.err" || { echo "$N failed"; exit 1; }
       python3 -c "
 import json; d = json.loads(open('$OUT/$N.json').read()); pt = d['path_tracer']; pm = d['passes_ms']

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/bud2
 for rep in $(seq 1 ${2:-2}); do
   for c in $1; do
-    timeout -k 10 300 python bench.py --no-1080p --no-cpu-baseline --steps 40 --pt-uniform closest_budget=$c \
+    timeout -k 10 300 python bench.py --full --no-1080p --no-cpu-baseline --steps 40 --pt-uniform closest_budget=$c \
       > gpurun_out/bud2/c${c}_$rep.json 2> gpurun_out/bud2/c${c}_$rep.err || exit 1
     python3 - gpurun_out/bud2/c${c}_$rep.json c$c rep$rep <<'PY'
 import json, sys

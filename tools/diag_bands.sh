@@ -7,7 +7,7 @@ port=29611
 while IFS= read -r extra; do
   port=$((port + 1))
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=2 --master-addr 127.0.0.1 \
-    --master-port=$port bench.py --gpus 2 --backend gloo --width 320 --height 256 --steps 4 --warmup 2 --no-extras \
+    --master-port=$port bench.py --full --gpus 2 --backend gloo --width 320 --height 256 --steps 4 --warmup 2 --no-extras \
     --no-1080p --no-cpu-baseline --shard bands --ship-gbuffer 0 $extra > gpurun_out/diag.json 2> gpurun_out/diag.err \
     || { echo "run failed: $extra"; tail -20 gpurun_out/diag.err; exit 1; }
   grep -h "ref2" gpurun_out/diag.err

@@ -12,7 +12,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for v in "${VALS[@]}"; do
     for view in ${VIEWS_AB:-default surface}; do
       f=gpurun_out/envab_$(echo "$v" | tr '/' '_')_$view.log
-      env "$N=$v" timeout -k 10 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-1080p --no-extras \
+      env "$N=$v" timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-1080p --no-extras \
         --view $view "$@" > $f 2>&1 || exit $?
       python - "$N" "$v" "$view" "$f" <<'PY'
 import json, sys

@@ -18,7 +18,7 @@ R="$GRAFT_REPO_ROOT"
 OUT="$R/gpurun_out/prof_$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-1080p --no-extras --frames-in-flight $FIF --view $VIEW $*"
+B="$R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-1080p --no-extras --frames-in-flight $FIF --view $VIEW $*"
 echo "$FIF $VIEW $B" > "$OUT/config.txt"
 # the a-trous machine code this profile measures (bench.py compares it with the library it loads)
 python3 "$R/tools/kernel_hash.py" "${PTSVGF_LIB_DIR:-$R/path-tracing-svgf_amd/lib}/libptsvgf.so" > "$OUT/atrous_code_sha256.txt"

@@ -13,7 +13,7 @@ for U in "$@"; do
   ARGS=""
   for kv in $(echo "$U" | tr ',' ' '); do ARGS="$ARGS --pt-uniform $kv"; done
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o run -- \
-    python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-1080p --no-extras --frames-in-flight 1 $ARGS \
+    python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-1080p --no-extras --frames-in-flight 1 $ARGS \
     > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
   echo "== $U"
   python3 - "$OUT/run_kernel_stats.csv" <<'PY'

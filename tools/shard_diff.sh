@@ -22,7 +22,7 @@ done
 for k in 1 4; do
   echo "bench K=$k: $(date +%T)"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_k$k" -o run -- \
-    python3 "$R/bench.py" --steps 16 --warmup 4 --no-cpu-baseline --no-1080p --no-extras --frames-in-flight $k \
+    python3 "$R/bench.py" --full --steps 16 --warmup 4 --no-cpu-baseline --no-1080p --no-extras --frames-in-flight $k \
     > "$OUT/bench_k$k.json" 2> "$OUT/bench_k$k.err" || exit $?
   tail -c 200 "$OUT/bench_k$k.json"
 done
