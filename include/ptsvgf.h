@@ -148,7 +148,10 @@ int pt_texbuffer_create(const void* host_data, size_t bytes, uint32_t fmt, uint3
  * radius (a surface-area-driven top, cheaper to walk); 0 keeps the plain LBVH. tri_out / node_out are existing
  * texbuffers (any size, e.g. created empty), distinct from tri_in and each other; their device and host copies are
  * replaced, so passes bound to them draw the new scene next time. leaf_n in [1, 15], ploc_radius in [0, 256].
- * out_nodes: node count (dummy included); out_ms: device time of the build (NULL: skipped).
+ * The walk trees of the new nodes (the packed binary tree, the leaf list and a 4-wide tree) are derived on the device
+ * right after the build and kept with node_out, so the first draw over the new buffers packs nothing on the host; a
+ * path-tracing pass walks the 4-wide tree unless its int uniform lbvh_wide is 0 (same image either way).
+ * out_nodes: node count (dummy included); out_ms: device time of the build, that derivation included (NULL: skipped).
  * Synchronous (waits for the build on the library stream). */
 int pt_bvh_build(uint32_t tri_in, int leaf_n, int ploc_radius, uint32_t tri_out, uint32_t node_out, int* out_nodes,
                  float* out_ms);

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/ptsvgf.h"
+#include "../../include/ptsvgf_debug.h"
 #include "../../include/ptsvgf_scene.h"
 #include "glsl_builtins.h"
 #include "pt_device.h"
@@ -64,7 +65,16 @@ struct Texture {
   uint64_t tflags_ver = 0;          // texture version / rows they were derived for
   int tflags_y0 = 0, tflags_y1 = -1;
   bool lbvh = false;     // written by pt_bvh_build (the device copy is authoritative: get_scene decodes it there)
+  // a node buffer pt_bvh_build wrote: the walk trees the device derived from it (owned; trees->version == version)
+  ptk::LbvhTrees* trees = nullptr;
 };
+
+void free_trees(Texture* t) {
+  if (!t->trees) return;
+  ptk::lbvh_trees_free(*t->trees);
+  delete t->trees;
+  t->trees = nullptr;
+}
 
 struct Uniform {
   int type = 0;  // 1 float 2 int 3 uint 4 bool 5 vec3 6 mat4
@@ -227,6 +237,8 @@ struct SceneGPU {
   int root_any = 0, need_any = 0;
   bool has4 = false;  // bvh4: the 4-wide form of bvh_any (pack_wide)
   bool nan4 = false;  // a child box of bvh4 has a NaN coordinate (PT_WIDE_SIGNED walks need lo <= hi: not walked)
+  // a scene pt_bvh_build wrote: bvh (== bvh_any), bvh4 and leaves belong to the node texture's LbvhTrees, not to this
+  bool lbvh = false;
   int root4 = 0, need4 = 0, root4c = 0;  // root4c: the closest-hit walks' root (SceneDev::root4c)
   // refine_leaves' fine boxes are padded for rays whose origin lies within kFineEyeReach x the scene's largest vertex
   // coordinate; an eye further out (pt_params) walks the reference tree instead
@@ -324,6 +336,7 @@ struct NodeRaw {
 };
 
 constexpr int kRefStack = 256;  // path_tracing.frag:378
+constexpr int kLbvhWideDefault = 1;  // pass uniform lbvh_wide (pt_params)
 
 // *need: deepest interior level (root = 1) = the most stack entries a walk holds
 int pack_bvh(const float* node_enc, int nnodes, std::vector<float4>& out, int* root_ref, int ntris, int* need) {
@@ -1266,7 +1279,15 @@ int tree_check(const float* node_enc, int nnodes, const float* tri_enc, int ntri
   return PT_OK;
 }
 
+// the trees a GPU-built scene borrowed from its node texture are that texture's to free (free_trees)
+void drop_borrowed(SceneGPU& sg) {
+  if (!sg.lbvh) return;
+  sg.bvh = sg.bvh4 = sg.bvh_any = sg.leaves = nullptr;
+  sg.lbvh = false;
+}
+
 void free_scene(SceneGPU& sg) {
+  drop_borrowed(sg);
   float4** bufs[6] = {&sg.geom, &sg.shade, &sg.bvh, &sg.bvh4, &sg.bvh_any, &sg.leaves};
   for (auto b : bufs) {
     if (*b) (void)hipFree(*b);
@@ -1285,8 +1306,21 @@ int upload_vec(const std::vector<T>& v, T** dst) {
 
 // The reference tree's leaves with their own boxes (the primary-ray tile rasteriser's items). The caller has checked
 // the leaf ranges (pack_bvh).
-static int upload_leaves(const float* ne, size_t nnodes, SceneGPU& sg) {
-  std::vector<float4> lv;
+// a child box of a 4-wide tree (pack_wide) has a NaN coordinate (SceneGPU::nan4)
+static bool wide_has_nan(const std::vector<float4>& bvh4) {
+  bool nan = false;
+  for (size_t k = 0; k + ptk::kWideStride <= bvh4.size(); k += ptk::kWideStride) {
+    const float* q = (const float*)&bvh4[k];
+    int refs[4];
+    memcpy(refs, q + 24, 16);
+    for (int c = 0; c < 4; ++c)
+      for (int i = 0; i < 6; ++i) nan = nan || (refs[c] != kNoneRef && std::isnan(q[4 * i + c]));
+  }
+  return nan;
+}
+
+static void collect_leaves(const float* ne, size_t nnodes, std::vector<float4>& lv) {
+  lv.clear();
   for (size_t i = 1; i < nnodes; ++i) {
     const float* f = ne + i * 12;
     const int n = (int)f[3], first = (int)f[4];
@@ -1297,29 +1331,42 @@ static int upload_leaves(const float* ne, size_t nnodes, SceneGPU& sg) {
     lv.push_back(float4{f[6], f[7], f[8], rf});
     lv.push_back(float4{f[9], f[10], f[11], 0.0f});
   }
+}
+static int upload_leaves(const float* ne, size_t nnodes, SceneGPU& sg) {
+  std::vector<float4> lv;
+  collect_leaves(ne, nnodes, lv);
   sg.nleaves = (int)(lv.size() / 2);
   return upload_vec(lv, &sg.leaves);
 }
 
 // A scene pt_bvh_build wrote (dynamic scenes): its triangles are decoded on the device (decode_tris: the host
 // decode's built-ins, the same records), and its own tree (an LBVH, not the reference's SAH tree) serves every walk:
-// no 4-wide or any-hit SAH tree is derived from it, so a rebuild costs the GPU build, this decode and the host
-// packing of the node texels (DESIGN.md "Dynamic scenes").
+// the packed binary tree (also the any-hit tree), the leaf list and the greedy 4-wide form of that tree are the ones
+// pt_bvh_build derived on the device (ptk::lbvh_trees_launch), borrowed from the node texture: a rebuild costs the
+// GPU build with that stage and this decode, and nothing is packed on the host (DESIGN.md "Dynamic scenes").
 int get_scene_lbvh(Texture* tris, Texture* nodes, SceneGPU& sg, SceneGPU** out) {
   const size_t ntris = tris->bytes / (45 * sizeof(float));
-  const size_t nnodes = nodes->host.size() / (12 * sizeof(float));
-  std::vector<float4> bvh;
-  int root = 0;
-  int rc = pack_bvh((const float*)nodes->host.data(), (int)nnodes, bvh, &root, (int)ntris, &sg.stack_need);
-  if (rc != PT_OK) return rc;
-  if ((rc = upload_leaves((const float*)nodes->host.data(), nnodes, sg)) != PT_OK) return rc;
-  if (bvh.empty()) bvh.push_back(float4{0, 0, 0, 0});
-  if ((rc = upload_vec(bvh, &sg.bvh)) != PT_OK) return rc;
-  float4** opt[2] = {&sg.bvh4, &sg.bvh_any};
-  for (auto b : opt)
+  const ptk::LbvhTrees* t = nodes->trees;
+  if (!t || t->version != nodes->version) return err(PT_ERR_STATE, "GPU-built node buffer without its walk trees");
+  // the reference walks with int stack[256] (path_tracing.frag:378); deeper trees are undefined there (pack_bvh)
+  if (t->dev_info[1] >= kRefStack) return err(PT_ERR_FORMAT, "BVH deeper than the reference's stack[256]");
+  drop_borrowed(sg);
+  float4** own[4] = {&sg.bvh, &sg.bvh4, &sg.bvh_any, &sg.leaves};  // of a host-built scene these handles held before
+  for (auto b : own)
     if (*b) { (void)hipFree(*b); *b = nullptr; }
-  sg.has4 = false;
-  sg.need_any = sg.root_any = sg.need4 = sg.root4 = sg.root4c = 0;  // no any-hit tree: its depth must not size the stack
+  sg.lbvh = true;
+  sg.bvh = sg.bvh_any = t->bin;
+  sg.bvh4 = t->wide;
+  sg.leaves = t->leaves;
+  sg.nleaves = t->nleaves();
+  const int root = t->dev_info[0];
+  sg.stack_need = sg.need_any = t->dev_info[1];
+  sg.root_any = root;
+  sg.has4 = true;
+  sg.nan4 = t->dev_info[6] != 0;
+  sg.root4 = sg.root4c = t->dev_info[3];  // 0, or the leaf ref of a tree that is one leaf
+  sg.need4 = t->dev_info[4];
+  sg.fine_eye_limit = INFINITY;  // no fine boxes
   if (sg.geom) (void)hipFree(sg.geom);
   if (sg.shade) (void)hipFree(sg.shade);
   sg.geom = sg.shade = nullptr;
@@ -1344,6 +1391,7 @@ int get_scene(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU*
   size_t ntris = tris->host.size() / (45 * sizeof(float));
   size_t nnodes = nodes->host.size() / (12 * sizeof(float));
   if (tris->lbvh && nodes->lbvh) return get_scene_lbvh(tris, nodes, sg, out);
+  drop_borrowed(sg);
   const float* te = (const float*)tris->host.data();
   std::vector<float4> geom(ntris * 4), shade(ntris * 9);
   for (size_t i = 0; i < ntris; ++i) {
@@ -1384,14 +1432,7 @@ int get_scene(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU*
       sg.has4 = true;
       sg.root4 = root4;
       sg.root4c = root4c;
-      sg.nan4 = false;
-      for (size_t k = 0; k + ptk::kWideStride <= bvh4.size(); k += ptk::kWideStride) {
-        const float* q = (const float*)&bvh4[k];
-        int refs[4];
-        memcpy(refs, q + 24, 16);
-        for (int c = 0; c < 4; ++c)
-          for (int i = 0; i < 6; ++i) sg.nan4 = sg.nan4 || (refs[c] != kNoneRef && std::isnan(q[4 * i + c]));
-      }
+      sg.nan4 = wide_has_nan(bvh4);
       sg.need4 = need4;
       if (getenv("PTSVGF_SCENE_INFO"))  // diagnostics: the walks' working set (DESIGN.md "The traversal in round 4")
         fprintf(stderr, "ptsvgf scene: %zu triangles (geometry %zu B, shading %zu B), reference tree %zu B, any-hit "
@@ -1642,7 +1683,12 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg) {
   // eye further out walks the reference tree, whose boxes are the reference's own
   const bool eye_near = fabsf(k.eye[0]) <= sg->fine_eye_limit && fabsf(k.eye[1]) <= sg->fine_eye_limit &&
                         fabsf(k.eye[2]) <= sg->fine_eye_limit;
-  if (ui(p, "shadow_tree", 1) && eye_near) {  // A/B switch: 0 = shadow rays walk the reference tree
+  // lbvh_wide (default kLbvhWideDefault): a scene pt_bvh_build wrote is walked through the 4-wide tree its device stage
+  // derived (same bits; DESIGN.md "Dynamic scenes"); 0 = its binary tree alone, as before that stage existed. Its
+  // any-hit tree is that same binary tree, so it is bound only for the 4-wide walk.
+  const bool wide_on = sg->has4 && !(PT_WIDE_SIGNED && sg->nan4) && ui(p, "wide_bvh", 1) &&
+                       (!sg->lbvh || ui(p, "lbvh_wide", kLbvhWideDefault));
+  if (ui(p, "shadow_tree", 1) && eye_near && (!sg->lbvh || wide_on)) {  // A/B switch: 0 = shadow rays walk the reference tree
     k.scene.bvh_any = sg->bvh_any;
     k.scene.root_any = sg->root_any;
     k.stack_need = std::max(k.stack_need, sg->need_any);
@@ -1650,8 +1696,7 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg) {
   // wide_bvh = 1 (default): the traversal kernels walk the 4-wide form of the any-hit tree: 28 % fewer node + triangle
   // visits, same bits. With the library built without the SLP vectorizer: 4K 197.7 / 198.9 -> 203.9 / 203.3 fps,
   // surface view 65.4 / 65.2 -> 67.3 / 67.1 (profiles/r03/wide_ab.log; with SLP it measured no faster)
-  k.scene.bvh4 = (k.scene.bvh_any && sg->has4 && !(PT_WIDE_SIGNED && sg->nan4) && ui(p, "wide_bvh", 1)) ? sg->bvh4
-                                                                                                     : nullptr;
+  k.scene.bvh4 = (k.scene.bvh_any && wide_on) ? sg->bvh4 : nullptr;
   k.scene.root4 = sg->root4;
   k.scene.root4c = sg->root4c;
   k.scene.ntris = sg->ntris;
@@ -1879,7 +1924,7 @@ int draw_pathtrace_batch(Pass** ps, int n) {
     // sets k[b].refill and the budgets from these uniforms later): every pass of the batch must agree on them, each
     // compared at its effective value (the default pt_params / pt_wf_setup apply when a pass never set it)
     struct Same { const char* name; int dflt; };
-    const Same same[] = {{"trace_refill", 0}, {"shadow_budget", 0}, {"closest_budget", 0}, {"wide_bvh", 1},
+    const Same same[] = {{"trace_refill", 0}, {"shadow_budget", 0}, {"closest_budget", 0}, {"wide_bvh", 1}, {"lbvh_wide", kLbvhWideDefault},
                          {"refill_waves", 0}, {"trace_fork", 0}, {"refill_grid", 0}, {"list_grid", 0}};
     bool agree = true;
     for (const Same& u : same) agree = agree && ui(ps[b], u.name, u.dflt) == ui(ps[0], u.name, u.dflt);
@@ -2208,6 +2253,7 @@ int pt_shutdown(void) {
     if (t->owned && t->dev) (void)hipFree(t->dev);
     if (t->aux) (void)hipFree(t->aux);
     if (t->tflags) (void)hipFree(t->tflags);
+    free_trees(t);
   }
   for (auto& kv : g.passes) {
     Pass* p = kv.second.get();
@@ -2510,6 +2556,9 @@ int pt_bvh_build(uint32_t tri_in, int leaf_n, int ploc_radius, uint32_t tri_out,
   int nodes = 0;
   int rc = ptk::lbvh_build(g_lbvh, (const float*)ti->dev, ptk::kTriEncoded, n, leaf_n, ploc_radius, tbuf, nbuf,
                            nullptr, &nodes, g.stream);
+  // the walk trees of the new nodes, derived where they lie; their counters arrive with the final sync below
+  std::unique_ptr<ptk::LbvhTrees> trees(new ptk::LbvhTrees);
+  int trc = rc == 0 ? ptk::lbvh_trees_launch(g_lbvh, nbuf, nodes, *trees, g.stream) : 0;
   if (out_ms) {
     (void)hipEventRecord(e1, g.stream);
     (void)hipEventSynchronize(e1);
@@ -2520,14 +2569,75 @@ int pt_bvh_build(uint32_t tri_in, int leaf_n, int ploc_radius, uint32_t tri_out,
   if (rc == 0) rc = texbuffer_take(to, tbuf, nt * 45 * sizeof(float));
   else rc = hip_err((hipError_t)rc, "lbvh_build");
   if (rc == PT_OK) rc = texbuffer_take(no, nbuf, (size_t)nodes * 12 * sizeof(float));
-  if (rc == PT_OK) {
+  {  // also after a failure: the stage's counters are copied into `trees`
     hipError_t e = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess) rc = hip_err(e, "pt_bvh_build");
+    if (e != hipSuccess && rc == PT_OK) rc = hip_err(e, "pt_bvh_build");
+  }
+  if (rc == PT_OK && trc == 0) trc = ptk::lbvh_trees_finish(*trees);
+  if (rc == PT_OK && trc != 0) rc = err(PT_ERR_HIP, "pt_bvh_build: deriving the walk trees failed");
+  if (no->trees && no->trees->version != no->version) free_trees(no);  // the replaced contents' trees
+  if (rc == PT_OK) {
+    trees->version = no->version;
+    no->trees = trees.release();
+  } else {
+    ptk::lbvh_trees_free(*trees);
   }
   (void)hipFree(tbuf);
   (void)hipFree(nbuf);
   if (rc == PT_OK && out_nodes) *out_nodes = nodes;
   return rc;
+}
+
+int pt_debug_lbvh_trees(uint32_t node_tex, int source, int which, void* host_out, size_t cap, size_t* bytes,
+                        int* info8) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  Texture* t = tex_of(node_tex);
+  if (!t || t->target != PT_TEXTURE_BUFFER) return err(PT_ERR_INVALID_HANDLE, "pt_debug_lbvh_trees: not a texture buffer");
+  if (!t->lbvh || !t->trees || t->trees->version != t->version)
+    return err(PT_ERR_STATE, "pt_debug_lbvh_trees: not a node buffer pt_bvh_build wrote");
+  if (source < 0 || source > 1 || which < 0 || which > 2) return err(PT_ERR_ARG, "pt_debug_lbvh_trees: source 0-1, which 0-2");
+  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<float4> host;
+  const void* src = nullptr;
+  size_t n = 0;
+  if (source == 0) {
+    const ptk::LbvhTrees& tr = *t->trees;
+    for (int i = 0; i < 7; ++i) info[i] = tr.dev_info[i];
+    info[7] = (int)lrintf(tr.stage_ms * 1000.0f);
+    src = which == 0 ? tr.bin : which == 1 ? tr.leaves : tr.wide;
+    n = which == 0 ? (size_t)tr.nbin() * 4 : which == 1 ? (size_t)tr.nleaves() * 2 : (size_t)tr.nwide() * ptk::kWideStride;
+  } else {
+    // the host functions over the host mirror of the texels: what the device stage has to equal
+    const float* ne = (const float*)t->host.data();
+    const int nnodes = (int)(t->host.size() / (12 * sizeof(float)));
+    std::vector<float4> bin, leaves, wide;
+    TRY(pack_bvh(ne, nnodes, bin, &info[0], (1 << 24) + 15, &info[1]));
+    collect_leaves(ne, (size_t)nnodes, leaves);
+    info[2] = (int)(leaves.size() / 2);
+    std::vector<SahNode> sn((size_t)nnodes - 1);  // encoded node i is SahNode i - 1: the root is node 0
+    for (int i = 1; i < nnodes; ++i) {
+      const float* f = ne + (size_t)i * 12;
+      SahNode& x = sn[(size_t)i - 1];
+      for (int a = 0; a < 3; ++a) { x.lo[a] = f[6 + a]; x.hi[a] = f[9 + a]; }
+      x.n = std::max((int)f[3], 0);
+      x.first = (int)f[4];
+      if (x.n == 0) { x.left = (int)f[0] - 1; x.right = (int)f[1] - 1; }
+    }
+    TRY(pack_wide(sn, [](int first, int cnt) { return -(first * 16 + cnt) - 1; }, wide, &info[3], &info[4], false));
+    info[5] = (int)(wide.size() / ptk::kWideStride);
+    info[6] = wide_has_nan(wide);
+    host.swap(which == 0 ? bin : which == 1 ? leaves : wide);
+    n = host.size();
+  }
+  if (bytes) *bytes = n * sizeof(float4);
+  if (info8) memcpy(info8, info, sizeof(info));
+  if (host_out && n) {
+    if (cap < n * sizeof(float4)) return err(PT_ERR_ARG, "pt_debug_lbvh_trees: host_out is too small");
+    if (source == 0) HIPCHK(hipMemcpy(host_out, src, n * sizeof(float4), hipMemcpyDeviceToHost));
+    else memcpy(host_out, host.data(), n * sizeof(float4));
+  }
+  return PT_OK;
 }
 
 int pt_texarray_create(int w, int h, int layers, uint32_t* out) {
@@ -2599,6 +2709,7 @@ int pt_texture_destroy(uint32_t tex) {
   if (it->second->owned && it->second->dev) (void)hipFree(it->second->dev);
   if (it->second->aux) (void)hipFree(it->second->aux);
   if (it->second->tflags) (void)hipFree(it->second->tflags);
+  free_trees(it->second.get());  // the scenes that borrowed them are dropped below
   g.textures.erase(it);
   for (auto hm = g.hdr_merged.begin(); hm != g.hdr_merged.end();) {  // merged environments built from it
     if (hm->first.first == tex || hm->first.second == tex) {
@@ -2737,15 +2848,15 @@ int pt_raster_pass_bind_device(uint32_t pass, const void* dverts, size_t n_float
   int rc = ptk::lbvh_build(g_lbvh, (const float*)dverts, ptk::kRasterVerts, ntris, 8, ploc_radius, nullptr, nbuf,
                            order, &nodes, g.stream);
   if (rc) { release(); return hip_err((hipError_t)rc, "raster lbvh_build"); }
-  std::vector<float> hn((size_t)nodes * 12);
-  if (hipMemcpy(hn.data(), nbuf, hn.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-    release();
-    return err(PT_ERR_HIP, "pt_raster_pass_bind_device: node readback");
-  }
-  std::vector<float4> bvh;
-  int root = 0, need = 0;
-  rc = pack_bvh(hn.data(), nodes, bvh, &root, ntris, &need);
-  if (rc != PT_OK || need >= kStack) {
+  // the packed binary tree (pack_bvh's records) and its depth come from the device stage: no node readback
+  ptk::LbvhTrees trees;
+  rc = ptk::lbvh_trees_launch(g_lbvh, nbuf, nodes, trees, g.stream);
+  if (hipStreamSynchronize(g.stream) != hipSuccess && rc == 0) rc = (int)hipErrorUnknown;
+  if (rc == 0) rc = ptk::lbvh_trees_finish(trees);
+  auto release_trees = [&]() { ptk::lbvh_trees_free(trees); };
+  const int root = trees.dev_info[0], need = trees.dev_info[1];
+  if (rc != 0 || need >= kStack) {
+    release_trees();
     // the G-buffer walk's stack holds kStack entries: a deeper device tree (coincident centroids) takes the host
     // bind, whose SAH builder caps the depth; the G-buffer does not depend on the tree
     std::vector<float> hv(n_floats);
@@ -2760,17 +2871,26 @@ int pt_raster_pass_bind_device(uint32_t pass, const void* dverts, size_t n_float
   if (hipMalloc((void**)&p->raster.geom, (size_t)ntris * 4 * sizeof(float4)) != hipSuccess ||
       hipMalloc((void**)&p->raster.nrm, (size_t)ntris * 3 * sizeof(float4)) != hipSuccess) {
     release();
+    release_trees();
     return err(PT_ERR_HIP, "pt_raster_pass_bind_device: out of device memory");
   }
   rc = ptk::decode_raster((const float*)dverts, order, ntris, p->raster.geom, p->raster.nrm, g.stream);
-  if (rc) { release(); return hip_err((hipError_t)rc, "decode_raster"); }
-  if (bvh.empty()) bvh.push_back(float4{0, 0, 0, 0});
-  if ((rc = upload_vec(bvh, &p->raster.bvh)) != PT_OK) { release(); return rc; }
+  if (rc) { release(); release_trees(); return hip_err((hipError_t)rc, "decode_raster"); }
+  // the pass owns a copy sized to the tree (an empty tree: one zero record, as the host bind uploads)
+  const size_t bvh_bytes = (size_t)std::max(1, trees.nbin()) * 4 * sizeof(float4);
+  if (p->raster.bvh) { (void)hipFree(p->raster.bvh); p->raster.bvh = nullptr; }
+  if (hipMalloc((void**)&p->raster.bvh, bvh_bytes) != hipSuccess ||
+      hipMemcpyAsync(p->raster.bvh, trees.bin, bvh_bytes, hipMemcpyDeviceToDevice, g.stream) != hipSuccess) {
+    release();
+    release_trees();
+    return err(PT_ERR_HIP, "pt_raster_pass_bind_device: out of device memory");
+  }
   p->raster.root_ref = root;
   p->raster.stack_need = need;
   // draws of other frames may run on other streams: the records are complete when this returns
   const hipError_t e = hipStreamSynchronize(g.stream);
   release();
+  release_trees();
   if (e != hipSuccess) return hip_err(e, "pt_raster_pass_bind_device");
   return PT_OK;
 }

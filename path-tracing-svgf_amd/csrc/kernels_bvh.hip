@@ -465,6 +465,290 @@ __global__ void __launch_bounds__(256) decode_raster_kernel(const float* __restr
   nrm[3 * k + 2] = float4{f[15], f[16], f[17], 0.0f};
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Walk trees of a built tree (lbvh_trees_launch): the packed binary tree, the leaf list and the 4-wide tree the
+// traversal kernels read, derived from the BVHNode_encoded texels without a trip through the host. Their content is
+// defined by capi.hip's pack_bvh, upload_leaves and pack_wide (greedy collapse, no keep / direct nodes); every
+// float32 operation below is spelled as those evaluate it (-ffp-contract=off).
+//   trees_local   per node: parent links; per interior node the child list of the 4-wide node it would root (local:
+//                 at most two nodes are opened, so only nodes up to three levels below are read)
+//   trees_sizes   bottom-up, lbvh_refit's arrive-second pattern: interior nodes and 4-wide nodes below each node
+//   trees_index   per interior node: walk up; its preorder index is the sum of 1 + (left sibling's size) on the way
+//   trees_emit    per leaf its list entry; per interior node its packed record, and a walk down from the root
+//                 through the child lists (preorder index + size = an O(1) ancestor test) that finds whether it is
+//                 a 4-wide node, which one, and the stack entries held above it
+// Every loop is bounded by the tree's depth (and by the node count, should the texels be no tree) or by 4; no
+// thread waits on another.
+enum { kInfoRoot = 0, kInfoNeed, kInfoLeaves, kInfoRoot4, kInfoNeed4, kInfoWide, kInfoNan, kInfoSpare, kInfoBin,
+       kInfoErr, kInfoInts };
+
+struct NodeTex {
+  int left, right, n, first;
+};
+__device__ __forceinline__ NodeTex node_tex(const float* __restrict__ nodes, int i) {
+  const float* f = nodes + (size_t)i * kNodeFloats;
+  return NodeTex{(int)f[0], (int)f[1], (int)f[3], (int)f[4]};
+}
+__device__ __forceinline__ bool node_ok(int i, int nn) { return i >= 1 && i < nn; }
+__device__ __forceinline__ int leaf_ref_of(const NodeTex& t) { return -(t.first * 16 + t.n) - 1; }
+
+// capi.hip sah_area: extents clamped as std::max(d, 0.0f) evaluates ((d < 0) ? 0 : d, so NaN stays NaN)
+__device__ __forceinline__ float tex_area(const float* __restrict__ nodes, int i) {
+  const float* f = nodes + (size_t)i * kNodeFloats;
+  float dx = f[9] - f[6], dy = f[10] - f[7], dz = f[11] - f[8];
+  dx = dx < 0.0f ? 0.0f : dx;
+  dy = dy < 0.0f ? 0.0f : dy;
+  dz = dz < 0.0f ? 0.0f : dz;
+  return (dx * dy + dy * dz) + dz * dx;
+}
+
+__global__ void __launch_bounds__(256) trees_local(const float* __restrict__ nodes, int nn, int* __restrict__ parent,
+                                                    int4* __restrict__ ch, int2* __restrict__ sz,
+                                                    int* __restrict__ leaf, int* __restrict__ info) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nn) return;
+  sz[i] = int2{0, 0};
+  ch[i] = int4{-1, -1, -1, -1};
+  if (i == 0) {
+    leaf[0] = 0;
+    return;
+  }
+  const NodeTex t = node_tex(nodes, i);
+  leaf[i] = t.n > 0;
+  if (t.n > 0) return;
+  if (!node_ok(t.left, nn) || !node_ok(t.right, nn) || t.left == t.right) {
+    atomicOr(&info[kInfoErr], 1);
+    return;
+  }
+  parent[t.left] = i;
+  parent[t.right] = i;
+  // pack_wide's greedy collapse: open the interior child of the greatest area (strict >, from -1: the first in the
+  // current order wins ties, area 0 qualifies, NaN never does) until four slots are used
+  int c[4] = {t.left, t.right, -1, -1};
+  float a[4] = {tex_area(nodes, t.left), tex_area(nodes, t.right), 0.0f, 0.0f};
+  int nc = 2;
+  for (int round = 0; round < 2; ++round) {
+    int best = -1;
+    float ba = -1.0f;
+    for (int k = 0; k < 4; ++k)
+      if (k < nc && node_tex(nodes, c[k]).n <= 0 && a[k] > ba) {
+        ba = a[k];
+        best = k;
+      }
+    if (best < 0) break;
+    const NodeTex b = node_tex(nodes, c[best]);
+    if (!node_ok(b.left, nn) || !node_ok(b.right, nn)) {
+      atomicOr(&info[kInfoErr], 1);
+      return;
+    }
+    for (int k = 3; k > 0; --k)
+      if (k > best + 1 && k <= nc) {
+        c[k] = c[k - 1];
+        a[k] = a[k - 1];
+      }
+    c[best] = b.left;
+    a[best] = tex_area(nodes, b.left);
+    c[best + 1] = b.right;
+    a[best + 1] = tex_area(nodes, b.right);
+    ++nc;
+  }
+  // PT_WIDE_ORDER: a stable sort by area, descending (std::stable_sort's insertion sort of so few elements)
+  for (int k = 1; k < 4; ++k) {
+    if (k >= nc) break;
+    const int cv = c[k];
+    const float av = a[k];
+    if (av > a[0]) {
+      for (int j = k; j > 0; --j) {
+        c[j] = c[j - 1];
+        a[j] = a[j - 1];
+      }
+      c[0] = cv;
+      a[0] = av;
+    } else {
+      int j = k;
+      while (j > 0 && av > a[j - 1]) {
+        c[j] = c[j - 1];
+        a[j] = a[j - 1];
+        --j;
+      }
+      c[j] = cv;
+      a[j] = av;
+    }
+  }
+  ch[i] = int4{c[0], c[1], c[2], c[3]};
+}
+
+__global__ void __launch_bounds__(256) trees_sizes(const float* __restrict__ nodes, int nn,
+                                                    const int* __restrict__ parent, const int4* __restrict__ ch,
+                                                    const int* __restrict__ leaf, int2* sz, int* flags) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < 1 || i >= nn || !leaf[i]) return;
+  int node = parent[i];
+  for (int step = 0; step < nn && node_ok(node, nn); ++step) {
+    // the first child to arrive stops; the second sees every size below (acq_rel orders the stores and loads)
+    if (__hip_atomic_fetch_add(&flags[node], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
+    const NodeTex t = node_tex(nodes, node);
+    const int4 c4 = ch[node];
+    const int c[4] = {c4.x, c4.y, c4.z, c4.w};
+    int wide = 1;
+    for (int k = 0; k < 4; ++k)
+      if (c[k] >= 0) wide += sz[c[k]].y;  // a leaf's sizes are 0
+    sz[node] = int2{1 + sz[t.left].x + sz[t.right].x, wide};
+    node = parent[node];
+  }
+}
+
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+
+__global__ void __launch_bounds__(256) trees_index(const float* __restrict__ nodes, int nn,
+                                                    const int* __restrict__ parent, const int* __restrict__ leaf,
+                                                    const int2* __restrict__ sz, int* __restrict__ idx,
+                                                    int* __restrict__ info) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  int depth = 0;
+  if (v >= 1 && v < nn && !leaf[v]) {
+    int k = 0, x = v;
+    depth = 1;
+    for (int step = 0; step < nn; ++step) {
+      const int p = parent[x];
+      if (!node_ok(p, nn)) break;
+      const int l = node_tex(nodes, p).left;
+      k += 1 + (x != l && node_ok(l, nn) ? sz[l].x : 0);
+      ++depth;
+      x = p;
+    }
+    idx[v] = k;
+  }
+  depth = wave_max(depth);
+  if ((threadIdx.x & 63) == 0 && depth) atomicMax(&info[kInfoNeed], depth);
+}
+
+__global__ void __launch_bounds__(256) trees_emit(const float* __restrict__ nodes, int nn, const int4* __restrict__ ch,
+                                                   const int* __restrict__ leaf, const int* __restrict__ leafpos,
+                                                   const int2* __restrict__ sz, const int* __restrict__ idx,
+                                                   float4* __restrict__ bin, int cap_bin, float4* __restrict__ leaves,
+                                                   int cap_leaves, float4* __restrict__ wide, int cap_wide,
+                                                   int* __restrict__ info) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  int need4 = 0, bits = 0;  // bits: 1 NaN child box, 2 child index out of range, 4 a record past its part's room
+  if (v >= 1 && v < nn) {
+    const NodeTex t = node_tex(nodes, v);
+    const float* f = nodes + (size_t)v * kNodeFloats;
+    if (v == 1) {
+      info[kInfoRoot] = info[kInfoRoot4] = t.n > 0 ? leaf_ref_of(t) : 0;
+      info[kInfoBin] = sz[1].x;
+      info[kInfoWide] = sz[1].y;
+    }
+    if (v == nn - 1) info[kInfoLeaves] = leafpos[v] + leaf[v];
+    if (t.n > 0) {
+      const int p = leafpos[v];
+      if (p < cap_leaves) {
+        leaves[2 * p] = float4{f[6], f[7], f[8], __int_as_float(leaf_ref_of(t))};
+        leaves[2 * p + 1] = float4{f[9], f[10], f[11], 0.0f};
+      } else {
+        bits |= 4;
+      }
+    } else if (node_ok(t.left, nn) && node_ok(t.right, nn)) {
+      const int k = idx[v];
+      {  // pack_bvh's record
+        const NodeTex L = node_tex(nodes, t.left), R = node_tex(nodes, t.right);
+        const float* l = nodes + (size_t)t.left * kNodeFloats;
+        const float* r = nodes + (size_t)t.right * kNodeFloats;
+        const int rl = L.n > 0 ? leaf_ref_of(L) : k + 1;
+        const int rr = R.n > 0 ? leaf_ref_of(R) : k + 1 + sz[t.left].x;
+        if (k >= 0 && k < cap_bin) {
+          bin[4 * k + 0] = float4{l[6], l[7], l[8], l[9]};
+          bin[4 * k + 1] = float4{l[10], l[11], r[6], r[7]};
+          bin[4 * k + 2] = float4{r[8], r[9], r[10], r[11]};
+          bin[4 * k + 3] = float4{__int_as_float(rl), __int_as_float(rr), 0.0f, 0.0f};
+        } else {
+          bits |= 4;
+        }
+      }
+      // down from the root through the 4-wide child lists: w = the 4-wide node's preorder index, acc = pack_wide's
+      int x = 1, w = 0, acc = 0;
+      bool is_wide = false;
+      for (int step = 0; step < nn; ++step) {
+        if (x == v) {
+          is_wide = true;
+          break;
+        }
+        const int4 c4 = ch[x];
+        const int c[4] = {c4.x, c4.y, c4.z, c4.w};
+        int nc = 0, next = -1, wn = w + 1;
+        for (int s = 0; s < 4; ++s) {
+          if (c[s] < 0) continue;
+          ++nc;
+          if (next >= 0 || leaf[c[s]]) continue;
+          const int2 cs = sz[c[s]];
+          const int ci = idx[c[s]];
+          if (ci <= k && k < ci + cs.x) next = c[s];
+          else wn += cs.y;
+        }
+        if (next < 0 || nc < 2) break;  // v was opened into a 4-wide node above it
+        x = next;
+        w = wn;
+        acc += nc - 1;
+      }
+      if (is_wide) {
+        const int4 c4 = ch[v];
+        const int c[4] = {c4.x, c4.y, c4.z, c4.w};
+        int nc = 0;
+        for (int s = 0; s < 4; ++s) nc += c[s] >= 0;
+        need4 = acc + nc;  // here = acc + nc - 1; need = max(need, here + 1)
+        if (w >= 0 && w < cap_wide) {
+          float q[28];
+          int wn = w + 1;
+          for (int s = 0; s < 4; ++s) {
+            int ref = kNoneRef;
+            float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+            float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+            if (c[s] >= 0) {
+              const float* b = nodes + (size_t)c[s] * kNodeFloats;
+              for (int a = 0; a < 3; ++a) {
+                lo[a] = b[6 + a];
+                hi[a] = b[9 + a];
+                if (lo[a] != lo[a] || hi[a] != hi[a]) bits |= 1;
+              }
+              const NodeTex ct = node_tex(nodes, c[s]);
+              if (ct.n > 0) {
+                ref = leaf_ref_of(ct);
+              } else {
+                ref = wn;
+                wn += sz[c[s]].y;
+              }
+            }
+            for (int a = 0; a < 3; ++a) {
+              q[8 * a + s] = lo[a];
+              q[8 * a + 4 + s] = hi[a];
+            }
+            q[24 + s] = __int_as_float(ref);
+          }
+          float4* o = wide + (size_t)kWideStride * w;
+          for (int j = 0; j < 7; ++j) o[j] = float4{q[4 * j], q[4 * j + 1], q[4 * j + 2], q[4 * j + 3]};
+          for (int j = 7; j < kWideStride; ++j) o[j] = float4{0.0f, 0.0f, 0.0f, 0.0f};
+        } else {
+          bits |= 4;
+        }
+      }
+    } else {
+      bits |= 2;
+    }
+  }
+  need4 = wave_max(need4);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) bits |= __shfl_xor(bits, o);
+  if ((threadIdx.x & 63) == 0) {
+    if (need4) atomicMax(&info[kInfoNeed4], need4);
+    if (bits & 1) atomicOr(&info[kInfoNan], 1);
+    if (bits & 6) atomicOr(&info[kInfoErr], bits >> 1);
+  }
+}
+
 }  // namespace
 
 int decode_raster(const float* verts, const int* order, int n, float4* geom, float4* nrm, hipStream_t s) {
@@ -625,6 +909,92 @@ int lbvh_build(LbvhWork& w, const float* tri, TriLayout lay, int n, int leaf_n, 
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
   *nnodes = 1 + tail[0] + tail[1];
   return (int)hipGetLastError();
+}
+
+void lbvh_trees_free(LbvhTrees& t) {
+  if (t.base) (void)hipFree(t.base);
+  if (t.e0) (void)hipEventDestroy(t.e0);
+  if (t.e1) (void)hipEventDestroy(t.e1);
+  t = LbvhTrees{};
+}
+
+int lbvh_trees_launch(LbvhWork& w, const float* nodes, int nnodes, LbvhTrees& out, hipStream_t s) {
+  if (nnodes < 2 || out.base) return (int)hipErrorInvalidValue;
+  const size_t nn = (size_t)nnodes;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  hipError_t e;
+  size_t scan_bytes = 0;
+  e = rocprim::exclusive_scan(nullptr, scan_bytes, (int*)nullptr, (int*)nullptr, 0, nn, rocprim::plus<int>(), s);
+  if (e != hipSuccess) return (int)e;
+  // parent, flags, leaf, leafpos, idx | child lists | sizes | info | scan scratch
+  const size_t need = 5 * up(sizeof(int) * nn) + up(sizeof(int4) * nn) + up(sizeof(int2) * nn) + 256 + up(scan_bytes);
+  if (w.bytes < need) {  // the build that wrote `nodes` has synchronised: its scratch is free
+    if (w.base) (void)hipFree(w.base);
+    w.base = nullptr;
+    w.bytes = 0;
+    if ((e = hipMalloc(&w.base, need)) != hipSuccess) return (int)e;
+    w.bytes = need;
+  }
+  // a full binary tree of nn - 1 nodes has (nn - 2) / 2 interior nodes; every record written is checked against
+  // its part's room anyway (error bit 2)
+  out.cap_bin = out.cap_wide = std::max(1, nnodes / 2);
+  out.cap_leaves = nnodes;
+  const size_t b_bin = up(sizeof(float4) * 4 * out.cap_bin), b_leaves = up(sizeof(float4) * 2 * out.cap_leaves),
+               b_wide = up(sizeof(float4) * kWideStride * out.cap_wide);
+  if ((e = hipMalloc(&out.base, b_bin + b_leaves + b_wide)) != hipSuccess) {
+    out.base = nullptr;
+    return (int)e;
+  }
+  out.bin = (float4*)out.base;
+  out.leaves = (float4*)((char*)out.base + b_bin);
+  out.wide = (float4*)((char*)out.base + b_bin + b_leaves);
+  char* p = (char*)w.base;
+  auto take = [&](size_t bytes) { char* q = p; p += up(bytes); return (void*)q; };
+  int* parent = (int*)take(sizeof(int) * nn);
+  int* flags = (int*)take(sizeof(int) * nn);
+  int* leaf = (int*)take(sizeof(int) * nn);
+  int* leafpos = (int*)take(sizeof(int) * nn);
+  int* idx = (int*)take(sizeof(int) * nn);
+  int4* ch = (int4*)take(sizeof(int4) * nn);
+  int2* sz = (int2*)take(sizeof(int2) * nn);
+  int* info = (int*)take(256);
+  void* scratch = (void*)p;
+  if (hipEventCreate(&out.e0) != hipSuccess || hipEventCreate(&out.e1) != hipSuccess) return (int)hipErrorUnknown;
+  (void)hipEventRecord(out.e0, s);
+  // parent and flags are adjacent: parent = -1 (no parent), flags = 0; an empty tree's parts read as one zero record
+  if ((e = hipMemsetAsync(parent, 0xff, sizeof(int) * nn, s)) != hipSuccess) return (int)e;
+  if ((e = hipMemsetAsync(flags, 0, sizeof(int) * nn, s)) != hipSuccess) return (int)e;
+  if ((e = hipMemsetAsync(info, 0, 256, s)) != hipSuccess) return (int)e;
+  if ((e = hipMemsetAsync(out.bin, 0, sizeof(float4) * 4, s)) != hipSuccess) return (int)e;
+  if ((e = hipMemsetAsync(out.leaves, 0, sizeof(float4) * 2, s)) != hipSuccess) return (int)e;
+  if ((e = hipMemsetAsync(out.wide, 0, sizeof(float4) * kWideStride, s)) != hipSuccess) return (int)e;
+  const dim3 grid((unsigned)((nn + 255) / 256)), block(256);
+  hipLaunchKernelGGL(trees_local, grid, block, 0, s, nodes, nnodes, parent, ch, sz, leaf, info);
+  size_t sb = scan_bytes;
+  if ((e = rocprim::exclusive_scan(scratch, sb, leaf, leafpos, 0, nn, rocprim::plus<int>(), s)) != hipSuccess)
+    return (int)e;
+  hipLaunchKernelGGL(trees_sizes, grid, block, 0, s, nodes, nnodes, parent, ch, leaf, sz, flags);
+  hipLaunchKernelGGL(trees_index, grid, block, 0, s, nodes, nnodes, parent, leaf, sz, idx, info);
+  hipLaunchKernelGGL(trees_emit, grid, block, 0, s, nodes, nnodes, ch, leaf, leafpos, sz, idx, out.bin, out.cap_bin,
+                     out.leaves, out.cap_leaves, out.wide, out.cap_wide, info);
+  (void)hipEventRecord(out.e1, s);
+  static_assert(sizeof(out.dev_info) == kInfoInts * sizeof(int), "dev_info holds the stage's counters");
+  if ((e = hipMemcpyAsync(out.dev_info, info, sizeof(out.dev_info), hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return (int)e;
+  return (int)hipGetLastError();
+}
+
+int lbvh_trees_finish(LbvhTrees& t) {
+  if (!t.base || !t.e0 || !t.e1) return (int)hipErrorInvalidValue;
+  hipError_t e = hipEventSynchronize(t.e1);  // long complete: the caller has synchronised the stream
+  if (e == hipSuccess) e = hipEventElapsedTime(&t.stage_ms, t.e0, t.e1);
+  (void)hipEventDestroy(t.e0);
+  (void)hipEventDestroy(t.e1);
+  t.e0 = t.e1 = nullptr;
+  if (e != hipSuccess) return (int)e;
+  if (t.dev_info[kInfoErr] || t.nbin() > t.cap_bin || t.nwide() > t.cap_wide || t.nleaves() > t.cap_leaves)
+    return (int)hipErrorInvalidValue;
+  return 0;
 }
 
 }  // namespace ptk

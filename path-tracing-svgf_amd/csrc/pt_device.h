@@ -516,5 +516,30 @@ constexpr TriLayout kRasterVerts{18, 6, 12};  // the raster vertex list (obj_loa
 int lbvh_build(LbvhWork& w, const float* tri, TriLayout lay, int n, int leaf_n, int ploc_r, float* tri_out,
                float* node_out, int* order, int* nnodes, hipStream_t s);
 
+// The walk trees of a tree lbvh_build wrote, derived on the device from its BVHNode_encoded texels (lbvh_trees):
+// the packed binary tree (capi.hip pack_bvh's records), the leaf list (upload_leaves') and the 4-wide tree
+// (pack_wide's greedy collapse), bit for bit what those host functions make of the same texels.
+struct LbvhTrees {
+  void* base = nullptr;  // one allocation: bin | leaves | wide (the owner frees it)
+  float4 *bin = nullptr, *leaves = nullptr, *wide = nullptr;
+  int cap_bin = 0, cap_leaves = 0, cap_wide = 0;  // records each part has room for
+  // what the device reports (one copy): root_ref, need (deepest interior level), leaves, root4, need4, 4-wide nodes,
+  // NaN flag (a child box of the 4-wide tree has a NaN coordinate), [7] unused; packed binary nodes; error bits
+  // (1: a child index out of range, 2: a record past its part's room)
+  int dev_info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float stage_ms = 0.0f;  // device time of the stage
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  uint64_t version = 0;  // the node texture's version these trees were derived from (capi.hip)
+  int nbin() const { return dev_info[8]; }
+  int nleaves() const { return dev_info[2]; }
+  int nwide() const { return dev_info[5]; }
+};
+// Launches the stage on s over `nodes` (nnodes x 12 floats on the device, dummy node 0, root node 1) and the copy of
+// dev_info; nothing is read back before lbvh_trees_finish, which the caller runs after its next synchronisation of s
+// (it fails when the texels were no tree). Only ever run on lbvh_build's own output. Scratch comes from w.
+int lbvh_trees_launch(LbvhWork& w, const float* nodes, int nnodes, LbvhTrees& out, hipStream_t s);
+int lbvh_trees_finish(LbvhTrees& t);
+void lbvh_trees_free(LbvhTrees& t);
+
 }  // namespace ptk
 #endif

@@ -126,6 +126,9 @@ _PT_SIGS = [
     ("pt_pass_draw_batch", C.c_int, [C.POINTER(_u32), C.c_int]),
     ("pt_pass_last_ms", C.c_int, [_u32, _fp]),
     ("pt_pass_destroy", C.c_int, [_u32]),
+    # include/ptsvgf_debug.h
+    ("pt_debug_lbvh_trees", C.c_int, [_u32, C.c_int, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_int)]),
 ]
 
 _PTS_SIGS = [

@@ -107,6 +107,29 @@ def bvh_build(tri_in: int, tri_out: int, node_out: int, leaf_n: int = 8, ploc_ra
     return n.value, ms.value
 
 
+LBVH_INFO_KEYS = ("root_ref", "need", "nleaves", "root4", "need4", "wide_nodes", "nan", "stage_us")
+
+
+def lbvh_trees(tex: int, source: int = 0) -> dict:
+    """pt_debug_lbvh_trees (include/ptsvgf_debug.h): the walk trees of a node buffer bvh_build wrote — source 0 the
+    buffers the device stage derived, 1 the host functions that define them run on the host mirror of the texels.
+    Returns {"binary": (k, 16), "leaves": (k, 8), "wide": (k, 28) float32 arrays, "info": the 8 ints} plus the ints
+    by name (LBVH_INFO_KEYS)."""
+    out = {}
+    info = (C.c_int * 8)()
+    for which, (name, width) in enumerate((("binary", 16), ("leaves", 8), ("wide", 28))):
+        nbytes = C.c_size_t()
+        check(pt().pt_debug_lbvh_trees(tex, source, which, None, 0, C.byref(nbytes), info))
+        a = np.zeros(nbytes.value // 4, np.float32)
+        if a.size:
+            check(pt().pt_debug_lbvh_trees(tex, source, which, a.ctypes.data_as(C.c_void_p), a.nbytes,
+                                           C.byref(nbytes), info))
+        out[name] = a.reshape(-1, width)
+    out["info"] = [int(v) for v in info]
+    out.update(zip(LBVH_INFO_KEYS, out["info"]))
+    return out
+
+
 class PtTileSeg(C.Structure):
     _fields_ = [("y_begin", C.c_int), ("y_end", C.c_int), ("offset", C.c_int), ("packed", C.c_void_p)]
 

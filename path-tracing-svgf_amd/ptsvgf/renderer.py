@@ -957,7 +957,9 @@ class Renderer:
         triangles) carries moved vertices; `raster` (the pre-BVH vertex list, obj_loader.h:143-160) moves the
         G-buffer's triangles with them; ploc_radius > 0 rebuilds the tree above the LBVH leaves by PLOC (0: the plain
         LBVH). Defaults: the fastest 4K walk measured (tools/dyn_sweep.py: leaves of <= 3, radius 32: 160 fps, against
-        146 for 8 / 16 and 126 for the plain LBVH). Frames already issued finish first. Returns (nodes, device ms)."""
+        146 for 8 / 16 and 126 for the plain LBVH; all over the binary walk). The build also derives the walk trees on
+        the device, among them the 4-wide tree the path tracer then walks (set_lbvh_wide; DESIGN.md "Dynamic scenes").
+        Frames already issued finish first. Returns (nodes, device ms, that derivation included)."""
         if self._streams is not None:
             import torch
 
@@ -981,6 +983,12 @@ class Renderer:
             for p in self.init_pass[1:]:  # the other G-buffer sets draw the same triangles: one tree
                 p.share_vertices(self.init_pass[0])
         return nodes, ms
+
+    def set_lbvh_wide(self, on: bool) -> None:
+        """Pass uniform lbvh_wide on every path-tracing slot: whether a scene rebuild_bvh built is walked through
+        the 4-wide tree derived with it (the default) or through its binary tree alone. Same image either way."""
+        for p, _ in self.pt_slots:
+            p.set_uniform_int("lbvh_wide", 1 if on else 0)
 
     def close(self) -> None:
         """Release every pass and texture this renderer created (the GL objects main.cpp never frees)."""
