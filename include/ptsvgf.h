@@ -173,6 +173,15 @@ int pt_raster_pass_bind(uint32_t pass, const float* vertices, size_t n_floats); 
  * builder (LBVH, PLOC top with ploc_radius > 0) and its records decoded on the device; the G-buffer does not depend
  * on the tree (closest t, ties to the lower original index), so the planes equal the host bind's bit for bit. */
 int pt_raster_pass_bind_device(uint32_t pass, const void* device_vertices, size_t n_floats, int ploc_radius);
+/* Dynamic scenes, no GL counterpart: the vertex list this (bound, not sharing) rasterize pass's triangles had one
+ * frame ago. Both lists are DEVICE pointers in pt_raster_pass_bind's layout with the bound triangle count and order.
+ * device_prev = NULL drops the records. While records are bound and the pass's int uniform object_motion is not 0
+ * (the default is 1), a surface pixel on a triangle that moved gets motion.xy measured to where its surface point was
+ * one frame ago, and motion.z = that point's change of linear depth under pre_viewproj, which svgf_reproject adds to
+ * this frame's depth before its history depth test; every other pixel is written as without records. The records
+ * are complete when the call returns; a bind drops them; passes sharing this pass's triangles read them too.
+ * PT_ERR_ARG for a wrong size, a sharing pass, an unbound pass or a non-raster pass. */
+int pt_raster_pass_set_prev_vertices(uint32_t pass, const void* device_prev, const void* device_cur, size_t n_floats);
 /* A rasterize pass drawing another (bound) rasterize pass's triangles and tree: the reference has one G-buffer pass;
  * a driver with several G-buffer targets (frames in flight) binds one and shares it. Rebinding `pass` ends the share;
  * destroying `src_pass` first makes `pass`'s draws fail with PT_ERR_STATE. */

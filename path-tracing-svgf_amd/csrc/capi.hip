@@ -86,6 +86,7 @@ struct Uniform {
 struct RasterScene {
   float4* geom = nullptr;
   float4* nrm = nullptr;
+  float4* disp = nullptr;  // pt_raster_pass_set_prev_vertices: displacement records beside nrm, or null
   float4* bvh = nullptr;
   int root_ref = 0;
   int stack_need = 0;
@@ -1295,6 +1296,14 @@ void free_scene(SceneGPU& sg) {
   }
 }
 
+// the displacement records of a rasterize pass (pt_raster_pass_set_prev_vertices), freed once no draw reads them
+static void drop_disp(Pass* p) {
+  if (!p->raster.disp) return;
+  (void)hipDeviceSynchronize();
+  (void)hipFree(p->raster.disp);
+  p->raster.disp = nullptr;
+}
+
 template <class T>
 int upload_vec(const std::vector<T>& v, T** dst) {
   if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
@@ -2004,6 +2013,8 @@ int draw_raster(Pass* p) {
   TRY(gbuf_flags(p, fwt, k));
   k.geom = rs.geom;
   k.nrm = rs.nrm;
+  // object motion: the source's displacement records, unless this pass's int uniform object_motion is 0
+  if (rs.disp && rs.ntris > 0 && ui(p, "object_motion", 1) != 0) k.disp = rs.disp;
   k.bvh = rs.bvh;
   k.root_ref = rs.root_ref;
   k.stack_need = rs.stack_need;
@@ -2259,6 +2270,7 @@ int pt_shutdown(void) {
     Pass* p = kv.second.get();
     if (p->raster.geom) (void)hipFree(p->raster.geom);
     if (p->raster.nrm) (void)hipFree(p->raster.nrm);
+    if (p->raster.disp) (void)hipFree(p->raster.disp);
     if (p->raster.bvh) (void)hipFree(p->raster.bvh);
     if (p->bins.base) (void)hipFree(p->bins.base);
     if (p->wf.base) (void)hipFree(p->wf.base);
@@ -2772,6 +2784,7 @@ int pt_raster_pass_bind(uint32_t pass, const float* verts, size_t n_floats) {
   if (g.programs[p->program] != PK_RASTER) return err(PT_ERR_ARG, "not a rasterize pass");
   if (n_floats % 18) return err(PT_ERR_ARG, "vertex list must be whole triangles of pos3+nrm3");
   int ntris = (int)(n_floats / 18);
+  drop_disp(p);  // the triangle order changes
   p->raster.ntris = ntris;
   p->raster_src = 0;
   p->bound = true;
@@ -2832,6 +2845,7 @@ int pt_raster_pass_bind_device(uint32_t pass, const void* dverts, size_t n_float
   if (n_floats / 18 > (1u << 24)) return err(PT_ERR_ARG, "more than 2^24 raster triangles");
   const int ntris = (int)(n_floats / 18);
   if (ntris > 0 && !dverts) return err(PT_ERR_ARG, "null device vertex list");
+  drop_disp(p);  // the triangle order changes
   p->raster.ntris = ntris;
   p->raster_src = 0;
   p->bound = true;
@@ -2892,6 +2906,38 @@ int pt_raster_pass_bind_device(uint32_t pass, const void* dverts, size_t n_float
   release();
   release_trees();
   if (e != hipSuccess) return hip_err(e, "pt_raster_pass_bind_device");
+  return PT_OK;
+}
+
+int pt_raster_pass_set_prev_vertices(uint32_t pass, const void* dprev, const void* dcur, size_t n_floats) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (g.programs[p->program] != PK_RASTER) return err(PT_ERR_ARG, "not a rasterize pass");
+  if (p->raster_src) return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: the pass shares another pass's triangles");
+  if (!p->bound) return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: raster pass not bound");
+  if (!dprev) {
+    drop_disp(p);
+    return PT_OK;
+  }
+  if (n_floats != (size_t)p->raster.ntris * 18)
+    return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: not the bound triangle count");
+  if (!dcur) return err(PT_ERR_ARG, "null device vertex list");
+  drop_disp(p);
+  const int ntris = p->raster.ntris;
+  if (ntris == 0) return PT_OK;
+  if (!p->raster.geom) return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: raster pass not bound");
+  float4* disp = nullptr;
+  HIPCHK(hipMalloc((void**)&disp, (size_t)ntris * 3 * sizeof(float4)));
+  const int rc = ptk::raster_disp(p->raster.geom, (const float*)dprev, (const float*)dcur, ntris, disp, g.stream);
+  // draws of other frames may run on other streams: the records are complete when this returns
+  const hipError_t e = rc ? (hipError_t)rc : hipStreamSynchronize(g.stream);
+  if (e != hipSuccess) {
+    (void)hipFree(disp);
+    return hip_err(e, "pt_raster_pass_set_prev_vertices");
+  }
+  p->raster.disp = disp;
   return PT_OK;
 }
 
@@ -3170,6 +3216,7 @@ int pt_pass_destroy(uint32_t pass) {
   Pass* p = it->second.get();
   if (p->raster.geom) (void)hipFree(p->raster.geom);
   if (p->raster.nrm) (void)hipFree(p->raster.nrm);
+  if (p->raster.disp) (void)hipFree(p->raster.disp);
   if (p->raster.bvh) (void)hipFree(p->raster.bvh);
   if (p->bins.base) (void)hipFree(p->bins.base);
   if (p->wf.base) (void)hipFree(p->wf.base);

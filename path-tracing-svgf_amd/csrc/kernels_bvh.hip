@@ -465,6 +465,34 @@ __global__ void __launch_bounds__(256) decode_raster_kernel(const float* __restr
   nrm[3 * k + 2] = float4{f[15], f[16], f[17], 0.0f};
 }
 
+// Displacement records of a bound rasterize pass (pt_raster_pass_set_prev_vertices): per triangle in leaf order, its
+// three vertices' prev - cur of the two vertex lists (original order, geom[4k].w = the original index); .w = 1 when
+// any of the nine components is non-zero (the moved flag gb_finish branches on). An index outside the lists (not
+// written by either bind) leaves a zero record.
+__global__ void __launch_bounds__(256) raster_disp_kernel(const float4* __restrict__ geom,
+                                                           const float* __restrict__ prev,
+                                                           const float* __restrict__ cur, int n,
+                                                           float4* __restrict__ disp) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const int oi = __float_as_int(geom[4 * k].w);
+  float d[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool moved = false;
+  if (oi >= 0 && oi < n) {
+    const float *a = prev + (size_t)oi * 18, *b = cur + (size_t)oi * 18;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        d[3 * j + c] = a[6 * j + c] - b[6 * j + c];
+        moved = moved || d[3 * j + c] != 0.0f;
+      }
+  }
+  const float w = moved ? 1.0f : 0.0f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) disp[3 * k + j] = float4{d[3 * j], d[3 * j + 1], d[3 * j + 2], w};
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Walk trees of a built tree (lbvh_trees_launch): the packed binary tree, the leaf list and the 4-wide tree the
 // traversal kernels read, derived from the BVHNode_encoded texels without a trip through the host. Their content is
@@ -754,6 +782,12 @@ __global__ void __launch_bounds__(256) trees_emit(const float* __restrict__ node
 int decode_raster(const float* verts, const int* order, int n, float4* geom, float4* nrm, hipStream_t s) {
   if (n <= 0) return 0;
   hipLaunchKernelGGL(decode_raster_kernel, dim3((n + 255) / 256), dim3(256), 0, s, verts, order, n, geom, nrm);
+  return (int)hipGetLastError();
+}
+
+int raster_disp(const float4* geom, const float* prev, const float* cur, int n, float4* disp, hipStream_t s) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(raster_disp_kernel, dim3((n + 255) / 256), dim3(256), 0, s, geom, prev, cur, n, disp);
   return (int)hipGetLastError();
 }
 

@@ -192,28 +192,50 @@ __device__ __forceinline__ v3 gb_dir(const GBufParams& p, int x, int y) {
 __device__ __forceinline__ void mat_vec4(const float* m, v3 P, float* o) {
   for (int r = 0; r < 4; ++r) o[r] = (m[r] * P.x + m[4 + r] * P.y) + (m[8 + r] * P.z + m[12 + r] * 1.0f);
 }
-__device__ __forceinline__ float lin_z(const GBufParams& p, v3 P) {
+__device__ __forceinline__ float lin_z_of(const float* m, v3 P) {
   float c[4];
-  mat_vec4(p.M, P, c);
+  mat_vec4(m, P, c);
   float zw = (c[2] / c[3]) * 0.5f + 0.5f;
   float fw = 1.0f / c[3];
   return zw / fw;
 }
+__device__ __forceinline__ float lin_z(const GBufParams& p, v3 P) { return lin_z_of(p.M, P); }
 
 // The G-buffer texels of pixel (x, y) from its closest front-facing hit (bests: geom index, best: t, (bu, bv):
 // barycentrics; bests < 0: background) and the wave's motion bound. Called by the whole wave (invalid lanes too).
+// OM (object motion, p.disp bound): a hit on a triangle whose displacement record is flagged moved was at
+// prevP = P + D one frame ago, D its vertices' displacements at the hit's barycentrics; its motion is measured to
+// prevP's old projection, and motion.z is the object's own share of the depth change (reproject_kernel adds it to
+// this frame's depth before the history depth test). Every other hit takes the OM = false statements.
+template <bool OM>
 __device__ __forceinline__ void gb_finish(const GBufParams& p, int x, int y, bool valid, int ln, v3 o, v3 d,
                                           float best, int bests, float bu, float bv) {
-  if (p.motion_max) {  // band planning (pt_pass_set_motion_bound): wave max of |motion.y|, one atomic per wave
-    float mv = 0.0f;
-    if (valid && bests >= 0) {  // the motion written below, recomputed for this lane
-      const v3 P = add(o, muls(d, best));
-      float c[4], pc[4];
-      mat_vec4(p.M, P, c);
-      mat_vec4(p.PV, P, pc);
-      mv = f_abs(((c[1] / c[3]) * 0.5f + 0.5f) - ((pc[1] / pc[3]) * 0.5f + 0.5f));
-      if (!(mv <= 3.0e38f)) mv = __builtin_inff();  // NaN / inf: unbounded
+  const bool surf = valid && bests >= 0;
+  const v3 P = add(o, muls(d, best));
+  float mox = 0.0f, moy = 0.0f, moz = 0.0f;  // the motion texel written below (surface pixels)
+  if (surf) {
+    v3 Pp = P;
+    if (OM) {
+      const float4* dd = p.disp + 3 * bests;
+      const float4 d1 = dd[0];
+      if (d1.w != 0.0f) {
+        const float4 d2 = dd[1], d3 = dd[2];
+        const float w0 = (1.0f - bu) - bv;
+        Pp = add(P, add(add(muls(xyz(d1), w0), muls(xyz(d2), bu)), muls(xyz(d3), bv)));
+        moz = lin_z_of(p.PV, Pp) - lin_z_of(p.PV, P);
+      }
     }
+    float c[4], pc[4];
+    mat_vec4(p.M, P, c);
+    mat_vec4(p.PV, Pp, pc);
+    float nowx = (c[0] / c[3]) * 0.5f + 0.5f, nowy = (c[1] / c[3]) * 0.5f + 0.5f;
+    float prex = (pc[0] / pc[3]) * 0.5f + 0.5f, prey = (pc[1] / pc[3]) * 0.5f + 0.5f;
+    mox = nowx - prex;
+    moy = nowy - prey;
+  }
+  if (p.motion_max) {  // band planning (pt_pass_set_motion_bound): wave max of |motion.y|, one atomic per wave
+    float mv = f_abs(moy);
+    if (!(mv <= 3.0e38f)) mv = __builtin_inff();  // NaN / inf: unbounded
     uint32_t mb = __float_as_uint(mv);  // non-negative floats order as their bits
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) mb = max(mb, (uint32_t)__shfl_xor((int)mb, s));
@@ -237,14 +259,8 @@ __device__ __forceinline__ void gb_finish(const GBufParams& p, int x, int y, boo
     float w0 = (1.0f - u) - v;
     return add(add(muls(n1, w0), muls(n2, u)), muls(n3, v));
   };
-  v3 P = add(o, muls(d, best));
   v3 N = interp(bu, bv);
   float lz = lin_z(p, P);
-  float c[4], pc[4];
-  mat_vec4(p.M, P, c);
-  mat_vec4(p.PV, P, pc);
-  float nowx = (c[0] / c[3]) * 0.5f + 0.5f, nowy = (c[1] / c[3]) * 0.5f + 0.5f;
-  float prex = (pc[0] / pc[3]) * 0.5f + 0.5f, prey = (pc[1] / pc[3]) * 0.5f + 0.5f;
   v3 dx = gb_dir(p, x ^ 1, y), dy = gb_dir(p, x, y ^ 1);
   MTr hx = moller(p1, e1, e2, o, dx, false), hy = moller(p1, e1, e2, o, dy, false);
   v3 Nx = interp(hx.u, hx.v), Ny = interp(hy.u, hy.v);
@@ -255,7 +271,7 @@ __device__ __forceinline__ void gb_finish(const GBufParams& p, int x, int y, boo
   float fwz = f_max(f_abs(zx - lz), f_abs(zy - lz));
   pst(p.world, x, y, f4(P.x, P.y, P.z, 1.0f));
   pst(p.normal_depth, x, y, f4(N.x, N.y, N.z, lz));
-  pst(p.motion, x, y, f4(nowx - prex, nowy - prey, 0.0f, 1.0f));
+  pst(p.motion, x, y, f4(mox, moy, moz, 1.0f));
   pst(p.fwidth, x, y, f4(length(fwN), fwz, lz, 1.0f));
   if (p.fwidth_aux)  // .y, sign bit = (linearZ == 1.0): the a-trous background test (svgf_Atrous.frag:77)
     p.fwidth_aux[(size_t)prow(p.fwidth, y) * p.W + x] =
@@ -268,7 +284,7 @@ __device__ __forceinline__ void gb_finish(const GBufParams& p, int x, int y, boo
 // the rasteriser's overflow fallback (p.bins.ctr set) it has work only after an overflow and launches a few hundred
 // blocks (launch_gbuffer): one block per tile, each reading one flag and leaving, held its stream for ~0.14 ms of a
 // 4K frame.
-template <int KS>
+template <int KS, bool OM>
 __global__ void __launch_bounds__(kBlock) gbuffer_kernel(GBufParams p, int ntx, int nslots) {
   __shared__ int stk[KS * kBlock];
   if (p.bins.ctr && p.bins.ctr[2] == 0) return;  // the rasteriser's fallback, not needed
@@ -348,7 +364,7 @@ __global__ void __launch_bounds__(kBlock) gbuffer_kernel(GBufParams p, int ntx, 
     }
   }
   sched_cost(p.tiles, tile, steps);
-  gb_finish(p, x, y, valid, ln, o, d, best, bests, bu, bv);
+  gb_finish<OM>(p, x, y, valid, ln, o, d, best, bests, bu, bv);
   }
 }
 
@@ -484,6 +500,7 @@ __global__ void __launch_bounds__(256) rast_setup(GBufParams p) {
 }
 
 // one block per tile: the tile's list staged through LDS, every pixel's Moller tests, gb_finish
+template <bool OM>
 __global__ void __launch_bounds__(kBlock) gbuffer_raster_kernel(GBufParams p) {
   __shared__ float4 sg[kRChunk * 3];
   __shared__ int4 sbox[kRChunk];
@@ -534,7 +551,7 @@ __global__ void __launch_bounds__(kBlock) gbuffer_raster_kernel(GBufParams p) {
       }
     }
   }
-  gb_finish(p, x, y, valid, ln, o, d, best, bests, bu, bv);
+  gb_finish<OM>(p, x, y, valid, ln, o, d, best, bests, bu, bv);
 }
 
 // A G-buffer whose planes another process wrote (multi-GPU frame shard: the rank tracing the frame drew these rows of
@@ -564,7 +581,9 @@ int launch_gbuffer_raster(const GBufParams& p, hipStream_t s) {
   if (p.bins.n > 0) hipLaunchKernelGGL(rast_setup, dim3((p.bins.n + 255) / 256), dim3(256), 0, s, p);
   int rc = launch_bins(p.bins, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(gbuffer_raster_kernel, dim3(ntx, nty), dim3(kBlock), 0, s, p);
+  // a pass with displacement records bound draws through the object-motion instantiation (gb_finish)
+  if (p.disp) hipLaunchKernelGGL(gbuffer_raster_kernel<true>, dim3(ntx, nty), dim3(kBlock), 0, s, p);
+  else hipLaunchKernelGGL(gbuffer_raster_kernel<false>, dim3(ntx, nty), dim3(kBlock), 0, s, p);
   // the ray cast runs only if a list overflowed (it reads the flag and returns otherwise)
   return launch_gbuffer(p, s);
 }
@@ -602,9 +621,15 @@ int launch_gbuffer(const GBufParams& p, hipStream_t s) {
   const int ntx = (p.W + 15) / 16, nslots = ntx * ((p.y1 - p.y0 + 15) / 16);
   const int fix = p.bins.ctr ? gbuffer_fix_blocks() : 0;
   const dim3 grid(fix > 0 ? std::min(nslots, fix) : nslots);
-  if (p.stack_need <= kStackSmall)
-    hipLaunchKernelGGL(gbuffer_kernel<kStackSmall>, grid, dim3(kBlock), 0, s, p, ntx, nslots);
-  else hipLaunchKernelGGL(gbuffer_kernel<kStack>, grid, dim3(kBlock), 0, s, p, ntx, nslots);
+  const bool small = p.stack_need <= kStackSmall;
+  if (p.disp) {
+    if (small) hipLaunchKernelGGL((gbuffer_kernel<kStackSmall, true>), grid, dim3(kBlock), 0, s, p, ntx, nslots);
+    else hipLaunchKernelGGL((gbuffer_kernel<kStack, true>), grid, dim3(kBlock), 0, s, p, ntx, nslots);
+  } else if (small) {
+    hipLaunchKernelGGL((gbuffer_kernel<kStackSmall, false>), grid, dim3(kBlock), 0, s, p, ntx, nslots);
+  } else {
+    hipLaunchKernelGGL((gbuffer_kernel<kStack, false>), grid, dim3(kBlock), 0, s, p, ntx, nslots);
+  }
   return (int)hipGetLastError();
 }
 

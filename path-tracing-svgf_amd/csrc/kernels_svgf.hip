@@ -119,6 +119,9 @@ __global__ void __launch_bounds__(256) PT_REPROJ_ATTR reproject_kernel(ReprojPar
   float ipx = uvx - mo.x, ipy = uvy - mo.y;
   v3 n = mk(cnd.x, cnd.y, cnd.z);
   float z = cnd.w;
+  // the depth this surface point had one frame ago, camera motion aside: motion.z is the object's own share of the
+  // depth change (gb_finish; 0.0 unless the G-buffer pass has displacement records bound)
+  const float zh = z + mo.z;
   float pI[4] = {0.f, 0.f, 0.f, 0.f}, pM[2] = {0.f, 0.f};
   const float ox[4] = {0.0f, p.inv_w, 0.0f, p.inv_w};
   const float oy[4] = {0.0f, 0.0f, p.inv_h, p.inv_h};
@@ -143,7 +146,7 @@ __global__ void __launch_bounds__(256) PT_REPROJ_ATTR reproject_kernel(ReprojPar
       const float4 q[4] = {lin_tap<0>(B, bt[0]), lin_tap<1>(B, bt[1]), lin_tap<2>(B, bt[2]), lin_tap<3>(B, bt[3])};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        v[k] = reprj_valid(ipx + ox[k], ipy + oy[k], z, q[k].w, fw.y, n, mk(q[k].x, q[k].y, q[k].z), fw.x,
+        v[k] = reprj_valid(ipx + ox[k], ipy + oy[k], zh, q[k].w, fw.y, n, mk(q[k].x, q[k].y, q[k].z), fw.x,
                            p.depth_thr, p.normal_thr);
         valid = valid || v[k];
       }
@@ -185,7 +188,7 @@ __global__ void __launch_bounds__(256) PT_REPROJ_ATTR reproject_kernel(ReprojPar
     for (int k = 0; k < 4; ++k) {
       float lx = ipx + ox[k], ly = ipy + oy[k];
       float4 q = lin(p.prev_nd, W, H, lx, ly);
-      v[k] = reprj_valid(lx, ly, z, q.w, fw.y, n, mk(q.x, q.y, q.z), fw.x, p.depth_thr, p.normal_thr);
+      v[k] = reprj_valid(lx, ly, zh, q.w, fw.y, n, mk(q.x, q.y, q.z), fw.x, p.depth_thr, p.normal_thr);
       valid = valid || v[k];
     }
     if (valid) {
@@ -214,7 +217,7 @@ __global__ void __launch_bounds__(256) PT_REPROJ_ATTR reproject_kernel(ReprojPar
       for (int xx = -1; xx <= 1; ++xx) {
         float lx = ipx + (float)xx * p.inv_w, ly = ipy + (float)yy * p.inv_h;
         float4 q = lin(p.prev_nd, W, H, lx, ly);
-        if (reprj_valid(lx, ly, z, q.w, fw.y, n, mk(q.x, q.y, q.z), fw.x, p.depth_thr, p.normal_thr)) {
+        if (reprj_valid(lx, ly, zh, q.w, fw.y, n, mk(q.x, q.y, q.z), fw.x, p.depth_thr, p.normal_thr)) {
           float4 qi = lin(p.prev_illum, W, H, lx, ly);
           float4 qm = lin(p.prev_moments, W, H, lx, ly);
           pI[0] += qi.x; pI[1] += qi.y; pI[2] += qi.z; pI[3] += qi.w;

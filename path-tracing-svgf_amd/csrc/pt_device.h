@@ -251,6 +251,7 @@ struct GBufParams {
   int tf_y0, tf_y1;       // the rows the a-trous passes draw (default: the G-buffer's own rows)
   const float4* geom;   // 4 x float4 per raster triangle (walk): (p1,idx)(e1,-)(e2,-)(Ng,-)
   const float4* nrm;    // 3 x float4 per raster triangle (closest hit only): n1, n2, n3
+  const float4* disp;   // object motion, or null: 3 x float4 per raster triangle, (prev - cur of vertex j, moved flag)
   const float4* bvh;
   int root_ref;
   int stack_need;       // deepest interior level of the raster BVH
@@ -504,6 +505,9 @@ int decode_tris(const float* te, int n, float4* geom, float4* shade, hipStream_t
 // Raster vertex list (18 floats per triangle) -> the G-buffer's geom (4 float4) / nrm (3 float4) records in the
 // given leaf order (order[k] = original triangle index), as pt_raster_pass_bind builds them on the host
 int decode_raster(const float* verts, const int* order, int n, float4* geom, float4* nrm, hipStream_t s);
+// Object motion: disp (3 float4 per raster triangle, leaf order) = prev - cur of the n-triangle vertex lists at each
+// record's original index (geom[4k].w), .w = 1 where the triangle moved
+int raster_disp(const float4* geom, const float* prev, const float* cur, int n, float4* disp, hipStream_t s);
 // Where a triangle record keeps its vertices: p1 at 0, p2 at o2, p3 at o3, records `stride` floats apart.
 struct TriLayout {
   int stride, o2, o3;

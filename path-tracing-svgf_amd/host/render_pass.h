@@ -105,5 +105,10 @@ class Rasterize_RenderPass : public RenderPass {
     for (GLuint t : colorAttachments) pt_check(pt_pass_add_color_attachment(handle(), t), "bindData");
     pt_check(pt_raster_pass_bind(handle(), vertices.data(), vertices.size()), "Rasterize_RenderPass::bindData");
   }
+  // Dynamic scenes (no reference counterpart): the device vertex list the bound triangles had one frame ago and the
+  // one bound now (n_floats each), for object motion vectors; prev = nullptr drops the records
+  void set_prev_vertices(const void* prev, const void* cur, size_t n_floats) {
+    pt_check(pt_raster_pass_set_prev_vertices(handle(), prev, cur, n_floats), "Rasterize_RenderPass::set_prev_vertices");
+  }
   void draw() { pt_check(pt_pass_draw(handle()), "draw"); }
 };

@@ -104,6 +104,7 @@ _PT_SIGS = [
     ("pt_pass_bind", C.c_int, [_u32, C.c_int]),
     ("pt_raster_pass_bind", C.c_int, [_u32, _fp, C.c_size_t]),
     ("pt_raster_pass_bind_device", C.c_int, [_u32, _vp, C.c_size_t, C.c_int]),
+    ("pt_raster_pass_set_prev_vertices", C.c_int, [_u32, _vp, _vp, C.c_size_t]),
     ("pt_raster_pass_share", C.c_int, [_u32, _u32]),
     ("pt_raster_pass_adopt", C.c_int, [_u32, C.c_int, C.c_int]),
     ("pt_tiles_count", C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int64)]),

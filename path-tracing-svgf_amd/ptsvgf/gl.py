@@ -305,6 +305,12 @@ class Rasterize_RenderPass(RenderPass):
         frame); derive the a-trous side data a draw makes, on the current library stream."""
         check(pt().pt_raster_pass_adopt(self._handle(), y0, y1))
 
+    def set_prev_vertices(self, prev_ptr, cur_ptr, n_floats: int) -> None:
+        """pt_raster_pass_set_prev_vertices: the device vertex list the bound triangles had one frame ago (and the
+        one bound now), for object motion vectors; prev_ptr None (or 0) drops the records."""
+        check(pt().pt_raster_pass_set_prev_vertices(self._handle(), C.c_void_p(prev_ptr or None),
+                                                    C.c_void_p(cur_ptr or None), n_floats))
+
     def share_vertices(self, src: "Rasterize_RenderPass") -> None:
         """pt_raster_pass_share: draw src's triangles and tree (src bound on its own)."""
         check(pt().pt_raster_pass_share(self._handle(), src._handle()))

@@ -274,6 +274,10 @@ class Renderer:
         # G-buffer (main.cpp:208-226); fast mode double-buffers it (prev normal/depth = other parity)
         self.init_pass = []
         self.gbuf = []
+        # object motion (rebuild_bvh(prev_raster=...)): records bound on init_pass[0]; the next frame draws with them
+        self.object_motion = True
+        self._motion_records = self._motion_pending = False
+        self._last_raster = np.ascontiguousarray(scene.raster, np.float32).reshape(-1)
         raster_prog = _prog("rasterize_frag.frag", "rasterize_vert.vert")
         for b in range(nbuf):
             g = dict(world=tex(W, H), normal_depth=tex(W, H), velocity=tex(W, H), fwidth=tex(W, H))
@@ -483,6 +487,9 @@ class Renderer:
         ip.set_uniform_mat4("projection", proj)
         ip.set_uniform_mat4("pre_viewproj", self.pre_viewproj)
         ip.set_uniform_uint("frameCounter", cam.frameCounter)
+        if self._motion_records:  # only the first frame after a rebuild_bvh(prev_raster=...) sees the objects move
+            ip.set_uniform_int("object_motion", 1 if self._motion_pending and self.object_motion else 0)
+            self._motion_pending = False
         if not self._draw_gbuffer:  # its planes come with the path tracer's (pt_source)
             return
         self._draw(ip, "gbuffer")
@@ -951,7 +958,7 @@ class Renderer:
             self._slot_free[f % self.K] = ev
 
     # --------------------------------------------------------- accessors ---
-    def rebuild_bvh(self, tri_enc=None, raster=None, leaf_n: int = 3, ploc_radius: int = 32):
+    def rebuild_bvh(self, tri_enc=None, raster=None, leaf_n: int = 3, ploc_radius: int = 32, prev_raster=None):
         """Dynamic scenes: rebuild the path tracer's BVH on the GPU (pt_bvh_build) into the scene
         buffers the passes are bound to. `tri_enc` (Triangle_encoded rows, any order; default: the scene's
         triangles) carries moved vertices; `raster` (the pre-BVH vertex list, obj_loader.h:143-160) moves the
@@ -959,6 +966,11 @@ class Renderer:
         LBVH). Defaults: the fastest 4K walk measured (tools/dyn_sweep.py: leaves of <= 3, radius 32: 160 fps, against
         146 for 8 / 16 and 126 for the plain LBVH; all over the binary walk). The build also derives the walk trees on
         the device, among them the 4-wide tree the path tracer then walks (set_lbvh_wide; DESIGN.md "Dynamic scenes").
+        `prev_raster` (with `raster`: the vertex list the same triangles had one frame ago, or True for the list of
+        the previous rebuild_bvh call) gives the next frame object motion vectors (pt_raster_pass_set_prev_vertices):
+        the first frame issued after the rebuild draws its G-buffer with object_motion = 1, so SVGF and TAA fetch a
+        moved object's history from where it was; later frames draw with 0 (the geometry is stationary again, the
+        planes those of a plain bind). `self.object_motion = False` keeps every frame at 0.
         Frames already issued finish first. Returns (nodes, device ms, that derivation included)."""
         if self._streams is not None:
             import torch
@@ -977,9 +989,19 @@ class Renderer:
             # rasteriser walks it only when a tile list overflows
             import torch
 
-            v = torch.from_numpy(np.ascontiguousarray(raster, np.float32).reshape(-1)).cuda()
+            cur = np.ascontiguousarray(raster, np.float32).reshape(-1)
+            if prev_raster is True:
+                prev_raster = self._last_raster
+            self._last_raster = cur
+            v = torch.from_numpy(cur).cuda()
             torch.cuda.synchronize()
-            self.init_pass[0].rebind_vertices_device(v.data_ptr(), v.numel(), 0)
+            self.init_pass[0].rebind_vertices_device(v.data_ptr(), v.numel(), 0)  # drops displacement records
+            self._motion_records = self._motion_pending = False
+            if prev_raster is not None:
+                pv = torch.from_numpy(np.ascontiguousarray(prev_raster, np.float32).reshape(-1)).cuda()
+                torch.cuda.synchronize()
+                self.init_pass[0].set_prev_vertices(pv.data_ptr(), v.data_ptr(), v.numel())
+                self._motion_records = self._motion_pending = True
             for p in self.init_pass[1:]:  # the other G-buffer sets draw the same triangles: one tree
                 p.share_vertices(self.init_pass[0])
         return nodes, ms
