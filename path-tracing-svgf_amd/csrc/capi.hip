@@ -235,6 +235,9 @@ struct SceneGPU {
   float4* bvh_any = nullptr;  // any-hit tree over the reference leaves (build_anyhit_tree)
   float4* leaves = nullptr;   // the reference leaves: (box lo, leaf ref bits), (box hi, 0) (wf_primary_raster)
   int nleaves = 0;
+  int* tri_leaf = nullptr;    // per triangle: its reference leaf's index in `leaves` (wf_primary_tri); always owned
+  int tri_leaf_cap = 0;       // triangles tri_leaf has room for
+  bool tri_shared = false;    // host-built trees: some triangle lies in two leaves (upload_leaves)
   int root_any = 0, need_any = 0;
   bool has4 = false;  // bvh4: the 4-wide form of bvh_any (pack_wide)
   bool nan4 = false;  // a child box of bvh4 has a NaN coordinate (PT_WIDE_SIGNED walks need lo <= hi: not walked)
@@ -338,6 +341,8 @@ struct NodeRaw {
 
 constexpr int kRefStack = 256;  // path_tracing.frag:378
 constexpr int kLbvhWideDefault = 1;  // pass uniform lbvh_wide (pt_params)
+// pass uniform primary_raster (pt_wf_setup): 2 = triangles binned to tiles (wf_primary_tri), 1 = reference leaves
+constexpr int kPrimaryRasterDefault = 2;
 
 // *need: deepest interior level (root = 1) = the most stack entries a walk holds
 int pack_bvh(const float* node_enc, int nnodes, std::vector<float4>& out, int* root_ref, int ntris, int* need) {
@@ -1294,6 +1299,24 @@ void free_scene(SceneGPU& sg) {
     if (*b) (void)hipFree(*b);
     *b = nullptr;
   }
+  if (sg.tri_leaf) (void)hipFree(sg.tri_leaf);
+  sg.tri_leaf = nullptr;
+  sg.tri_leaf_cap = 0;
+}
+
+// The triangle -> reference leaf map of a scene whose `leaves` were just built or rebuilt (on g.stream, after the
+// work that wrote them).
+static int build_tri_leaf(SceneGPU& sg, int ntris) {
+  if (ntris > sg.tri_leaf_cap) {
+    if (sg.tri_leaf) (void)hipFree(sg.tri_leaf);
+    sg.tri_leaf = nullptr;
+    sg.tri_leaf_cap = 0;
+    HIPCHK(hipMalloc((void**)&sg.tri_leaf, (size_t)ntris * sizeof(int)));
+    sg.tri_leaf_cap = ntris;
+  }
+  if (ntris <= 0) return PT_OK;
+  const int rc = ptk::launch_tri_leaf_map(sg.leaves, sg.nleaves, sg.tri_leaf, ntris, g.stream);
+  return rc ? hip_err((hipError_t)rc, "triangle leaf map") : PT_OK;
 }
 
 // the displacement records of a rasterize pass (pt_raster_pass_set_prev_vertices), freed once no draw reads them
@@ -1345,6 +1368,21 @@ static int upload_leaves(const float* ne, size_t nnodes, SceneGPU& sg) {
   std::vector<float4> lv;
   collect_leaves(ne, nnodes, lv);
   sg.nleaves = (int)(lv.size() / 2);
+  // the triangle rasteriser tests a triangle once, under its one leaf's box: a tree whose leaf ranges overlap (the
+  // reference would test the shared triangles once per leaf) keeps the leaf rasteriser (pt_wf_setup)
+  std::vector<char> seen;
+  sg.tri_shared = false;
+  for (size_t l = 0; l < lv.size(); l += 2) {
+    int ref;
+    memcpy(&ref, &lv[l].w, 4);
+    const int first = (-(ref + 1)) >> 4, n = (-(ref + 1)) & 15;
+    if (first < 0) continue;
+    if (seen.size() < (size_t)first + n) seen.resize((size_t)first + n, 0);
+    for (int k = first; k < first + n; ++k) {
+      sg.tri_shared = sg.tri_shared || seen[k];
+      seen[k] = 1;
+    }
+  }
   return upload_vec(lv, &sg.leaves);
 }
 
@@ -1368,6 +1406,7 @@ int get_scene_lbvh(Texture* tris, Texture* nodes, SceneGPU& sg, SceneGPU** out) 
   sg.bvh4 = t->wide;
   sg.leaves = t->leaves;
   sg.nleaves = t->nleaves();
+  sg.tri_shared = false;  // the LBVH's leaves are disjoint ranges of the Morton order
   const int root = t->dev_info[0];
   sg.stack_need = sg.need_any = t->dev_info[1];
   sg.root_any = root;
@@ -1382,6 +1421,7 @@ int get_scene_lbvh(Texture* tris, Texture* nodes, SceneGPU& sg, SceneGPU** out) 
   HIPCHK(hipMalloc((void**)&sg.geom, std::max<size_t>(ntris, 1) * 4 * sizeof(float4)));
   HIPCHK(hipMalloc((void**)&sg.shade, std::max<size_t>(ntris, 1) * 9 * sizeof(float4)));
   HIPCHK((hipError_t)ptk::decode_tris((const float*)tris->dev, (int)ntris, sg.geom, sg.shade, g.stream));
+  if (const int rc = build_tri_leaf(sg, (int)ntris)) return rc;
   sg.root_ref = root;
   sg.ntris = (int)ntris;
   sg.tri_ver = tris->version;
@@ -1456,6 +1496,7 @@ int get_scene(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU*
     }
   }
   if ((rc = upload_leaves((const float*)nodes->host.data(), nnodes, sg)) != PT_OK) return rc;
+  if ((rc = build_tri_leaf(sg, (int)ntris)) != PT_OK) return rc;
   if ((rc = upload_vec(geom, &sg.geom)) != PT_OK) return rc;
   if ((rc = upload_vec(shade, &sg.shade)) != PT_OK) return rc;
   if (bvh.empty()) bvh.push_back(float4{0, 0, 0, 0});
@@ -1711,6 +1752,7 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg) {
   k.scene.ntris = sg->ntris;
   k.scene.leaves = sg->leaves;
   k.scene.nleaves = sg->nleaves;
+  k.scene.tri_leaf = sg->tri_leaf;
   if (lt && lt->target == PT_TEXTURE_BUFFER) {
     k.scene.lights = (const float*)lt->dev;
     k.scene.nlights_buf = (int)(lt->bytes / (6 * sizeof(float)));
@@ -1839,11 +1881,14 @@ int pt_wf_setup(Pass* p, PTParams& k, SceneGPU* sg, const WFState& st) {
     k.list_grid = std::max(0, ui(p, "list_grid", 0));
     const int ntiles = wf_subset_tiles(k.W, std::max(0, k.y1 - k.y0), k.tile_stride, k.tile_offset);  // wf_primary's grid
     TRY(tile_order_begin(p, ntiles, &k.tiles));
-    // primary rays by tile-binned rasterisation of the reference leaves (default; 0 = the per-pixel walk); the leaves
-    // are binned to every tile of the band, a tile subset rasterises its own tiles
-    if (ui(p, "primary_raster", 1)) {
-      TRY(bins_for(p->bins, sg->nleaves, k.W, k.y0, k.y1, ui(p, "raster_pair_cap", 0), &k.leaf_bins));
-      k.primary_raster = 1;
+    // primary rays by tile-binned rasterisation: 1 = of the reference leaves, 2 = of the triangles; 0 = the per-pixel
+    // walk. The items are binned to every tile of the band, a tile subset rasterises its own tiles
+    const int pr = ui(p, "primary_raster", kPrimaryRasterDefault);
+    if (pr) {
+      // (the triangle rasteriser packs pixel coordinates into 16 bits)
+      const bool tri = pr == 2 && !sg->tri_shared && k.W <= 65536 && k.H <= 65536;
+      TRY(bins_for(p->bins, tri ? sg->ntris : sg->nleaves, k.W, k.y0, k.y1, ui(p, "raster_pair_cap", 0), &k.leaf_bins));
+      k.primary_raster = tri ? 2 : 1;
     }
     return PT_OK;
 }

@@ -131,6 +131,9 @@ struct SceneDev {
   // rasteriser's items (wf_primary_raster)
   const float4* leaves;
   int nleaves;
+  // per triangle of tri_geom: the index into `leaves` of the reference leaf holding it, -1 for a triangle no leaf
+  // holds (launch_tri_leaf_map); the triangle rasteriser's items are the triangles (wf_primary_tri)
+  const int* tri_leaf;
 };
 
 // Wavefront path-tracer state (kernels_wavefront.hip): SoA per band pixel.
@@ -234,9 +237,10 @@ struct PTParams {
   // offset 0 = every tile. Interleaved subsets give every rank of a multi-GPU frame an equal share of the
   // expensive tiles (ptsvgf.dist, DESIGN.md "Multi-GPU").
   int tile_stride, tile_offset;
-  // primary rays by tile rasterisation of the reference leaves (wf_primary_raster; primary_raster uniform): the
-  // bins, and for the wf_primary launch that follows it the bins' counters (pr_fix non-null: that launch walks
-  // only the pixels the rasteriser flagged — exact-t ties — or every pixel after a list overflow)
+  // primary rays by tile rasterisation (primary_raster uniform) of the reference leaves (1: wf_primary_raster) or of
+  // the triangles (2: wf_primary_tri): the bins of those items, and for the wf_primary launch that follows it the
+  // bins' counters (pr_fix non-null: that launch walks only the pixels the rasteriser flagged — exact-t ties — or
+  // every pixel after a list overflow)
   Bins leaf_bins;
   int primary_raster;
   const int* pr_fix;
@@ -376,6 +380,8 @@ int launch_gbuffer(const GBufParams& p, hipStream_t s);
 int launch_gbuffer_raster(const GBufParams& p, hipStream_t s);
 int launch_gbuffer_adopt(const GBufParams& p, hipStream_t s);  // side data of G-buffer planes written elsewhere  // bins, resolves, and the ray cast on overflow
 int launch_bins(const Bins& b, hipStream_t s);  // after the item setup kernel: large items, scan, scatter
+// SceneDev::tri_leaf of `ntris` triangles from the `nleaves` reference leaves' refs (first, count)
+int launch_tri_leaf_map(const float4* leaves, int nleaves, int* tri_leaf, int ntris, hipStream_t s);
 // nb frames' path tracing with batched traversal launches (ps[b]: frame b, its wavefront state at pid offset b * n)
 int launch_pathtrace_wavefront_batch(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk = nullptr);
 int launch_reproject(const ReprojParams& p, hipStream_t s);
@@ -412,11 +418,12 @@ struct TileBox {
 __device__ __forceinline__ TileBox tile_box(const Bins& b, int4 box) {
   return TileBox{box.x / kRTile, box.z / kRTile, (box.y - b.y0) / kRTile, (box.w - b.y0) / kRTile};
 }
-// Pixel box of projected extents (pixel coordinates of the centre rays), widened by kBoxMargin, clipped to the band.
-__device__ __forceinline__ int4 pixel_box(const Bins& b, float x0, float y0, float x1, float y1) {
+// Pixel box of projected extents (pixel coordinates of the centre rays), widened by `margin`, clipped to the band.
+__device__ __forceinline__ int4 pixel_box(const Bins& b, float x0, float y0, float x1, float y1,
+                                          int margin = kBoxMargin) {
   const float lim = 1.0e8f;  // keeps the float -> int conversion in range
-  const int bx0 = (int)floorf(fmaxf(x0, -lim)) - kBoxMargin, bx1 = (int)ceilf(fminf(x1, lim)) + kBoxMargin;
-  const int by0 = (int)floorf(fmaxf(y0, -lim)) - kBoxMargin, by1 = (int)ceilf(fminf(y1, lim)) + kBoxMargin;
+  const int bx0 = (int)floorf(fmaxf(x0, -lim)) - margin, bx1 = (int)ceilf(fminf(x1, lim)) + margin;
+  const int by0 = (int)floorf(fmaxf(y0, -lim)) - margin, by1 = (int)ceilf(fminf(y1, lim)) + margin;
   return make_int4(max(bx0, 0), max(by0, b.y0), min(bx1, b.W - 1), min(by1, b.y1 - 1));
 }
 // Sutherland-Hodgman against s * w + sgn * c[axis] >= 0 (homogeneous coordinates: x, y, w)
@@ -439,7 +446,7 @@ __device__ __forceinline__ int clip_plane(const float3* in, int n, float3* out, 
 // rays have NDC ((2x+1)/W - 1, (2y+1)/H - 1) scaled by (sx, sy): clipped to the widened frustum first.
 // Returns false when nothing of it lies in front of the camera inside the frustum.
 __device__ __forceinline__ bool poly_box(const Bins& b, int H, float3* A, int n, float sx, float sy, int4* box,
-                                         float* tmin) {
+                                         float* tmin, int margin = kBoxMargin) {
   float3 B[16];
   n = clip_plane(A, n, B, 0, 1.0f);
   n = clip_plane(B, n, A, 0, -1.0f);
@@ -465,7 +472,7 @@ __device__ __forceinline__ bool poly_box(const Bins& b, int H, float3* A, int n,
     x0 = fminf(x0, px); x1 = fmaxf(x1, px);
     y0 = fminf(y0, py); y1 = fmaxf(y1, py);
   }
-  *box = pixel_box(b, x0, y0, x1, y1);
+  *box = pixel_box(b, x0, y0, x1, y1, margin);
   *tmin = wmin;
   return true;
 }
