@@ -159,6 +159,11 @@ int pt_texarray_create(int width, int height, int layers, uint32_t* out_tex);   
 int pt_texarray_upload_layer(uint32_t tex, int layer, int width, int height, int channels,
                              const uint8_t* host_data);
 int pt_texture_readback(uint32_t tex, float* host_out, size_t bytes);             /* syncs the device */
+/* The compact one-float side plane of a 2-D texture's stored rows (width x rows floats): a depth-fwidth attachment's
+ * fwidth.y with the background flag in its sign bit; a world-position attachment's primary-ray bound, written by a
+ * rasterize draw with the vec3 uniform bound_eye set (+inf: none). *bytes receives its size, 0 when the texture holds
+ * none that matches its texels; it is copied to host_out when host_out is not NULL (cap: its room). Syncs the device. */
+int pt_texture_readback_aux(uint32_t tex, float* host_out, size_t cap, size_t* bytes);
 int pt_texture_upload_rgba(uint32_t tex, const float* host_rgba, size_t bytes);   /* raw RGBA32F rows */
 int pt_texture_device_ptr(uint32_t tex, void** out_ptr);
 int pt_texture_info(uint32_t tex, int* width, int* height, int* row0);

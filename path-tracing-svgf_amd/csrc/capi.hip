@@ -58,8 +58,11 @@ struct Texture {
   size_t bytes = 0;
   std::vector<uint8_t> host;  // buffers: host copy for decoding
   uint64_t version = 1;
-  float* aux = nullptr;  // compact depth-fwidth side plane
+  // compact one-float side plane of the stored rows: a depth-fwidth attachment's fwidth.y with the background flag, a
+  // world-position attachment's primary-ray bound for rays from aux_eye (draw_raster)
+  float* aux = nullptr;
   bool aux_valid = false;
+  float aux_eye[3] = {0.0f, 0.0f, 0.0f};
   unsigned char* tflags = nullptr;  // a-trous per-tile surface flags derived from aux (atrous_tile_flags)
   size_t tflags_cap = 0;
   uint64_t tflags_ver = 0;          // texture version / rows they were derived for
@@ -1619,6 +1622,7 @@ int copy_plane(Texture* dst, Texture* src, Pass* p, int y0, int y1) {
                             (size_t)(b - a) * rb, hipMemcpyDeviceToDevice, g.stream));
     }
     dst->aux_valid = true;
+    memcpy(dst->aux_eye, src->aux_eye, sizeof(dst->aux_eye));
   }
   return PT_OK;
 }
@@ -1852,6 +1856,11 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg) {
   if (hp && hn && ui(p, "primary_bound", 1)) {
     TRY(plane_of(hp, p, &k.hint_pos, "gWorldPos"));
     TRY(plane_of(hn, p, &k.hint_nd, "gNormalAndLinearZ"));
+    // the set's compact bound plane (written by the G-buffer draw, draw_raster) replaces the two-plane read when it
+    // was formed for this pass's eye; bound_plane = 0 keeps the two-plane read (A/B, tests). A set without one
+    // (adopted or uploaded planes, a draw without bound_eye) reads the two planes.
+    if (!k.hint_pos.aux || !ui(p, "bound_plane", 1) || memcmp(hp->aux_eye, k.eye, sizeof(k.eye)) != 0)
+      k.hint_pos.aux = nullptr;
   }
   // tile subset (PTParams::tile_stride): this pass traces every tile_stride-th 16 x 16 tile of the band
   k.tile_stride = ui(p, "tile_stride", 1);
@@ -1879,6 +1888,8 @@ int pt_wf_setup(Pass* p, PTParams& k, SceneGPU* sg, const WFState& st) {
     k.refill_waves = std::max(0, ui(p, "refill_waves", 0));
     k.refill_grid = std::max(0, ui(p, "refill_grid", 0));
     k.list_grid = std::max(0, ui(p, "list_grid", 0));
+    // 1: paths end in place (no wf_finalize, no wf_finish between two shades); 0 keeps those launches (A/B, tests)
+    k.shade_fold = ui(p, "shade_fold", 1) != 0;
     const int ntiles = wf_subset_tiles(k.W, std::max(0, k.y1 - k.y0), k.tile_stride, k.tile_offset);  // wf_primary's grid
     TRY(tile_order_begin(p, ntiles, &k.tiles));
     // primary rays by tile-binned rasterisation: 1 = of the reference leaves, 2 = of the triangles; 0 = the per-pixel
@@ -1979,7 +1990,8 @@ int draw_pathtrace_batch(Pass** ps, int n) {
     // compared at its effective value (the default pt_params / pt_wf_setup apply when a pass never set it)
     struct Same { const char* name; int dflt; };
     const Same same[] = {{"trace_refill", 0}, {"shadow_budget", 0}, {"closest_budget", 0}, {"wide_bvh", 1}, {"lbvh_wide", kLbvhWideDefault},
-                         {"refill_waves", 0}, {"trace_fork", 0}, {"refill_grid", 0}, {"list_grid", 0}};
+                         {"refill_waves", 0}, {"trace_fork", 0}, {"refill_grid", 0}, {"list_grid", 0},
+                         {"shade_fold", 1}};
     bool agree = true;
     for (const Same& u : same) agree = agree && ui(ps[b], u.name, u.dflt) == ui(ps[0], u.name, u.dflt);
     if (sb != sg || k[b].W != k[0].W || k[b].y0 != k[0].y0 || k[b].y1 != k[0].y1 || k[b].max_depth != k[0].max_depth ||
@@ -2056,6 +2068,19 @@ int draw_raster(Pass* p) {
   k.fwidth_aux = fwt->aux;
   // the a-trous per-tile surface flags of this G-buffer, marked by the G-buffer kernels as they write the pixels
   TRY(gbuf_flags(p, fwt, k));
+  // vec3 uniform bound_eye (the origin of this frame's primary rays): the draw also writes the primary rasterisers'
+  // pruning bound of every pixel into the world attachment's compact plane, 4 bytes instead of their 32 of texels
+  Texture* wt = tex_of(p->att[0]);
+  const Uniform* be = U(p, "bound_eye", 5);
+  if (be) {
+    if (!wt->aux) {  // rows no draw has reached hold "no bound"
+      const size_t n = (size_t)wt->W * wt->rows;
+      HIPCHK(hipMalloc((void**)&wt->aux, n * 4));
+      HIPCHK(hipMemsetD32Async((hipDeviceptr_t)wt->aux, 0x7f800000, n, g.stream));
+    }
+    k.bound_aux = wt->aux;
+    memcpy(k.bound_eye, be->f, sizeof(k.bound_eye));
+  }
   k.geom = rs.geom;
   k.nrm = rs.nrm;
   // object motion: the source's displacement records, unless this pass's int uniform object_motion is 0
@@ -2097,6 +2122,10 @@ int draw_raster(Pass* p) {
     TRY(tile_order_finish(p, k.tiles));
   }
   fwt->aux_valid = true;
+  if (k.bound_aux) {
+    wt->aux_valid = true;
+    memcpy(wt->aux_eye, k.bound_eye, sizeof(wt->aux_eye));
+  }
   return PT_OK;
 }
 
@@ -2529,6 +2558,8 @@ int pt_texture2d_upload(uint32_t tex, int w, int h, uint32_t fmt, const float* d
   if (w != t->W || h != t->H) {  // glTexImage2D respecifies the image
     if (t->owned && t->dev) HIPCHK(hipFree(t->dev));
     if (!t->owned) return err(PT_ERR_ARG, "cannot resize a wrapped texture");
+    if (t->aux) (void)hipFree(t->aux);  // sized for the old image
+    t->aux = nullptr;
     t->W = w; t->H = h; t->row0 = 0; t->rows = h;
     if (g.band_h > 0 && w == g.band_w && h == g.band_h) { t->row0 = g.band_row0; t->rows = g.band_rows; }
     t->bytes = (size_t)w * t->rows * 16;
@@ -2643,6 +2674,20 @@ int pt_bvh_build(uint32_t tri_in, int leaf_n, int ploc_radius, uint32_t tri_out,
   (void)hipFree(nbuf);
   if (rc == PT_OK && out_nodes) *out_nodes = nodes;
   return rc;
+}
+
+int pt_texture_readback_aux(uint32_t tex, float* host_out, size_t cap, size_t* bytes) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  Texture* t = tex_of(tex);
+  if (!t || t->target != PT_TEXTURE_2D) return err(PT_ERR_INVALID_HANDLE, "invalid 2-D texture");
+  if (!bytes) return err(PT_ERR_ARG, "null bytes");
+  *bytes = t->aux && t->aux_valid ? (size_t)t->W * t->rows * 4 : 0;
+  if (!host_out || !*bytes) return PT_OK;
+  if (cap < *bytes) return err(PT_ERR_ARG, "aux buffer too small");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(host_out, t->aux, *bytes, hipMemcpyDeviceToHost));
+  return PT_OK;
 }
 
 int pt_debug_lbvh_trees(uint32_t node_tex, int source, int which, void* host_out, size_t cap, size_t* bytes,

@@ -249,6 +249,7 @@ __device__ __forceinline__ void gb_finish(const GBufParams& p, int x, int y, boo
     pst(p.motion, x, y, bg);
     pst(p.fwidth, x, y, bg);
     if (p.fwidth_aux) p.fwidth_aux[(size_t)prow(p.fwidth, y) * p.W + x] = -0.3f;  // .y with the zCenter == 1 flag
+    if (p.bound_aux) p.bound_aux[(size_t)prow(p.world, y) * p.W + x] = __builtin_inff();  // background: no bound
     return;
   }
   const float4* g = p.geom + 4 * bests;
@@ -276,6 +277,14 @@ __device__ __forceinline__ void gb_finish(const GBufParams& p, int x, int y, boo
   if (p.fwidth_aux)  // .y, sign bit = (linearZ == 1.0): the a-trous background test (svgf_Atrous.frag:77)
     p.fwidth_aux[(size_t)prow(p.fwidth, y) * p.W + x] =
         __uint_as_float(__float_as_uint(fwz) | (lz == 1.0f ? 0x80000000u : 0u));
+  if (p.bound_aux) {  // raster_bound's statements on the texels stored above (P, and lz as its background test);
+    float bound = __builtin_inff();  // +inf: no bound (raster_bound reads it as its own "none")
+    if (lz != 1.0f) {
+      const float dist = length(sub(P, mk(p.bound_eye[0], p.bound_eye[1], p.bound_eye[2])));
+      if (dist == dist) bound = dist * 1.001f + 1.0e-3f;
+    }
+    p.bound_aux[(size_t)prow(p.world, y) * p.W + x] = bound;
+  }
   // the a-trous tiles holding this surface pixel (their background-only peers copy without reading their flags)
   if (p.tflags && lz != 1.0f && y >= p.tf_y0 && y < p.tf_y1) atrous_mark_tiles(p.tflags, p.tf_off, p.W, x, y - p.tf_y0);
 }

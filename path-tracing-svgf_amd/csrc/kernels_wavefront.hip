@@ -5,6 +5,9 @@
 //   per bounce i:  trace_closest -> shade -> trace_shadow (HDR + point light) -> finish
 //   then          finalize (clamp / NaN / accumulate / store)
 //
+// With shade_fold (the default) a path's colour is stored where the path ends, in the shade or the last bounce's
+// finish, and a bounce's finish runs at the top of the next bounce's shade: no finalize, one finish per frame.
+//
 // Rays that stay alive are compacted into a list with one wave-ballot atomic per
 // wave, so traversal waves carry only live rays (58 % of the 4K frame is sky).
 // The arithmetic per pixel is exactly the megakernel's (and the reference's):
@@ -388,7 +391,12 @@ __global__ void __launch_bounds__(256) pr_setup(PTParams p) {
 // margin) are sought; a pixel that finds none below it is flagged for the walk (which retries unbounded).
 __device__ __forceinline__ float raster_bound(const PTParams& p, bool valid, int x, int y, v3 S) {
   float bound = PT_INF;
-  if (valid && p.hint_pos.p && p.prune) {
+  if (valid && p.hint_pos.aux && p.prune) {
+    // the G-buffer pass formed this float from the same texels and this eye with the statements below (gb_finish;
+    // pt_params binds the plane only for that eye): 4 bytes per pixel instead of two float4 texels. +inf: none
+    const float b = p.hint_pos.aux[(size_t)prow(p.hint_pos, y) * p.hint_pos.W + x];
+    if (b != __builtin_inff()) bound = b;
+  } else if (valid && p.hint_pos.p && p.prune) {
     const float4 nd = pld(p.hint_nd, x, y);
     if (nd.w != 1.0f) {
       const float dist = length(sub(xyz(pld(p.hint_pos, x, y)), S));
@@ -1453,33 +1461,75 @@ __device__ __forceinline__ bool zero_bits(v3 a) {  // all three exactly +0.0f
   return (__float_as_uint(a.x) | __float_as_uint(a.y) | __float_as_uint(a.z)) == 0u;
 }
 
+// A path's end: wf_finalize's statements for the radiance `light` of pixel (x, y).
+__device__ __forceinline__ void terminal_write(const PTParams& p, int x, int y, v3 light) {
+  light = vclamp(light, 0.0f, p.clamp_threshold);  // :1110-1113
+  v3 color = splat(0.0f);
+  if (!f_isnan(light.x) && !f_isnan(light.y) && !f_isnan(light.z)) color = light;
+  if (p.accumulate && p.last.p) {  // :1116-1119
+    float4 lc = pld(p.last, x, y);
+    color = mixv(xyz(lc), color, 1.0f / (float)(p.frameCounter + 1u));
+  }
+  pst(p.color, x, y, f4(color.x, color.y, color.z, 1.0f));
+}
+// A bounce's shadow verdicts applied to the path of pixel `pid`: wf_finish's statements on (red, light).
+__device__ __forceinline__ void finish_apply(const PTParams& p, int pid, v3* red_io, v3* light_io) {
+  float4 q0 = ldnt(&p.wf.pend0[pid]), q1 = ldnt(&p.wf.pend1[pid]), q2 = ldnt(&p.wf.pend2[pid]), q3 = ldnt(&p.wf.pend3[pid]);
+  NeeTerms nt;
+  nt.hcalc = xyz(q0); nt.pcalc = xyz(q1); nt.bcalc = xyz(q2);
+  nt.hpdf = q0.w; nt.bpdf = q1.w;
+  nt.ppdf = p.pointLightSize != 0 ? (2.0f * PT_PI) / (float)p.pointLightSize : 0.0f;
+  v3 cosb = xyz(q3);
+  v3 red = *red_io, light = *light_io;
+  v3 hitLight = nee_hit_light(red, nt, p.wf.occ_h[pid] != 0, p.wf.occ_p[pid] != 0);
+  red = mul(red, divs(cosb, nt.bpdf));
+  light = add(light, hitLight);
+  *red_io = red;
+  *light_io = light;
+}
+
 // ------------------------------------------------------------------ shade ---
 // Bounce i: consume the closest hit of the ray in (ray_o, ray_d); on a hit,
 // sample the next direction and prepare both NEE contributions (:948-968).
 // Shadow rays whose verdict cannot change a bit of the result (a light below the
 // surface: zero BRDF) are not queued; the others go to one compacted list.
 #ifndef PT_SHADE_WAVES
-#define PT_SHADE_WAVES 0  // waves/SIMD wf_shade is compiled for (0: the compiler's choice, 93 VGPRs = 5 waves)
+// waves/SIMD wf_shade is compiled for, at least (0: the compiler's choice). 4: the folded shades of later bounces,
+// left to the compiler, take 152 / 148 VGPRs = 3 waves; held to 4 they fit 128 VGPRs with 20 / 12 bytes of private
+// segment (the unfolded kernel: 128 VGPRs either way). The first-bounce instantiations take 84 / 82 = 5 waves.
+#define PT_SHADE_WAVES 4
 #endif
 #if PT_SHADE_WAVES > 0
 #define PT_SHADE_ATTR __attribute__((amdgpu_waves_per_eu(PT_SHADE_WAVES)))
 #else
 #define PT_SHADE_ATTR
 #endif
-__global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bounce, const int* __restrict__ list_in,
+// FOLD (uniform shade_fold): paths end where they end. A path that ends in this shade (a miss, a hit that pushes no
+// ray) writes its pixel's `color` itself (terminal_write) and stores no state; a shade after the first applies the
+// previous bounce's shadow verdicts in registers (finish_apply: the wf_finish launch between two shades is gone); the
+// last bounce's wf_finish<true> writes `color` for the paths still alive, and wf_finalize is not launched. FIRST /
+// LAST (the bounce is the first / the last of the path; read only with FOLD) drop at compile time the loads the first
+// bounce does not have and the stores nothing reads after the last: ray_d and seed. `red` and `light` are still
+// stored on the last bounce's continuing paths, whose wf_finish<true> reads both. The statements and their order
+// per path are those of the unfolded launches, so every plane keeps its bits.
+template <bool FOLD, bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bounce_rt, const int* __restrict__ list_in,
                                                 const int* __restrict__ counts_in, int* __restrict__ list_out,
                                                 int* __restrict__ counts_out, int* __restrict__ shadow_out,
                                                 int* __restrict__ shadow_counts, int cap) {
+  // folded: bounce_rt is any bounce of the instantiation's kind; only `bounce == 0` is decided at compile time
+  const int bounce = FOLD && FIRST ? 0 : bounce_rt;
+  const bool first = FOLD ? FIRST : bounce == 0;
   // bounce 0: one tile per block. Later bounces: 256 list items per chunk, a block taking chunks blockIdx.x,
   // + gridDim.x, ... (a grid a multiple of kSeg: chunk c appends to segment c % kSeg, as one block per chunk did)
   int total = 0;
-  if (bounce > 0)
+  if (!first)
     for (int i = 0; i < kLiveBins * kSeg; ++i) total += counts_in[i];
-  for (int c = blockIdx.x; bounce == 0 || c * 256 < total; c += gridDim.x) {
+  for (int c = blockIdx.x; first || c * 256 < total; c += gridDim.x) {
     const int k = c * 256 + threadIdx.x;
     int pid = 0;
     bool valid;
-    if (bounce == 0) {
+    if (first) {
       // one 16 x 16 primary tile per block, in descending order of this frame's primary-ray cost
       // (tiles.perm_next, sorted right after wf_primary): the rays of expensive tiles are appended to
       // the lists first, so every later list-driven trace launch starts its slowest rays first
@@ -1501,7 +1551,7 @@ __global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bo
       v3 S, d;
       uint32_t seed;
       v3 light, red;
-      if (bounce == 0) {
+      if (first) {
         S = mk(p.eye[0], p.eye[1], p.eye[2]);
         d = primary_dir(p, x, y);
         seed = ((uint32_t)x * 1973u + (uint32_t)y * 9277u + p.frameCounter * 26699u) | 1u;  // :433-436
@@ -1515,16 +1565,18 @@ __global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bo
         seed = ldnt(&p.wf.seed[pid]);
         light = xyz(ldnt(&p.wf.light[pid]));
         red = xyz(ldnt(&p.wf.red[pid]));
+        if (FOLD) finish_apply(p, pid, &red, &light);  // the previous bounce's verdicts (its wf_finish)
       }
       if (hr.x < 0) {  // miss (:1084-1087)
         light = add(light, mul(hdr_color(p, d), red));
-        if (bounce == 0) {
+        if (first) {
           pst(p.emission, x, y, f4(0.0f, 0.0f, 0.0f, 1.0f));
           pst(p.albedo, x, y, f4(0.0f, 0.0f, 0.0f, 1.0f));
         }
+        if (FOLD) terminal_write(p, x, y, light);
       } else {
         Hit h = decode_hit(p.scene, hr.x, __int_as_float(hr.y), S, d);
-        if (bounce == 0) {
+        if (first) {
           pst(p.emission, x, y, f4(h.m.emissive.x, h.m.emissive.y, h.m.emissive.z, 1.0f));
           pst(p.albedo, x, y, f4(h.m.baseColor.x, h.m.baseColor.y, h.m.baseColor.z, 1.0f));
         }
@@ -1587,43 +1639,46 @@ __global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bo
           stnt(&p.wf.sh_h[pid], f4(hd.x, hd.y, hd.z, 0.0f));
           stnt(&p.wf.sh_p[pid], shp);
           stnt(&p.wf.ray_o[pid], f4(h.P.x, h.P.y, h.P.z, 0.0f));
-          stnt(&p.wf.ray_d[pid], f4(L.x, L.y, L.z, 0.0f));
+          if (!(FOLD && LAST)) stnt(&p.wf.ray_d[pid], f4(L.x, L.y, L.z, 0.0f));
           stnt(&p.wf.red[pid], f4(red.x, red.y, red.z, 0.0f));
           stnt(&p.wf.occ_h[pid], (uint8_t)0);
           stnt(&p.wf.occ_p[pid], (uint8_t)0);
+        } else if (FOLD) {
+          terminal_write(p, x, y, light);
         }
       }
-      stnt(&p.wf.seed[pid], seed);
-      stnt(&p.wf.light[pid], f4(light.x, light.y, light.z, 0.0f));
+      if (!FOLD || (push && !LAST)) stnt(&p.wf.seed[pid], seed);
+      if (!FOLD || push) stnt(&p.wf.light[pid], f4(light.x, light.y, light.z, 0.0f));
     }
     // HDR and point-light shadow rays go to separate lists so trace waves stay homogeneous
 
     block_push_shade(push, lbin, need_h, need_p, pbin, pid, list_out, counts_out, shadow_out, shadow_counts, cap, c);
-    if (bounce == 0) break;
+    if (first) break;
     __syncthreads();  // the next chunk's push reuses block_push_shade's shared counters
   }
 }
 
 // ----------------------------------------------------------------- finish ---
+// TERMINAL (the last bounce's finish with shade_fold): the path ends here, so its pixel's `color` is written
+// (terminal_write) and neither `red` nor `light` is stored.
+template <bool TERMINAL>
 __global__ void __launch_bounds__(256) wf_finish(PTParams p, const int* __restrict__ list,
                                                  const int* __restrict__ counts, int cap) {
   int total = 0;
   for (int i = 0; i < kLiveBins * kSeg; ++i) total += counts[i];
   for (int k = blockIdx.x * 256 + threadIdx.x; k < total; k += gridDim.x * 256) {
-  int pid;
-  if (!bins_get(list, counts, kLiveBins, cap, k, &pid)) continue;
-  float4 q0 = ldnt(&p.wf.pend0[pid]), q1 = ldnt(&p.wf.pend1[pid]), q2 = ldnt(&p.wf.pend2[pid]), q3 = ldnt(&p.wf.pend3[pid]);
-  NeeTerms nt;
-  nt.hcalc = xyz(q0); nt.pcalc = xyz(q1); nt.bcalc = xyz(q2);
-  nt.hpdf = q0.w; nt.bpdf = q1.w;
-  nt.ppdf = p.pointLightSize != 0 ? (2.0f * PT_PI) / (float)p.pointLightSize : 0.0f;
-  v3 cosb = xyz(q3);
-  v3 red = xyz(ldnt(&p.wf.red[pid])), light = xyz(ldnt(&p.wf.light[pid]));
-  v3 hitLight = nee_hit_light(red, nt, p.wf.occ_h[pid] != 0, p.wf.occ_p[pid] != 0);
-  red = mul(red, divs(cosb, nt.bpdf));
-  light = add(light, hitLight);
-  stnt(&p.wf.red[pid], f4(red.x, red.y, red.z, 0.0f));
-  stnt(&p.wf.light[pid], f4(light.x, light.y, light.z, 0.0f));
+    int pid;
+    if (!bins_get(list, counts, kLiveBins, cap, k, &pid)) continue;
+    v3 red = xyz(ldnt(&p.wf.red[pid])), light = xyz(ldnt(&p.wf.light[pid]));
+    finish_apply(p, pid, &red, &light);
+    if (TERMINAL) {
+      int x, y;
+      pix_xy(p, pid, &x, &y);
+      terminal_write(p, x, y, light);
+    } else {
+      stnt(&p.wf.red[pid], f4(red.x, red.y, red.z, 0.0f));
+      stnt(&p.wf.light[pid], f4(light.x, light.y, light.z, 0.0f));
+    }
   }
 }
 
@@ -1637,14 +1692,7 @@ __global__ void __launch_bounds__(256) wf_finalize(PTParams p) {
     const int t = ((y - p.y0) >> 4) * ((p.W + 15) / 16) + (x >> 4);
     if (t % p.tile_stride != p.tile_offset) return;
   }
-  v3 light = vclamp(xyz(ldnt(&p.wf.light[k])), 0.0f, p.clamp_threshold);  // :1110-1113
-  v3 color = splat(0.0f);
-  if (!f_isnan(light.x) && !f_isnan(light.y) && !f_isnan(light.z)) color = light;
-  if (p.accumulate && p.last.p) {  // :1116-1119
-    float4 lc = pld(p.last, x, y);
-    color = mixv(xyz(lc), color, 1.0f / (float)(p.frameCounter + 1u));
-  }
-  pst(p.color, x, y, f4(color.x, color.y, color.z, 1.0f));
+  terminal_write(p, x, y, xyz(ldnt(&p.wf.light[k])));
 }
 
 // A producer block appends at most 256 items to the segment blockIdx % kSeg; the most blocks
@@ -1664,7 +1712,8 @@ int wf_subset_tiles(int W, int rows, int stride, int offset) {
 // Launch order of one frame. With a WfFork (uniform trace_fork) the closest-hit trace of bounce 1 (it needs only the
 // rays and live list the bounce-0 shade wrote) runs beside the bounce-0 shadow trace and finish on the side stream;
 // the join comes before the bounce-1 shade, which reuses the shadow list and reads the finished throughput. The two
-// traversal launches then fill each other's tails. Without `fk` the launches are serial.
+// traversal launches then fill each other's tails. Without `fk` the launches are serial. (With shade_fold the
+// bounce-0 finish is part of the bounce-1 shade and the join follows the shadow walk.)
 // nb > 1: a batch of frames (pt_pass_draw_batch) — per-frame launches for the primaries, shades and finishes, ONE
 // launch per bounce for the list-driven traversals of every frame's rays (lane-refill kernels; the one-ray-per-lane
 // kernels run per frame). Frame b's wavefront state lies at pid offset b * N of ps[0]'s, its counters at
@@ -1760,6 +1809,8 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
   };
   // deep trees keep one stream: both walks would use the pixel's spill columns
   const bool split = fk && !DEEP && p.max_depth > 1;
+  // paths end in place (shade_fold; a path of no bounce has no shade to end in: wf_finalize writes its colour)
+  const bool fold = p.shade_fold && p.max_depth > 0;
   for (int i = 0; i < p.max_depth; ++i) {
     if (i > 0) closest(i);
     if (i == 1 && split) {
@@ -1769,9 +1820,17 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
     for (int b = 0; b < nb; ++b) {
       const PTParams& f = ps[b];
       const int* live_in = f.wf.counters + kWfCtr * (i > 0 ? i - 1 : 0);
-      hipLaunchKernelGGL(wf_shade, dim3(i == 0 ? gS0 : gL), dim3(256), 0, s, f, i, (const int*)lst(f, i + 1), live_in,
-                         lst(f, i), f.wf.counters + kWfCtr * i, f.wf.shadow_list, f.wf.counters + kWfCtr * i + kCtrHdr,
-                         cap);
+#define PT_SHADE_LAUNCH(FOLD, FIRST, LAST)                                                                          \
+  hipLaunchKernelGGL((wf_shade<FOLD, FIRST, LAST>), dim3(i == 0 ? gS0 : gL), dim3(256), 0, s, f, i,                  \
+                     (const int*)lst(f, i + 1), live_in, lst(f, i), f.wf.counters + kWfCtr * i, f.wf.shadow_list, \
+                     f.wf.counters + kWfCtr * i + kCtrHdr, cap)
+      const bool last = i + 1 == p.max_depth;
+      if (!fold) PT_SHADE_LAUNCH(false, false, false);
+      else if (i == 0 && last) PT_SHADE_LAUNCH(true, true, true);
+      else if (i == 0) PT_SHADE_LAUNCH(true, true, false);
+      else if (last) PT_SHADE_LAUNCH(true, false, true);
+      else PT_SHADE_LAUNCH(true, false, false);
+#undef PT_SHADE_LAUNCH
     }
     hipStream_t ss = s;  // the shadow walk's and finish's stream
     if (i == 0 && split) {
@@ -1816,15 +1875,23 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
       for (int b = 0; b < nb; ++b)
         hipLaunchKernelGGL(wf_shadow_stats, dim3(gN), dim3(256), 0, ss, ps[b], (const int*)ps[b].wf.shadow_list,
                            (const int*)(ps[b].wf.counters + kWfCtr * i + kCtrHdr), cap);
-    for (int b = 0; b < nb; ++b)
-      hipLaunchKernelGGL(wf_finish, dim3(gL), dim3(256), 0, ss, ps[b], (const int*)lst(ps[b], i),
-                         (const int*)(ps[b].wf.counters + kWfCtr * i), cap);
+    // folded: bounce i's verdicts are applied at the top of the bounce-(i + 1) shade; the last bounce's finish ends
+    // the paths still alive
+    for (int b = 0; b < nb && !(fold && i + 1 < p.max_depth); ++b) {
+      if (fold)
+        hipLaunchKernelGGL(wf_finish<true>, dim3(gL), dim3(256), 0, ss, ps[b], (const int*)lst(ps[b], i),
+                           (const int*)(ps[b].wf.counters + kWfCtr * i), cap);
+      else
+        hipLaunchKernelGGL(wf_finish<false>, dim3(gL), dim3(256), 0, ss, ps[b], (const int*)lst(ps[b], i),
+                           (const int*)(ps[b].wf.counters + kWfCtr * i), cap);
+    }
     if (i == 0 && split) {
       const hipError_t e = hipEventRecord(fk->join, ss);
       if (e != hipSuccess) return (int)e;
     }
   }
-  for (int b = 0; b < nb; ++b) hipLaunchKernelGGL(wf_finalize, dim3(gN), dim3(256), 0, s, ps[b]);
+  if (!fold)
+    for (int b = 0; b < nb; ++b) hipLaunchKernelGGL(wf_finalize, dim3(gN), dim3(256), 0, s, ps[b]);
   return (int)hipGetLastError();
 }
 

@@ -226,6 +226,8 @@ struct PTParams {
   int refill_waves;     // resident waves a refill launch is sized for (0: the whole chip, kResidentWaves)
   int refill_grid;      // most blocks of a refill launch (uniform refill_grid; 0: PTSVGF_REFILL_GRID / its default)
   int list_grid;        // most blocks of the list-driven shade / finish (uniform list_grid; 0: PTSVGF_LIST_BLOCKS)
+  int shade_fold;       // wavefront: paths write `color` where they end, a bounce's verdicts are applied by the next
+                        // shade (uniform shade_fold, default 1; 0: wf_finish per bounce and wf_finalize, for A/B)
   float sobol_u[4], sobol_v[4];  // sobolVec2(frameCounter+1, b): uniform across pixels
   WFState wf;
   // optional bound for the primary rays from this frame's G-buffer (world position + normal/linearZ planes,
@@ -250,6 +252,10 @@ struct GBufParams {
   int W, H, y0, y1;
   Plane world, normal_depth, motion, fwidth;
   float* fwidth_aux;    // compact depth-fwidth plane (rows of fwidth), may be null
+  // compact primary-ray bound plane (rows of world), may be null: per pixel the float the path tracer's primary
+  // rasterisers prune with (raster_bound, kernels_wavefront.hip), for primary rays that start at bound_eye
+  float* bound_aux;
+  float bound_eye[3];
   unsigned char* tflags;  // a-trous per-tile surface flags (atrous_mark_tiles) of rows [tf_y0, tf_y1), may be null
   int tf_off[5];          // their per-step offsets (atrous_flag_offset)
   int tf_y0, tf_y1;       // the rows the a-trous passes draw (default: the G-buffer's own rows)

@@ -95,6 +95,7 @@ _PT_SIGS = [
     ("pt_texarray_create", C.c_int, [C.c_int, C.c_int, C.c_int, _u32p]),
     ("pt_texarray_upload_layer", C.c_int, [_u32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     ("pt_texture_readback", C.c_int, [_u32, _fp, C.c_size_t]),
+    ("pt_texture_readback_aux", C.c_int, [_u32, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("pt_texture_upload_rgba", C.c_int, [_u32, _fp, C.c_size_t]),
     ("pt_texture_device_ptr", C.c_int, [_u32, C.POINTER(_vp)]),
     ("pt_texture_info", C.c_int, [_u32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -180,6 +180,19 @@ def readback(tex: int) -> np.ndarray:
     return out
 
 
+def readback_aux(tex: int):
+    """pt_texture_readback_aux: the compact one-float side plane of a texture's stored rows as
+    (rows, W) float32, or None when the texture holds none that matches its texels."""
+    w, rows, _ = texture_info(tex)
+    n = C.c_size_t()
+    check(pt().pt_texture_readback_aux(tex, None, 0, C.byref(n)))
+    if not n.value:
+        return None
+    out = np.empty((rows, w), np.float32)
+    check(pt().pt_texture_readback_aux(tex, fptr(out), out.nbytes, C.byref(n)))
+    return out
+
+
 def upload_rgba(tex: int, data: np.ndarray) -> None:
     a = np.ascontiguousarray(data, dtype=np.float32)
     check(pt().pt_texture_upload_rgba(tex, fptr(a), a.nbytes))

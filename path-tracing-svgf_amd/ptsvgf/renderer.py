@@ -139,6 +139,12 @@ def priority_stream(priority: int):
 
 
 class Renderer:
+    # True (set before a frame is drawn): the fast driver's G-buffer draws also write the primary rasterisers' bound of
+    # every pixel as one float (vec3 uniform bound_eye; kernels_pt.hip gb_finish), which the frame's path tracer then
+    # reads instead of the two hint planes (its int uniform bound_plane = 0 keeps the two-plane read). Same bits; off
+    # by default: it measured inside the noise (DESIGN.md "Paths end in place")
+    bound_plane = False
+
     def __init__(self, scene: Scene, width: int, height: int, config: parameter_config | None = None,
                  mode: str = "fast", aspect_corrected: bool | None = None, band=None, prune: bool = True,
                  atrous_exact: bool = False, run_taa: bool = True, run_output: bool = True, tex_factory=None,
@@ -487,6 +493,8 @@ class Renderer:
         ip.set_uniform_mat4("projection", proj)
         ip.set_uniform_mat4("pre_viewproj", self.pre_viewproj)
         ip.set_uniform_uint("frameCounter", cam.frameCounter)
+        if self.mode == "fast" and self.bound_plane:
+            ip.set_uniform_vec3("bound_eye", cam.cam_position)
         if self._motion_records:  # only the first frame after a rebuild_bvh(prev_raster=...) sees the objects move
             ip.set_uniform_int("object_motion", 1 if self._motion_pending and self.object_motion else 0)
             self._motion_pending = False
