@@ -249,8 +249,25 @@ int pt_pass_set_trace_stats_n(uint32_t pass, void* device_u64, int count);
  * the first 12 above; the two shadow-split counters are not written. */
 #define PT_TRACE_STATS_V1 12
 int pt_pass_set_trace_stats(uint32_t pass, void* device_u64);
-/* Number of traversal counters this library writes (14). */
+/* 14: the counters of the form above, kept for callers that sized their buffers
+ * by this call before the two point-light counters below were added. New
+ * callers size their buffer by pt_trace_stats_total(). */
 int pt_trace_stats_count(void);
+/* Every traversal counter this library writes (16): the 14 above, then the
+ * point-light shadow rays decided by the lights' triangle bins (pass uniform
+ * point_bins) and those handed to the tree walk instead. A buffer of this many
+ * counters, passed with its count to pt_pass_set_trace_stats_n, receives all. */
+int pt_trace_stats_total(void);
+/* The point-light triangle bins (pass uniform point_bins) of the scene decoded
+ * from (tri_tex, node_tex), as the last path-tracing draw of that scene built
+ * them; PT_ERR_STATE when it has none. Synchronises the device.
+ * info8x4[8 * l ..] for light l < lights: [0] != 0 the light has no usable bins
+ * (its rays walk), [1] entries, [2..4] float bits of the light position the
+ * bins were built around, [5] float bits of the coordinate magnitude the build
+ * assumed, [6] entries of its catch-all list, [7] 0.
+ * dims4: cells per cube-face edge, lights, entries a light has room for, 0.
+ * *bytes: the allocation. Any output may be NULL. */
+int pt_point_bins_info(uint32_t tri_tex, uint32_t node_tex, int* info8x4, int* dims4, size_t* bytes);
 int pt_pass_draw(uint32_t pass);
 /* Draw `count` (1..8) path-tracing passes — the frames of a batch, each with its
  * own uniforms, samplers and attachments, one scene, size and band — as one

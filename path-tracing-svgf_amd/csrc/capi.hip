@@ -226,11 +226,48 @@ struct Pass {
   uint32_t* row_cost = nullptr;  // pt_pass_set_row_cost (not owned)
   uint32_t* motion_max = nullptr;  // pt_pass_set_motion_bound (not owned)
   struct HdrMerged* hdr_reads = nullptr;  // the merged environment the draw being issued reads (pt_params)
+  struct PointBinsGPU* pbins_reads = nullptr;  // the point-light bins it reads (point_bins_for)
   unsigned long long* stats = nullptr;  // pt_pass_set_trace_stats (not owned)
   int stats_n = 0;                      // counters that buffer holds (pt_pass_set_trace_stats_n)
 };
 
+// The point-light triangle bins of a scene (ptk::PointBinsDev, kernels_pointbins.hip) for the lights texture a
+// path-tracing draw bound: built on the device by the first such draw, rebuilt when the scene's triangles or tree, the
+// lights texture (handle, device memory, version) or pointLightSize change. Read by the path tracers of every frame
+// in flight on other streams, so buffers are handled as HdrMerged's are: a `built` event every draw's stream waits
+// for, per-stream readers' events, and a retired buffer reused only once its readers have finished. No host wait.
+constexpr int kPointBinsR = 64;  // cells per cube-face edge (uniform point_bins_r overrides: A/B)
+struct PointBinsGPU {
+  void* buf = nullptr;
+  size_t bytes = 0;
+  ptk::PointBinsDev dev{};
+  uint64_t tri_ver = 0, node_ver = 0, light_ver = 0;
+  uint32_t light_handle = 0;
+  const void* light_dev = nullptr;
+  int nl = 0, R = 0, ntris = 0;
+  hipEvent_t built = nullptr;
+  std::map<hipStream_t, hipEvent_t> uses;
+  struct Spare {
+    void* buf;
+    size_t bytes;
+    std::vector<hipEvent_t> readers;
+  };
+  std::vector<Spare> spare;
+};
+// drops a scene's point-light bins (the caller has synchronised the streams that read them)
+void free_point_bins(PointBinsGPU& m) {
+  if (m.buf) (void)hipFree(m.buf);
+  for (auto& sp : m.spare) {
+    (void)hipFree(sp.buf);
+    for (hipEvent_t e : sp.readers) (void)hipEventDestroy(e);
+  }
+  for (auto& u : m.uses) (void)hipEventDestroy(u.second);
+  if (m.built) (void)hipEventDestroy(m.built);
+  m = PointBinsGPU{};
+}
+
 struct SceneGPU {
+  PointBinsGPU pbins;
   float4* geom = nullptr;
   float4* shade = nullptr;
   float4* bvh = nullptr;
@@ -1296,6 +1333,8 @@ void drop_borrowed(SceneGPU& sg) {
 }
 
 void free_scene(SceneGPU& sg) {
+  if (sg.pbins.buf || !sg.pbins.spare.empty()) (void)hipDeviceSynchronize();  // its readers may run on any stream
+  free_point_bins(sg.pbins);
   drop_borrowed(sg);
   float4** bufs[6] = {&sg.geom, &sg.shade, &sg.bvh, &sg.bvh4, &sg.bvh_any, &sg.leaves};
   for (auto b : bufs) {
@@ -1709,6 +1748,75 @@ int bins_for(RasterBins& b, int n, int W, int y0, int y1, int cap, Bins* out) {
   return PT_OK;
 }
 
+// uniform point_bins (default kPointBinsDefault; 0 for a scene built on the device: point_bins_for): 1 = the
+// wavefront path tracer decides point-light shadow rays by the lights' triangle bins (wf_shadow_point_bins), 0 = they
+// walk the tree with the HDR rays. Same bits either way.
+constexpr int kPointBinsDefault = 1;
+// The point-light bins of a path-tracing draw (PTParams::point_bins / pbins), built or rebuilt on the draw's stream
+// when stale. Off (the rays walk) without 1 .. kPointBins lights all present in the lights buffer, or when a triangle
+// sits in two leaves (the condition that keeps primary_raster at 2: tri_leaf names one leaf per triangle).
+int point_bins_for(Pass* p, SceneGPU* sg, Texture* lt, uint32_t lh, PTParams& k) {
+  k.point_bins = 0;
+  p->pbins_reads = nullptr;
+  const int nl = k.pointLightSize;
+  // A scene rebuilt on the device (pt_bvh_build) pays the bins' build with every rebuild, which costs about a frame
+  // (DESIGN.md): there the default is 0. An explicit point_bins wins. (One frame at a time the bins measured slower,
+  // so the renderer sets 0 then, beside its other settings that depend on the frames in flight.)
+  const int dflt = sg->lbvh ? 0 : kPointBinsDefault;
+  if (!ui(p, "point_bins", dflt) || ui(p, "pt_kernel", 0) != 0 || nl < 1 || nl > ptk::kPointBins ||
+      !k.scene.lights || nl > k.scene.nlights_buf || !sg->tri_leaf || sg->tri_shared || !sg->leaves || sg->ntris <= 0)
+    return PT_OK;
+  const int R = std::min(ptk::kPointBinsMaxR, std::max(4, ui(p, "point_bins_r", kPointBinsR)));
+  PointBinsGPU& m = sg->pbins;
+  const bool stale = !m.buf || m.tri_ver != sg->tri_ver || m.node_ver != sg->node_ver || m.ntris != sg->ntris ||
+                     m.light_handle != lh || m.light_dev != lt->dev || m.light_ver != lt->version || m.nl != nl ||
+                     m.R != R;
+  if (stale) {
+    const size_t need = ptk::point_bins_bytes(sg->ntris, nl, R);
+    if (m.buf) {  // retired with its readers' events; reused by a later rebuild once they have completed
+      PointBinsGPU::Spare sp{m.buf, m.bytes, {}};
+      for (auto& u : m.uses) sp.readers.push_back(u.second);
+      m.uses.clear();
+      m.spare.push_back(std::move(sp));
+      m.buf = nullptr;
+    }
+    for (size_t i = 0; i < m.spare.size() && !m.buf; ++i) {
+      bool idle = m.spare[i].bytes >= need;
+      for (size_t j = 0; idle && j < m.spare[i].readers.size(); ++j)
+        idle = hipEventQuery(m.spare[i].readers[j]) == hipSuccess;
+      if (!idle) continue;
+      m.buf = m.spare[i].buf;
+      m.bytes = m.spare[i].bytes;
+      for (hipEvent_t e : m.spare[i].readers) (void)hipEventDestroy(e);
+      m.spare.erase(m.spare.begin() + i);
+    }
+    if (!m.buf) {
+      HIPCHK(hipMalloc(&m.buf, need));
+      m.bytes = need;
+    }
+    if (!m.built) HIPCHK(hipEventCreateWithFlags(&m.built, hipEventDisableTiming));
+    const int rc = ptk::launch_point_bins_build(k.scene, nl, R, m.buf, &m.dev, g.stream);
+    if (rc) return hip_err((hipError_t)rc, "point-light bins build");
+    HIPCHK(hipEventRecord(m.built, g.stream));
+    m.tri_ver = sg->tri_ver;
+    m.node_ver = sg->node_ver;
+    m.ntris = sg->ntris;
+    m.light_handle = lh;
+    m.light_dev = lt->dev;
+    m.light_ver = lt->version;
+    m.nl = nl;
+    m.R = R;
+    if (getenv("PTSVGF_SCENE_INFO"))
+      fprintf(stderr, "ptsvgf point-light bins: %d lights, R = %d, %zu B allocated (headers %zu B per light)\n", nl, R,
+              need, (size_t)(6 * R * R + 1) * sizeof(int2));
+  }
+  HIPCHK(hipStreamWaitEvent(g.stream, m.built, 0));  // (a no-op wait once the build has run)
+  p->pbins_reads = &m;
+  k.point_bins = 1;
+  k.pbins = m.dev;
+  return PT_OK;
+}
+
 // ------------------------------------------------------------- draw calls ---
 // PTParams of a path-tracing pass's draw from its uniforms, samplers and attachments (the wavefront state aside).
 int pt_params(Pass* p, PTParams& k, SceneGPU*& sg) {
@@ -1828,6 +1936,7 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg) {
   }
   k.hdrResolution = ui(p, "hdrResolution", hm->W);
   k.pointLightSize = ui(p, "pointLightSize", 0);
+  TRY(point_bins_for(p, sg, lt, lh, k));
   k.frameCounter = uu(p, "frameCounter", 0);
   const Uniform* cr = U(p, "cameraRotate", 6);
   if (cr) memcpy(k.camRot, cr->f, 64);
@@ -1874,6 +1983,7 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg) {
 // share of a batch's), counters, budgets, refill, cost-ordered tiles and the primary rasteriser's bins.
 int pt_wf_setup(Pass* p, PTParams& k, SceneGPU* sg, const WFState& st) {
     k.wf = st;
+    if (k.wf.spill) k.point_bins = 0;  // deep trees keep the walk (launch_wavefront<.., DEEP>)
     k.wf.row_cost = p->row_cost;
     k.wf.stats = p->stats;
     k.wf.stats_n = p->stats_n;
@@ -1942,6 +2052,14 @@ const ptk::WfFork* wf_fork(Pass* p, hipStream_t s, int* rc) {
 // after a path-tracing draw that read a merged environment: its stream's use event, so a later rebuild knows when
 // this draw no longer reads the buffer (HdrMerged::uses)
 int note_hdr_read(Pass* p) {
+  if (PointBinsGPU* b = p->pbins_reads) {  // likewise the point-light bins (PointBinsGPU::uses)
+    p->pbins_reads = nullptr;
+    if (b->buf) {
+      hipEvent_t& e = b->uses[g.stream];
+      if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      HIPCHK(hipEventRecord(e, g.stream));
+    }
+  }
   HdrMerged* m = p->hdr_reads;
   p->hdr_reads = nullptr;
   if (!m || !m->buf) return PT_OK;
@@ -2007,6 +2125,13 @@ int draw_pathtrace_batch(Pass** ps, int n) {
   TRY(wf_alloc(h->wf, k[0].W, std::max(0, k[0].y1 - k[0].y0), cap));
   if (wf_spill(h->wf, k[0].stack_need) != PT_OK) return err(PT_ERR_HIP, "spill stack allocation failed");
   for (int b = 0; b < n; ++b) TRY(pt_wf_setup(ps[b], k[b], sg, h->wf.stb[b]));
+  // the batched shadow launches read frame 0's point-light bins for every frame: frames that do not share them (other
+  // lights, another pointLightSize) all walk
+  bool same_bins = true;
+  for (int b = 1; b < n; ++b)
+    same_bins = same_bins && k[b].point_bins == k[0].point_bins && k[b].pbins.hdr == k[0].pbins.hdr &&
+                k[b].pbins.nl == k[0].pbins.nl;
+  for (int b = 0; b < n && !same_bins; ++b) k[b].point_bins = 0;
   int rc;
   const ptk::WfFork* fk = wf_fork(h, g.stream, &rc);
   if (rc) return rc;
@@ -2398,6 +2523,13 @@ int pt_stream_release(void* s) {
     (void)hipEventDestroy(u->second);
     kv.second.uses.erase(u);
   }
+  for (auto& kv : g.scenes) {  // and of a scene's point-light bins
+    auto u = kv.second.pbins.uses.find(st);
+    if (u == kv.second.pbins.uses.end()) continue;
+    (void)hipEventSynchronize(u->second);
+    (void)hipEventDestroy(u->second);
+    kv.second.pbins.uses.erase(u);
+  }
   if (g.stream == st) g.stream = g.own;
   return PT_OK;
 }
@@ -2739,6 +2871,28 @@ int pt_debug_lbvh_trees(uint32_t node_tex, int source, int which, void* host_out
     if (source == 0) HIPCHK(hipMemcpy(host_out, src, n * sizeof(float4), hipMemcpyDeviceToHost));
     else memcpy(host_out, host.data(), n * sizeof(float4));
   }
+  return PT_OK;
+}
+
+int pt_point_bins_info(uint32_t tri_tex, uint32_t node_tex, int* info8x4, int* dims4, size_t* bytes) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  auto it = g.scenes.find({tri_tex, node_tex});
+  if (it == g.scenes.end() || !it->second.pbins.buf)
+    return err(PT_ERR_STATE, "pt_point_bins_info: no point-light bins built for this scene");
+  const PointBinsGPU& m = it->second.pbins;
+  HIPCHK(hipDeviceSynchronize());
+  if (info8x4) {
+    memset(info8x4, 0, sizeof(int) * ptk::kPointBins * ptk::kPointBinsInfo);
+    HIPCHK(hipMemcpy(info8x4, m.dev.info, sizeof(int) * m.nl * ptk::kPointBinsInfo, hipMemcpyDeviceToHost));
+  }
+  if (dims4) {
+    dims4[0] = m.R;
+    dims4[1] = m.nl;
+    dims4[2] = m.dev.cap;
+    dims4[3] = 0;
+  }
+  if (bytes) *bytes = m.bytes;
   return PT_OK;
 }
 
@@ -3229,7 +3383,8 @@ int pt_pass_set_trace_stats(uint32_t pass, void* device_u64) {
   return pt_pass_set_trace_stats_n(pass, device_u64, PT_TRACE_STATS_V1);
 }
 
-int pt_trace_stats_count(void) { return kStatCount; }
+int pt_trace_stats_count(void) { return ptk::kStatCountV2; }
+int pt_trace_stats_total(void) { return kStatCount; }
 
 int pt_pass_set_motion_bound(uint32_t pass, void* device_u32) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);

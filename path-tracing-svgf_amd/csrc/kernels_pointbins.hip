@@ -1,0 +1,280 @@
+// kernels_pointbins.hip — the build of the point-light triangle bins (PointBinsDev, pt_device.h): for every point
+// light a cube map of direction cells around it, each cell listing the triangles a shadow ray arriving at the light
+// from that cell's directions can hit. wf_shadow_point_bins (kernels_wavefront.hip) then decides a point-light shadow
+// ray by testing its cell's list instead of walking a tree. Built once per scene and light set, on the device.
+//
+// What a cell must hold (DESIGN.md "Point-light shadow rays by light-binned triangles"). A ray (S, d) toward light L, d = normalize(L - S) rounded, can
+// be found to hit triangle T only at a point P = S + d t within e of a point Q of T, e = 3.2e-5 Mtot + 2 dev
+// (pr_tri_setup's bound of hitTriangle's slack with the magnitudes of every ray origin and the light: Mtot; the extra
+// 0.2e-5 Mtot covers the ray passing the light within a few eps |L - S|). Seen from L, Q lies within the angle
+// e / |Q - L| of -d. Each face's triangle is clipped to the face's frustum widened to |x|, |y| <= 1.01 w, projected,
+// and binned to the cells its projection covers widened by that angle in cells; |Q - L| >= w >= wmin, the clipped
+// polygon's least depth. A triangle with wmin < r0 = 0.01 Mtot or e >= 0.002 wmin on some face (then the angle, under
+// 0.002, moves the projection by under 0.007 < 0.01: a point just across a face edge is still inside the widened
+// frustum), with a non-finite vertex, or whose N is not perpendicular to its edges goes to the light's catch-all list.
+#include <hip/hip_runtime.h>
+
+#include "glsl_builtins.h"
+#include "pt_device.h"
+#include "pt_shading.h"
+
+using namespace glsl;
+
+namespace ptk {
+
+namespace {
+
+constexpr int kScanThreads = 1024;
+
+struct PbLayout {
+  size_t info, hdr, cnt, tmp, ent, total;
+  int cap;
+};
+// entries a light's lists have room for. Measured on the bench scene (30 633 triangles, lights 0.3 .. 1 from the
+// geometry): at most 8.5 / 25 / 84 entries per triangle at R = 32 / 64 / 128; the per-cell term leaves room for the
+// few large triangles that cover whole faces. A light whose entries do not fit gets no bins (its rays walk).
+inline PbLayout pb_layout(int ntris, int nl, int R) {
+  const size_t ncell1 = (size_t)6 * R * R + 1, al = 256;
+  auto up = [&](size_t v) { return (v + al - 1) / al * al; };
+  PbLayout l{};
+  const size_t cap = (size_t)(R > 64 ? 96 : 32) * (size_t)std::max(ntris, 1) + 8 * ncell1;
+  l.cap = (int)std::min<size_t>(cap, (size_t)1 << 28);
+  l.info = 0;
+  l.cnt = up((size_t)(kPointBins + 1) * kPointBinsInfo * sizeof(int));  // (+1: the scene's magnitude)
+  l.hdr = l.cnt + up((size_t)nl * ncell1 * sizeof(int));
+  l.tmp = l.hdr + up((size_t)nl * ncell1 * sizeof(int2));
+  l.ent = l.tmp + up((size_t)l.cap * sizeof(uint4));
+  l.total = l.ent + up((size_t)nl * l.cap * sizeof(uint4));
+  return l;
+}
+
+struct PbBuild {
+  SceneDev sc;
+  int* info;     // kPointBins x kPointBinsInfo, then [0] of the next record: float bits of the scene's magnitude
+  int* cnt;      // nl x (ncell + 1): cell counts, then the scatter's fill counts
+  int2* hdr;     // nl x (ncell + 1)
+  uint4* tmp;    // cap: one light's entries in scatter order (the lights are scattered and sorted one after another)
+  uint4* ent;    // nl x cap: entries, each cell ascending by near
+  int R, nl, cap;
+  int l0;        // the scatter's and the sort's light (their grids have one light)
+};
+
+// largest finite coordinate magnitude of the triangles' vertices (a positive float's bits order as an int's)
+__global__ void __launch_bounds__(256) pb_extent(PbBuild b) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  float m = 0.0f;
+  if (i < b.sc.ntris) {
+    const TriGeom tg = tri_load(b.sc.tri_geom, i);
+    const float c[9] = {tg.a.x, tg.a.y, tg.a.z, tg.b.x, tg.b.y, tg.b.z, tg.c.x, tg.c.y, tg.c.z};
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+      if (fabsf(c[k]) <= 3.0e38f) m = fmaxf(m, fabsf(c[k]));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(b.info + kPointBins * kPointBinsInfo, __float_as_int(m));
+}
+
+__global__ void __launch_bounds__(64) pb_lights(PbBuild b) {
+  const int l = threadIdx.x;
+  if (l >= b.nl) return;
+  int* f = b.info + l * kPointBinsInfo;
+  const float* lp = b.sc.lights + 6 * l;
+  const float ms = __int_as_float(b.info[kPointBins * kPointBinsInfo]);
+  const float ml = fmaxf(fabsf(lp[0]), fmaxf(fabsf(lp[1]), fabsf(lp[2])));
+  const bool ok = fabsf(lp[0]) <= 3.0e38f && fabsf(lp[1]) <= 3.0e38f && fabsf(lp[2]) <= 3.0e38f;
+  f[0] = ok ? 0 : 1;
+  f[1] = 0;
+  f[2] = __float_as_int(lp[0]);
+  f[3] = __float_as_int(lp[1]);
+  f[4] = __float_as_int(lp[2]);
+  f[5] = __float_as_int(ok ? ms + ml : 0.0f);
+}
+
+constexpr uint32_t kBoxEmpty = 0x000000ffu;  // x0 = 255 > x1 = 0
+
+// One thread per (triangle, light blockIdx.y): the triangle's cell box and near bound on each face, or the catch-all
+// list. SCATTER = false counts the cells, true writes the entries (the same arithmetic, so the same cells).
+template <bool SCATTER>
+__global__ void __launch_bounds__(256) pb_bin(PbBuild b) {
+  const int i = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y + b.l0;
+  if (i >= b.sc.ntris) return;
+  const int* f = b.info + l * kPointBinsInfo;
+  if (f[0]) return;  // no usable bins for this light
+  const int R = b.R, ncell = 6 * R * R;
+  int* cnt = b.cnt + (size_t)l * (ncell + 1);
+  const int2* hdr = b.hdr + (size_t)l * (ncell + 1);
+  uint4* tmp = b.tmp;
+  auto emit = [&](int cell, float near, uint32_t sub) {
+    const int slot = atomicAdd(cnt + cell, 1);
+    if (SCATTER) {
+      const int pos = hdr[cell].x + slot;
+      if (pos >= 0 && pos < b.cap) tmp[pos] = make_uint4((uint32_t)i, __float_as_uint(near), sub, 0u);
+    }
+  };
+  const TriGeom tg = tri_load(b.sc.tri_geom, i);
+  const v3 N = xyz(tg.n), v[3] = {xyz(tg.a), xyz(tg.b), xyz(tg.c)};
+  const float big = 3.0e38f;
+  const bool nfin = fabsf(N.x) <= big && fabsf(N.y) <= big && fabsf(N.z) <= big;  // (false for NaN too)
+  // a triangle in no leaf is never tested by the reference; with a non-finite N hitTriangle rejects every ray
+  if (b.sc.tri_leaf[i] < 0 || !nfin) return;
+  const v3 L = mk(__int_as_float(f[2]), __int_as_float(f[3]), __int_as_float(f[4]));
+  const float Mtot = __int_as_float(f[5]);
+  bool fin = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) fin = fin && fabsf(v[k].x) <= big && fabsf(v[k].y) <= big && fabsf(v[k].z) <= big;
+  const v3 E[3] = {sub(v[1], v[0]), sub(v[2], v[1]), sub(v[0], v[2])};
+  bool perp = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) perp = perp && fabsf(dot(N, E[k])) <= 1.0e-3f * length(E[k]);
+  const float dev = fmaxf(fabsf(dot(N, E[0])), fabsf(dot(N, E[2])));  // the vertices' distance from N.x = N.p1
+  const float e = 3.2e-5f * Mtot + 2.0f * dev, r0 = 0.01f * Mtot;
+  bool catchall = !fin || !perp || !(e == e);
+  // every point of the triangle lies at least ds from the light: its distance from the centroid's sphere
+  const v3 c = muls(add(add(v[0], v[1]), v[2]), 1.0f / 3.0f);
+  const float rad = fmaxf(length(sub(v[0], c)), fmaxf(length(sub(v[1], c)), length(sub(v[2], c))));
+  const float ds = fmaxf(length(sub(c, L)) - rad * 1.00001f, 0.0f);
+  uint32_t box[6];
+  float nearf[6], ext[6][4];  // per face: cell box, near bound, the widened projection's extent in cell coordinates
+  for (int fc = 0; fc < 6 && !catchall; ++fc) {
+    box[fc] = kBoxEmpty;
+    nearf[fc] = 0.0f;
+    const int a = fc >> 1;
+    const float sg = (fc & 1) ? -1.0f : 1.0f;
+    float3 A[16], B[16];
+    for (int k = 0; k < 3; ++k) {
+      const float q[3] = {v[k].x - L.x, v[k].y - L.y, v[k].z - L.z};
+      A[k] = make_float3(q[(a + 1) % 3], q[(a + 2) % 3], sg * q[a]);
+    }
+    int n = clip_plane(A, 3, B, 0, 1.0f);
+    n = clip_plane(B, n, A, 0, -1.0f);
+    n = clip_plane(A, n, B, 1, 1.0f);
+    n = clip_plane(B, n, A, 1, -1.0f);
+    if (n <= 0) continue;  // nothing of it in this face's widened frustum
+    float x0 = 3.0e38f, y0 = 3.0e38f, x1 = -3.0e38f, y1 = -3.0e38f, wmin = 3.0e38f;
+    bool bad = false;
+    for (int k = 0; k < n; ++k) {
+      const float w = A[k].z;
+      // cell coordinate of the direction (x, y, w): the cell is floor((x / w + 1) R / 2) (wf_shadow_point_bins)
+      const float px = (A[k].x / w + 1.0f) * 0.5f * (float)R, py = (A[k].y / w + 1.0f) * 0.5f * (float)R;
+      bad = bad || !(w > 0.0f) || !(px == px && py == py);
+      wmin = fminf(wmin, w);
+      x0 = fminf(x0, px); x1 = fmaxf(x1, px);
+      y0 = fminf(y0, py); y1 = fmaxf(y1, py);
+    }
+    if (bad || wmin < r0 || !(e < 0.002f * wmin)) {
+      catchall = true;
+      break;
+    }
+    // the angle e / wmin moves a direction's x / w by under 3.5 times itself (w >= |direction| / sqrt 3 on its face
+    // and just across its edges); 0.02 of a cell for the rounding of both sides' cell coordinates
+    const float fw = 3.5f * (e / wmin) * 0.5f * (float)R + 0.02f;
+    const float lim = 1.0e6f;
+    const int cx0 = max((int)floorf(fmaxf(x0 - fw, -lim)), 0), cx1 = min((int)floorf(fminf(x1 + fw, lim)), R - 1);
+    const int cy0 = max((int)floorf(fmaxf(y0 - fw, -lim)), 0), cy1 = min((int)floorf(fminf(y1 + fw, lim)), R - 1);
+    if (cx0 > cx1 || cy0 > cy1) continue;  // only in the widened rim
+    box[fc] = (uint32_t)cx0 | ((uint32_t)cx1 << 8) | ((uint32_t)cy0 << 16) | ((uint32_t)cy1 << 24);
+    ext[fc][0] = fmaxf(x0 - fw, -lim); ext[fc][1] = fminf(x1 + fw, lim);
+    ext[fc][2] = fmaxf(y0 - fw, -lim); ext[fc][3] = fminf(y1 + fw, lim);
+    // a point the ray can be found to hit lies within e of a point of the triangle inside this face's frustum, which
+    // is at least max(ds, wmin) from the light
+    nearf[fc] = fmaxf(fmaxf(ds, wmin) * 0.99999f - e, 0.0f);
+  }
+  if (catchall) {
+    emit(ncell, 0.0f, 0xff00ff00u);
+    return;
+  }
+  for (int fc = 0; fc < 6; ++fc) {
+    const uint32_t bx = box[fc];
+    const int cx0 = bx & 255u, cx1 = (bx >> 8) & 255u, cy0 = (bx >> 16) & 255u, cy1 = bx >> 24;
+    if (cx0 > cx1) continue;
+    // the extent inside each cell in 1 / 256 of a cell: (x0, x1, y0, y1), 8 bits each (kernels_wavefront.hip sub_cell)
+    auto q = [](float v) { return (uint32_t)min(max((int)floorf(v * 256.0f), 0), 255); };
+    for (int cy = cy0; cy <= cy1; ++cy)
+      for (int cx = cx0; cx <= cx1; ++cx)
+        emit((fc * R + cy) * R + cx, nearf[fc],
+             q(ext[fc][0] - (float)cx) | (q(ext[fc][1] - (float)cx) << 8) | (q(ext[fc][2] - (float)cy) << 16) |
+                 (q(ext[fc][3] - (float)cy) << 24));
+  }
+}
+
+// One block per light: headers (first entry, entries) from the cell counts, which are zeroed for the scatter; a
+// light whose entries exceed `cap` gets no bins.
+__global__ void __launch_bounds__(kScanThreads) pb_scan(PbBuild b) {
+  __shared__ int part[kScanThreads];
+  const int l = blockIdx.x, n1 = 6 * b.R * b.R + 1, t = threadIdx.x;
+  int* cnt = b.cnt + (size_t)l * n1;
+  int2* hdr = b.hdr + (size_t)l * n1;
+  const int per = (n1 + kScanThreads - 1) / kScanThreads, lo = min(t * per, n1), hi = min(lo + per, n1);
+  long long sum = 0;
+  for (int c = lo; c < hi; ++c) sum += cnt[c];
+  part[t] = (int)min(sum, (long long)0x3fffffff);
+  __syncthreads();
+  for (int o = 1; o < kScanThreads; o <<= 1) {  // inclusive scan (saturating: an overflow stays one)
+    const int add = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] = min(part[t] + add, 0x3fffffff);
+    __syncthreads();
+  }
+  const int total = part[kScanThreads - 1];
+  int off = t > 0 ? part[t - 1] : 0;
+  for (int c = lo; c < hi; ++c) {
+    const int k = cnt[c];
+    hdr[c] = make_int2(off, k);
+    if (c == n1 - 1) b.info[l * kPointBinsInfo + 6] = k;  // the catch-all list's entries
+    off = min(off + k, 0x3fffffff);
+    cnt[c] = 0;
+  }
+  if (t == 0) {
+    int* f = b.info + l * kPointBinsInfo;
+    f[1] = total;
+    if (total > b.cap) f[0] = 1;
+  }
+}
+
+// One wave per cell: its entries from scatter order into ascending (near, triangle) order, by rank.
+__global__ void __launch_bounds__(256) pb_sort(PbBuild b) {
+  const int l = blockIdx.y + b.l0, n1 = 6 * b.R * b.R + 1;
+  const int cell = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (cell >= n1 || b.info[l * kPointBinsInfo]) return;
+  const int2 h = b.hdr[(size_t)l * n1 + cell];
+  const uint4* src = b.tmp + h.x;
+  uint4* dst = b.ent + (size_t)l * b.cap + h.x;
+  for (int i = lane; i < h.y; i += 64) {
+    const uint4 me = src[i];
+    int rank = 0;
+    for (int j = 0; j < h.y; ++j) {
+      const uint4 o = src[j];
+      rank += (o.y < me.y || (o.y == me.y && o.x < me.x)) ? 1 : 0;
+    }
+    dst[rank] = me;
+  }
+}
+
+}  // namespace
+
+size_t point_bins_bytes(int ntris, int nl, int R) { return pb_layout(ntris, nl, R).total; }
+
+int launch_point_bins_build(const SceneDev& sc, int nl, int R, void* base, PointBinsDev* out, hipStream_t s) {
+  if (nl < 1 || nl > kPointBins || R < 1 || R > kPointBinsMaxR || !base || !sc.lights || !sc.tri_leaf)
+    return (int)hipErrorInvalidValue;
+  const PbLayout lay = pb_layout(sc.ntris, nl, R);
+  char* c = (char*)base;
+  PbBuild b{sc, (int*)(c + lay.info), (int*)(c + lay.cnt), (int2*)(c + lay.hdr), (uint4*)(c + lay.tmp),
+            (uint4*)(c + lay.ent), R, nl, lay.cap, 0};
+  hipError_t e = hipMemsetAsync(base, 0, lay.hdr, s);  // info and the cell counts
+  if (e != hipSuccess) return (int)e;
+  const int gt = (sc.ntris + 255) / 256, n1 = 6 * R * R + 1;
+  if (gt > 0) hipLaunchKernelGGL(pb_extent, dim3(gt), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(pb_lights, dim3(1), dim3(64), 0, s, b);
+  if (gt > 0) hipLaunchKernelGGL(pb_bin<false>, dim3(gt, nl), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(pb_scan, dim3(nl), dim3(kScanThreads), 0, s, b);
+  for (b.l0 = 0; b.l0 < nl; ++b.l0) {  // one scatter buffer serves every light in turn
+    if (gt > 0) hipLaunchKernelGGL(pb_bin<true>, dim3(gt, 1), dim3(256), 0, s, b);
+    hipLaunchKernelGGL(pb_sort, dim3((n1 + 3) / 4, 1), dim3(256), 0, s, b);
+  }
+  *out = PointBinsDev{b.hdr, b.ent, b.info, R, nl, lay.cap};
+  return (int)hipGetLastError();
+}
+
+}  // namespace ptk

@@ -805,6 +805,17 @@ __global__ void __launch_bounds__(kTB) PT_TRACE_ATTR wf_trace_closest(PTParams p
   stat_add(p, kStatTieRewalks, rewalk ? 1u : 0u);
 }
 
+// The point-light lists wf_shadow_point_bins decides (bit c: list c): those of the lights with usable bins. The shadow
+// walks take the others with the HDR list: a light whose entries overflowed, a non-finite light, a list past the
+// lights the bins were built for.
+__device__ __forceinline__ uint32_t bins_lists(const PTParams& p) {
+  uint32_t m = 0;
+  if (p.point_bins)
+    for (int c = 0; c < kPointBins; ++c)
+      if (c < p.pbins.nl && p.pbins.info[c * kPointBinsInfo] == 0) m |= 1u << c;
+  return m;
+}
+
 // Shadow rays from the compacted lists wf_shade queued: HDR rays, then point-light rays.
 template <int KS, bool WIDE, bool DEEP>
 __global__ void __launch_bounds__(kTB) PT_TRACE_ATTR wf_trace_shadow(PTParams p, const int* __restrict__ list,
@@ -819,10 +830,12 @@ __global__ void __launch_bounds__(kTB) PT_TRACE_ATTR wf_trace_shadow(PTParams p,
   if (!point) {
     seg_get(list, counts, cap, k, &pid);
   } else {
+    const uint32_t skip = bins_lists(p);  // wf_shadow_point_bins takes these lists
     int r = k - nh;
     valid = false;
 #pragma unroll
     for (int b = 0; b < kPointBins; ++b) {
+      if ((skip >> b) & 1u) continue;
       const int nb = seg_total(counts + (1 + b) * kSeg);
       if (r < nb) {
         seg_get(list + (size_t)(1 + b) * kSeg * cap, counts + (1 + b) * kSeg, cap, r, &pid);
@@ -862,8 +875,9 @@ __global__ void __launch_bounds__(kTB) PT_TRACE_ATTR wf_trace_shadow(PTParams p,
 }
 
 // Dense index k of the shadow lists (HDR list, then the point-light lists bin by bin) -> pixel, kind.
+// `skip`: point-light lists left out of the dense range (bins_lists).
 __device__ __forceinline__ bool shadow_item(const int* __restrict__ list, const int* __restrict__ counts, int cap,
-                                            int nh, int k, int* pid, bool* point) {
+                                            int nh, int k, int* pid, bool* point, uint32_t skip = 0u) {
   if (k < nh) {
     *point = false;
     return seg_get(list, counts, cap, k, pid);
@@ -872,6 +886,7 @@ __device__ __forceinline__ bool shadow_item(const int* __restrict__ list, const 
   int r = k - nh;
 #pragma unroll
   for (int b = 0; b < kPointBins; ++b) {
+    if ((skip >> b) & 1u) continue;
     const int nb = seg_total(counts + (1 + b) * kSeg);
     if (r < nb) return seg_get(list + (size_t)(1 + b) * kSeg * cap, counts + (1 + b) * kSeg, cap, r, pid);
     r -= nb;
@@ -1031,6 +1046,14 @@ __global__ void __launch_bounds__(256) wf_shadow_stats(PTParams p, const int* __
   }
   stat_add(p, kStatShadowPoint, npoint);
   stat_add(p, kStatShadowOccluded, nocc);
+  // with the bins on, the rays of the lists they do not take were walked: counted as handed over
+  if (p.point_bins && blockIdx.x == 0 && threadIdx.x == 0 && kStatShadowPointFallback < p.wf.stats_n) {
+    const uint32_t taken = bins_lists(p);
+    unsigned long long left = 0;
+    for (int c = 0; c < kPointBins; ++c)
+      if (!((taken >> c) & 1u)) left += (unsigned long long)seg_total(counts + (1 + c) * kSeg);
+    if (left) atomicAdd(p.wf.stats + kStatShadowPointFallback, left);
+  }
 }
 
 // Shadow rays with lane refill. In wf_trace_shadow a wave lives as long as its longest ray while lanes whose rays
@@ -1051,11 +1074,13 @@ __global__ void __launch_bounds__(kTB) PT_TRACE_ATTR wf_trace_shadow_refill(PTPa
   const int lane = threadIdx.x & 63;
   int nh[kMaxBatch], tot[kMaxBatch];
   int total = 0;
+  const uint32_t skip = bins_lists(p);
   for (int b = 0; b < lb.nb; ++b) {
     nh[b] = seg_total(lb.counts[b]);
     tot[b] = nh[b];
 #pragma unroll
-    for (int c = 0; c < kPointBins; ++c) tot[b] += seg_total(lb.counts[b] + (1 + c) * kSeg);
+    for (int c = 0; c < kPointBins; ++c)  // (the lists wf_shadow_point_bins takes are not walked)
+      if (!((skip >> c) & 1u)) tot[b] += seg_total(lb.counts[b] + (1 + c) * kSeg);
     total += tot[b];
   }
   WaveQueue q = refill_queue(heads, total, p.refill, p.refill_waves);
@@ -1075,7 +1100,7 @@ __global__ void __launch_bounds__(kTB) PT_TRACE_ATTR wf_trace_shadow_refill(PTPa
       // refill: the next items go to the idle lanes in lane order
       int k = q.next + __popcll(idle & below);
       const int fb = k < q.end ? batch_frame(tot, lb.nb, &k) : -1;
-      if (!have && fb >= 0 && shadow_item(lb.list[fb], lb.counts[fb], cap, nh[fb], k, &pid, &point)) {
+      if (!have && fb >= 0 && shadow_item(lb.list[fb], lb.counts[fb], cap, nh[fb], k, &pid, &point, skip)) {
         pid += fb * lb.n;
         rvis = 0;
         const float4 o = ldnt(&p.wf.ray_o[pid]);
@@ -1343,6 +1368,142 @@ __global__ void __launch_bounds__(kTB) PT_TRACE_ATTR wf_trace_closest_refill(PTP
   stat_add(p, kStatBounceVisits, nvis);
   stat_slots(p, kStatBounceSlots, nvis);
   stat_add(p, kStatTieRewalks, nrewalk);
+}
+
+// Point-light shadow rays by the lights' triangle bins (PTParams::pbins, kernels_pointbins.hip) instead of a tree
+// walk. A point-light ray is occluded iff some triangle T passes (1) the ray passes the box of T's reference leaf,
+// (2) hitTriangle accepts, (3) t < PT_INF and length(d t) < maxd: a verdict that does not depend on which triangles
+// are tested besides, or in which order (anyhit2 / wf_trace_shadow_refill evaluate the same three). Every triangle
+// that can pass (2) and (3) for a ray toward light l lies in the list of the cell holding -d on l's cube map or in
+// l's catch-all list (the build's footprint argument), with `near` no greater than the light's distance from any
+// acceptable point, which lies between S and the light: entries with near beyond maxd * 1.0002 + 2e-4 (the walk's
+// pruning bound) are skipped, and the lists ascend by near, so the scan stops at the first.
+// The build's argument holds for d = normalize(L - S) and maxd = length(L - S) of the light L the bins were built
+// around: the kernel recomputes both with wf_shade's expressions and takes only rays whose stored bits match; any
+// other ray (a light index past the lists' lights, new light positions the bins have not seen, a non-finite
+// direction, an axis-parallel one) goes to the cooperative walk through the straggler list. The lists of a light
+// without usable bins, and of a light index past the bins' lights, stay with the shadow walk (bins_lists).
+// Lists of light l = list l of each frame; one wave takes 64 consecutive items of one list, so the light is
+// wave-uniform. The next entry's triangle is fetched one iteration ahead and the index of the one after that two
+// ahead: the addresses are known up front, so the loads of consecutive entries overlap.
+__global__ void __launch_bounds__(256) wf_shadow_point_bins(PTParams p, ListBatch lb, int cap,
+                                                            int* __restrict__ strag_count) {
+  const PointBinsDev& pb = p.pbins;
+  const int lane = threadIdx.x & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const int nw = gridDim.x * 4;
+  int vc = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));  // this wave's next chunk of 64
+  const int R = pb.R, ncell = pb.ncell();
+  uint32_t nvis = 0, nray = 0, nbin = 0, nfall = 0, wvis = 0;
+  for (int fb = 0; fb < lb.nb; ++fb) {
+    for (int c = 0; c < kPointBins; ++c) {
+      const int* counts = lb.counts[fb] + (1 + c) * kSeg;
+      const int* list = lb.list[fb] + (size_t)(1 + c) * kSeg * cap;
+      const int n = seg_total(counts), nch = (n + 63) >> 6;
+      if (c >= pb.nl || pb.info[c * kPointBinsInfo] != 0) continue;  // no usable bins: the shadow walk takes the list
+      const int* f = pb.info + (c < pb.nl ? c : 0) * kPointBinsInfo;
+      const v3 L = mk(__int_as_float(f[2]), __int_as_float(f[3]), __int_as_float(f[4]));
+      const int2* hdr = pb.hdr + (size_t)(c < pb.nl ? c : 0) * (ncell + 1);
+      const uint4* ent = pb.ent + (size_t)(c < pb.nl ? c : 0) * pb.cap;
+      for (; vc < nch; vc += nw) {
+        int pid = 0;
+        const bool valid = seg_get(list, counts, cap, vc * 64 + lane, &pid);
+        pid += fb * lb.n;
+        bool fall = valid;
+        int occ = 0;
+        uint32_t vis = 0;
+        if (valid) {
+          const float4 o = ldnt(&p.wf.ray_o[pid]), dir = ldnt(&p.wf.sh_p[pid]);
+          const v3 S = xyz(o), d = xyz(dir);
+          const float maxd = dir.w;
+          const v3 ld = normalize(sub(L, S));  // wf_shade's expressions
+          const float dist = length(sub(L, S));
+          const v3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+          const bool same = __float_as_uint(ld.x) == __float_as_uint(d.x) && __float_as_uint(ld.y) == __float_as_uint(d.y) &&
+                            __float_as_uint(ld.z) == __float_as_uint(d.z) && __float_as_uint(dist) == __float_as_uint(maxd);
+          if (same && finite3(inv) && __builtin_isfinite(maxd)) {
+            fall = false;
+            // the cell of -d: the face of its largest component (x before y before z on a tie), then (x, y) / w
+            const v3 v = neg(d);
+            const float ax = fabsf(v.x), ay = fabsf(v.y), az = fabsf(v.z);
+            const int a = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+            const float w = a == 0 ? v.x : (a == 1 ? v.y : v.z);
+            const float xf = a == 0 ? v.y : (a == 1 ? v.z : v.x), yf = a == 0 ? v.z : (a == 1 ? v.x : v.y);
+            const float aw = fabsf(w);
+            const float px = (xf / aw + 1.0f) * 0.5f * (float)R, py = (yf / aw + 1.0f) * 0.5f * (float)R;
+            const int cx = min(max((int)floorf(px), 0), R - 1), cy = min(max((int)floorf(py), 0), R - 1);
+            // where in its cell, in 1 / 256 of the cell: an entry's sub-cell box holds every direction of the cell
+            // from which a ray can be found to hit its triangle (the build's extent, rounded outward)
+            const uint32_t qx = (uint32_t)min(max((int)floorf((px - (float)cx) * 256.0f), 0), 255);
+            const uint32_t qy = (uint32_t)min(max((int)floorf((py - (float)cy) * 256.0f), 0), 255);
+            const int2 h0 = hdr[ncell], h1 = hdr[((2 * a + (w < 0.0f ? 1 : 0)) * R + cy) * R + cx];
+            const int n0 = h0.y, ne = n0 + h1.y;
+            const float lim = maxd * 1.0002f + 2.0e-4f;
+            auto entry = [&](int j) {  // catch-all entries (near 0) first, then the cell's, ascending
+              j = min(j, ne - 1);
+              return j < n0 ? ent[h0.x + j] : ent[h1.x + (j - n0)];
+            };
+            if (ne > 0) {
+              uint4 e1 = entry(0), e2 = entry(1);
+              TriGeom g1 = tri_load(p.scene.tri_geom, (int)e1.x);
+              int last_leaf = -1;
+              bool last_ok = false;
+              for (int i = 0; i < ne; ++i) {
+                const uint4 cur = e1;
+                const TriGeom tg = g1;
+                e1 = e2;
+                g1 = tri_load(p.scene.tri_geom, (int)e1.x);
+                e2 = entry(i + 2);
+                if (__uint_as_float(cur.y) > lim) break;  // this one and all after it lie beyond the ray's start
+                const uint32_t sb = cur.z;
+                if (qx < (sb & 255u) || qx > ((sb >> 8) & 255u) || qy < ((sb >> 16) & 255u) || qy > (sb >> 24)) continue;
+                float t;
+                ++vis;
+                if (!tri_test(tg, S, d, &t)) continue;
+                if (!(t < PT_INF && length(sub(add(S, muls(d, t)), S)) < maxd)) continue;
+                // a hit that counts: the reference tested this triangle only if the ray passes its leaf's box
+                const int leaf = p.scene.tri_leaf[cur.x];
+                if (leaf != last_leaf) {
+                  const float4 lo = p.scene.leaves[2 * leaf], hi = p.scene.leaves[2 * leaf + 1];
+                  float t0;
+                  last_ok = slab(S, inv, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, &t0) > 0.0f;
+                  last_leaf = leaf;
+                  ++vis;
+                }
+                if (last_ok) {
+                  occ = 1;
+                  break;
+                }
+              }
+            }
+            p.wf.occ_p[pid] = (uint8_t)occ;
+          }
+        }
+        nray += valid ? 1u : 0u;
+        nbin += valid && !fall ? 1u : 0u;
+        nfall += fall ? 1u : 0u;
+        nvis += vis;
+        uint32_t wm = vis;  // the wave's longest scan
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o));
+        wvis += wm;
+        const unsigned long long m = __ballot(fall);
+        if (m) {
+          int base = 0;
+          if (lane == __ffsll((long long)m) - 1) base = atomicAdd(strag_count, __popcll(m));
+          base = __shfl(base, __ffsll((long long)m) - 1);
+          if (fall) p.wf.straggler[base + __popcll(m & below)] = pid | (int)0x80000000;
+        }
+      }
+      vc -= nch;
+    }
+  }
+  stat_add(p, kStatShadowRays, nray);
+  stat_add(p, kStatShadowVisits, nvis);
+  if (p.wf.stats && kStatShadowSlots < p.wf.stats_n && lane == 0 && wvis)
+    atomicAdd(p.wf.stats + kStatShadowSlots, 64ull * wvis);
+  stat_add(p, kStatShadowPointBinned, nbin);
+  stat_add(p, kStatShadowPointFallback, nfall);
 }
 
 // The shadow rays wf_trace_shadow deferred: one wave per ray walks cooperatively (shadow_coop_walk). A fixed
@@ -1807,6 +1968,12 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
                            (const int*)(ps[b].wf.counters + kWfCtr * (i - 1)), cap);
     }
   };
+  // point-light shadow rays by the lights' triangle bins (every frame of a batch agrees: capi.hip); deep trees keep
+  // the walk
+  const bool pbins = !DEEP && p.point_bins;
+  // its grid: a wave per 64 point-light rays (at most one per pixel), at most the resident waves (8 per SIMD), each
+  // striding over the lists' chunks
+  auto point_blocks = [](int pixels) { return std::max(1, std::min((pixels + 255) / 256, 256 * 8)); };
   // deep trees keep one stream: both walks would use the pixel's spill columns
   const bool split = fk && !DEEP && p.max_depth > 1;
   // paths end in place (shade_fold; a path of no bounce has no shade to end in: wf_finalize writes its colour)
@@ -1846,6 +2013,8 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
         lb.counts[b] = ps[b].wf.counters + kWfCtr * i + kCtrHdr;
       }
       int* strag = p.wf.counters + kWfCtr * i + kCtrStrag;  // shadow rays handed to the cooperative walk
+      if (pbins)  // the point-light rays by the lights' triangle bins; the walk below takes the other lists
+        hipLaunchKernelGGL(wf_shadow_point_bins, dim3(point_blocks(nb * N)), dim3(256), 0, ss, p, lb, cap, strag);
       if constexpr (!DEEP)
         if (wide) {
           hipLaunchKernelGGL((wf_trace_shadow_refill<kWideKS, false, true>), dim3(refill_blocks(2 * nb * N, p.refill_grid)), dim3(kTB), 0,
@@ -1854,20 +2023,26 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
       if (!wide)
         hipLaunchKernelGGL((wf_trace_shadow_refill<KS, DEEP, false>), dim3(refill_blocks(2 * nb * N, p.refill_grid)), dim3(kTB), 0, ss,
                            p, lb, cap, p.wf.counters + kWfCtr * i + kCtrQShadow, strag);
-      if (p.wf.shadow_budget || wide)
+      if (p.wf.shadow_budget || wide || pbins)  // (the bins hand the rays they cannot take to it)
         hipLaunchKernelGGL(wf_shadow_coop, dim3(kCoopBlocks), dim3(64 * kCoopWaves), 0, ss, p, (const int*)strag);
     } else {
       for (int b = 0; b < nb; ++b) {
         const PTParams& f = ps[b];
         const int* shadow = f.wf.counters + kWfCtr * i + kCtrHdr;
         int* strag = f.wf.counters + kWfCtr * i + kCtrStrag;
+        if (pbins) {
+          ListBatch one{1, N, {}, {}};
+          one.list[0] = f.wf.shadow_list;
+          one.counts[0] = shadow;
+          hipLaunchKernelGGL(wf_shadow_point_bins, dim3(point_blocks(N)), dim3(256), 0, ss, f, one, cap, strag);
+        }
         if (f.scene.bvh4)
           hipLaunchKernelGGL((wf_trace_shadow<KS, true, DEEP>), dim3(gT2), dim3(kTB), 0, ss, f,
                              (const int*)f.wf.shadow_list, shadow, cap, strag);
         else
           hipLaunchKernelGGL((wf_trace_shadow<KS, false, DEEP>), dim3(gT2), dim3(kTB), 0, ss, f,
                              (const int*)f.wf.shadow_list, shadow, cap, strag);
-        if (f.wf.shadow_budget)
+        if (f.wf.shadow_budget || pbins)
           hipLaunchKernelGGL(wf_shadow_coop, dim3(kCoopBlocks), dim3(64 * kCoopWaves), 0, ss, f, (const int*)strag);
       }
     }

@@ -169,7 +169,10 @@ struct WFState {
 // (lane-refill walks), those toward point lights and those found occluded.
 enum { kStatPrimRays, kStatPrimVisits, kStatBounceRays, kStatBounceVisits, kStatShadowRays, kStatShadowVisits,
        kStatTieRewalks, kStatPrimRetries, kStatSpills, kStatPrimSlots, kStatBounceSlots, kStatShadowSlots,
-       kStatShadowPoint, kStatShadowOccluded, kStatCount };
+       kStatShadowPoint, kStatShadowOccluded,
+       // point-light rays the light's triangle bins decided (wf_shadow_point_bins) / handed to the walk instead
+       kStatShadowPointBinned, kStatShadowPointFallback, kStatCount };
+constexpr int kStatCountV2 = kStatShadowOccluded + 1;  // the 14 counters pt_trace_stats_count() has always reported
 
 // A path-tracing draw over several frames' pixels (pt_pass_draw_batch): frame b's pixels are the pids
 // [b * n, (b + 1) * n) of one shared per-pixel wavefront state; its lists hold frame-local pids. The list-driven
@@ -200,6 +203,26 @@ struct Bins {
   int large_cap;
   int* ctr;             // [0] large items, [1] binned pairs, [2] overflow (the caller's fallback then runs)
   int W, y0, y1;        // band: tiles counted from row y0
+};
+
+// Point-light triangle bins (kernels_pointbins.hip): per light l < nl a cube map of 6 x R x R direction cells around
+// the light. Cell c = (face * R + row) * R + column of light l has the header hdr[l * (ncell + 1) + c] = (first
+// entry, entries) into ent + l * cap; header ncell is the light's catch-all list (triangles the build cannot bound:
+// every ray to the light tests them). An entry is (triangle, float bits of `near`, sub-cell box, 0): `near` a lower
+// bound of the distance from the light to any point of the triangle a shadow ray can be found to hit (a cell's
+// entries ascend by it); the box (x0 | x1 << 8 | y0 << 16 | y1 << 24, in 1 / 256 of the cell) holds every direction
+// of the cell from which such a ray can arrive.
+// info: kPointBinsInfo ints per light: [0] != 0: the light has no usable bins (a non-finite position, or the entries
+// overflowed `cap`: its rays walk), [1] entries, [2..4] float bits of the light position the bins were built around,
+// [5] float bits of Mtot, the coordinate magnitude of the scene plus the light's, [6] the catch-all list's entries.
+constexpr int kPointBinsInfo = 8;
+constexpr int kPointBinsMaxR = 128;  // (the build packs a cell box into 4 x 8 bits)
+struct PointBinsDev {
+  const int2* hdr;
+  const uint4* ent;
+  const int* info;
+  int R, nl, cap;
+  __host__ __device__ int ncell() const { return 6 * R * R; }
 };
 
 struct PTParams {
@@ -246,6 +269,10 @@ struct PTParams {
   Bins leaf_bins;
   int primary_raster;
   const int* pr_fix;
+  // point_bins != 0: the point-light shadow rays of the lights with usable bins are decided by wf_shadow_point_bins
+  // over `pbins`; the shadow walks take the HDR rays and the other lights' (uniform point_bins; capi.hip point_bins_for)
+  int point_bins;
+  PointBinsDev pbins;
 };
 
 struct GBufParams {
@@ -403,6 +430,10 @@ int launch_output(const OutputParams& p, hipStream_t s);
 int launch_taa(const TAAParams& p, hipStream_t s);
 int launch_tile_sort(uint32_t* cost, int* perm, int ntiles, hipStream_t s);  // cost -> perm, clears cost
 int launch_hdr_merge(const float4* hdr, const float4* cache, float4* out, int n, hipStream_t s);  // (hdr.xyz, cache.z)
+// Point-light triangle bins of `nl` lights (sc.lights, 6 floats each) over sc's triangles with R x R cells per cube
+// face: point_bins_bytes() bytes at `base`; *out describes them. Everything runs on s; nothing is read back.
+size_t point_bins_bytes(int ntris, int nl, int R);
+int launch_point_bins_build(const SceneDev& sc, int nl, int R, void* base, PointBinsDev* out, hipStream_t s);
 }  // namespace ptk
 
 namespace ptk {

@@ -124,6 +124,8 @@ _PT_SIGS = [
     ("pt_pass_set_trace_stats", C.c_int, [_u32, C.c_void_p]),
     ("pt_pass_set_trace_stats_n", C.c_int, [_u32, C.c_void_p, C.c_int]),
     ("pt_trace_stats_count", C.c_int, []),
+    ("pt_trace_stats_total", C.c_int, []),
+    ("pt_point_bins_info", C.c_int, [_u32, _u32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     ("pt_pass_draw", C.c_int, [_u32]),
     ("pt_pass_draw_batch", C.c_int, [C.POINTER(_u32), C.c_int]),
     ("pt_pass_last_ms", C.c_int, [_u32, _fp]),

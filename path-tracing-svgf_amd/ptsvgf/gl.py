@@ -130,6 +130,20 @@ def lbvh_trees(tex: int, source: int = 0) -> dict:
     return out
 
 
+def point_bins_info(tri_tex: int, node_tex: int) -> dict:
+    """pt_point_bins_info: the point-light triangle bins the last path-tracing draw of the scene (tri_tex, node_tex)
+    built: cells per face edge R, lights, entry capacity per light, allocated bytes, and per light {"off": no usable
+    bins, "entries", "catch_all", "pos", "magnitude"}."""
+    info = (C.c_int * 32)()
+    dims = (C.c_int * 4)()
+    nbytes = C.c_size_t()
+    check(pt().pt_point_bins_info(tri_tex, node_tex, info, dims, C.byref(nbytes)))
+    raw = np.array(list(info), np.int32).reshape(4, 8)
+    lights = [{"off": int(r[0]), "entries": int(r[1]), "catch_all": int(r[6]), "pos": r[2:5].view(np.float32).tolist(),
+               "magnitude": float(r[5:6].view(np.float32)[0])} for r in raw[:dims[1]]]
+    return {"R": dims[0], "lights": dims[1], "cap": dims[2], "bytes": nbytes.value, "per_light": lights}
+
+
 class PtTileSeg(C.Structure):
     _fields_ = [("y_begin", C.c_int), ("y_end", C.c_int), ("offset", C.c_int), ("packed", C.c_void_p)]
 

@@ -439,6 +439,11 @@ class Renderer:
             # (their launch tails overlap): 4K serial 131.3 -> 145.4 fps, surface view 48.3 -> 49.3; with frames in
             # flight the other frames already fill those tails (215.7 / 215.6 fps at K = 4, profiles/r04/fork/)
             p.set_uniform_int("trace_fork", 1 if self.K == 1 else 0)
+            # point-light shadow rays by the lights' triangle bins: +3.4 % at 4K with K = 4; one frame at a
+            # time the bins' launch and the HDR walk run one after the other and measured 2.6 % slower
+            # (profiles/point_bins/ab_first.log): off then. With frames in flight the library's default holds.
+            if self.K == 1:
+                p.set_uniform_int("point_bins", 0)
             # a ray still walking past VISIT_BUDGET node + triangle visits is finished by the wave-cooperative walk
             # (same bits): the launches no longer end on a few long walks. Round 5, same box (profiles/r05/serial/):
             # one frame at a time with lane refill 145.2 -> 160.8 fps at 4K (budgets 128 / 512: 151.3 / 151.8; refill
@@ -833,13 +838,16 @@ class Renderer:
     STAT_KEYS = ("primary_rays", "primary_visits", "bounce_rays", "bounce_visits", "shadow_rays", "shadow_visits",
                  "tie_rewalks", "primary_retries", "spills", "primary_slots", "bounce_slots",
                  "shadow_slots", "shadow_point_rays", "shadow_occluded")  # pt_pass_set_trace_stats order (pt_device.h kStat*)
+    # the counters after those (pt_trace_stats_total): point-light rays decided by the lights' triangle bins / walked
+    STAT_KEYS_POINT_BINS = ("shadow_point_binned", "shadow_point_fallback")
 
     def trace_stats(self) -> dict:
         """Render one frame with the path tracer's traversal counters on (pt_pass_set_trace_stats): rays traced and
         node + triangle visits per traversal kind. Synchronises; diagnostics, not for timed frames."""
         import torch
 
-        buf = torch.zeros(len(self.STAT_KEYS), dtype=torch.int64, device="cuda")
+        keys = self.STAT_KEYS + self.STAT_KEYS_POINT_BINS
+        buf = torch.zeros(len(keys), dtype=torch.int64, device="cuda")
         self.flush()  # frames already issued are not counted
         torch.cuda.synchronize()
         for p, _ in self.pt_slots:
@@ -851,7 +859,7 @@ class Renderer:
         finally:
             for p, _ in self.pt_slots:
                 p.set_trace_stats(0)
-        return dict(zip(self.STAT_KEYS, (int(v) for v in buf.cpu().tolist())))
+        return dict(zip(keys, (int(v) for v in buf.cpu().tolist())))
 
     def latency_ms(self) -> float | None:
         """Mean camera-to-modulate latency (ms) of the frames recorded since latency_events was set to a list: from
