@@ -22,7 +22,8 @@
  *   Rasterize_RenderPass::draw()            render_pass.h:64-79     -> pt_pass_draw
  *   glUniform*(glGetUniformLocation(...))   main.cpp:223-226,243-247,436-441 -> pt_pass_set_uniform_* (same)
  *   buildBVHwithSAH + node/triangle encode  Utils/BVH.h:42-173, main.cpp:88-151 -> pt_bvh_build (GPU, dynamic
- *                                           scenes: a different tree in the same buffer formats)
+ *                                           scenes: a different tree in the same buffer formats; pt_bvh_refit
+ *                                           keeps that tree and moves its boxes)
  *
  * Conventions:
  *  - handles are opaque uint32 owned by the library (0 is never a valid handle);
@@ -155,6 +156,22 @@ int pt_texbuffer_create(const void* host_data, size_t bytes, uint32_t fmt, uint3
  * Synchronous (waits for the build on the library stream). */
 int pt_bvh_build(uint32_t tri_in, int leaf_n, int ploc_radius, uint32_t tri_out, uint32_t node_out, int* out_nodes,
                  float* out_ms);
+/* Refit for geometry that moved but kept its triangles and their order (deformation, rigid motion): the topology
+ * of a built tree stays, only its boxes are recomputed. tri_out / node_out are the pair one pt_bvh_build call wrote,
+ * not written since (refits excepted); tri_in holds as many Triangle_encoded records as that build's tri_in, in its
+ * order (vertices and any other field may differ). After the call tri_out = tri_in permuted by the build's leaf
+ * order; every node's childs and leafInfo texels are unchanged bit for bit; a leaf's AA / BB are its triangles'
+ * min(p1, min(p2, p3)) / max(p1, max(p2, p3)) folded in leaf order from the first (lo = min(lo, lo_t)), an interior
+ * node's min / max (left, right) of its children's, glm's min / max throughout (tests/lbvh_refit_ref.py restates
+ * it); the dummy node 0 is untouched. Both buffers are written where they lie (no staging copy); their host mirrors
+ * are brought up to date when next read. The walk trees are derived again as in pt_bvh_build (a new set replaces the
+ * old) and both textures' versions advance, so the next draw decodes the triangles and reads the new trees. The
+ * caller has no draw in flight that reads these buffers. Synchronous on the library stream.
+ * out_ms: device time, the derivation included (NULL: skipped).
+ * PT_ERR_ARG: a handle used twice, a non-texbuffer, tri_in not whole records or another triangle count than the
+ * build's. PT_ERR_STATE: tri_out / node_out are not a pair of one pt_bvh_build, or one of them was written by
+ * another build or upload since. On either the buffers and their trees are unchanged. */
+int pt_bvh_refit(uint32_t tri_in, uint32_t tri_out, uint32_t node_out, float* out_ms);
 int pt_texarray_create(int width, int height, int layers, uint32_t* out_tex);     /* RGBA8 2-D array */
 int pt_texarray_upload_layer(uint32_t tex, int layer, int width, int height, int channels,
                              const uint8_t* host_data);
@@ -178,6 +195,15 @@ int pt_raster_pass_bind(uint32_t pass, const float* vertices, size_t n_floats); 
  * builder (LBVH, PLOC top with ploc_radius > 0) and its records decoded on the device; the G-buffer does not depend
  * on the tree (closest t, ties to the lower original index), so the planes equal the host bind's bit for bit. */
 int pt_raster_pass_bind_device(uint32_t pass, const void* device_vertices, size_t n_floats, int ploc_radius);
+/* Refit of a pass pt_raster_pass_bind_device bound (not sharing), for a DEVICE vertex list of the same triangles in
+ * the same order at new positions: the records are decoded again in the bind's leaf order (a record's original index
+ * is unchanged), the bind's tree keeps its topology and gets new boxes, and the packed tree is derived from it again.
+ * Displacement records are dropped, as a bind drops them (pt_raster_pass_set_prev_vertices sets new ones; its order
+ * argument still holds). Passes sharing this pass see the new records. Complete when it returns; no draw of the pass
+ * may be in flight. PT_ERR_ARG: another triangle count, a sharing pass, a non-raster pass. PT_ERR_STATE: the pass was
+ * bound on the host, or its device bind took the host fallback (a tree too deep for the walk's stack): bind again.
+ * On either the pass draws as before. */
+int pt_raster_pass_refit_device(uint32_t pass, const void* device_vertices, size_t n_floats);
 /* Dynamic scenes, no GL counterpart: the vertex list this (bound, not sharing) rasterize pass's triangles had one
  * frame ago. Both lists are DEVICE pointers in pt_raster_pass_bind's layout with the bound triangle count and order.
  * device_prev = NULL drops the records. While records are bound and the pass's int uniform object_motion is not 0

@@ -27,6 +27,7 @@
 
 #include "../../include/ptsvgf.h"
 #include "../../include/ptsvgf_debug.h"
+#include "../../include/ptsvgf_debug_refit.h"
 #include "../../include/ptsvgf_scene.h"
 #include "glsl_builtins.h"
 #include "pt_device.h"
@@ -70,6 +71,13 @@ struct Texture {
   bool lbvh = false;     // written by pt_bvh_build (the device copy is authoritative: get_scene decodes it there)
   // a node buffer pt_bvh_build wrote: the walk trees the device derived from it (owned; trees->version == version)
   ptk::LbvhTrees* trees = nullptr;
+  // a node buffer pt_bvh_build wrote: what pt_bvh_refit needs (owned, held as trees is) and the pair it belongs to,
+  // the triangle buffer's handle and both versions as the build (or the last refit) left them
+  ptk::LbvhRefit* refit = nullptr;
+  uint32_t refit_tri = 0;
+  uint64_t refit_tri_ver = 0, refit_node_ver = 0;
+  // pt_bvh_refit wrote dev in place; host is brought up to date by its readers (refresh_host)
+  bool host_stale = false;
 };
 
 void free_trees(Texture* t) {
@@ -77,6 +85,13 @@ void free_trees(Texture* t) {
   ptk::lbvh_trees_free(*t->trees);
   delete t->trees;
   t->trees = nullptr;
+}
+
+void free_refit(Texture* t) {
+  if (!t->refit) return;
+  ptk::lbvh_refit_free(*t->refit);
+  delete t->refit;
+  t->refit = nullptr;
 }
 
 struct Uniform {
@@ -94,7 +109,21 @@ struct RasterScene {
   int root_ref = 0;
   int stack_need = 0;
   int ntris = 0;
+  // pt_raster_pass_bind_device: the encoded nodes of the bind and what refits them (pt_raster_pass_refit_device);
+  // null after a host bind
+  float* enc_nodes = nullptr;
+  ptk::LbvhRefit* refit = nullptr;
+  int bvh_records = 0;  // packed records bvh has room for (that bind's)
 };
+
+void free_raster_refit(RasterScene& r) {
+  if (r.enc_nodes) (void)hipFree(r.enc_nodes);
+  r.enc_nodes = nullptr;
+  if (!r.refit) return;
+  ptk::lbvh_refit_free(*r.refit);
+  delete r.refit;
+  r.refit = nullptr;
+}
 
 // Scratch of the tile-binned G-buffer (launch_gbuffer_raster), per rasterize pass, sized by its triangles and band.
 struct RasterBins {
@@ -1428,6 +1457,18 @@ static int upload_leaves(const float* ne, size_t nnodes, SceneGPU& sg) {
   return upload_vec(lv, &sg.leaves);
 }
 
+// The host mirror of a texbuffer pt_bvh_refit wrote in place is lazy: the refit pays no copy, and whoever reads
+// t->host's contents calls this first (pt_debug_lbvh_trees source 1, get_scene's host decode; pt_texture_readback
+// reads the device copy, and get_scene_lbvh only the sizes, which a refit keeps).
+int refresh_host(Texture* t) {
+  if (!t->host_stale) return PT_OK;
+  HIPCHK(hipDeviceSynchronize());
+  t->host.resize(t->bytes);
+  if (t->bytes) HIPCHK(hipMemcpy(t->host.data(), t->dev, t->bytes, hipMemcpyDeviceToHost));
+  t->host_stale = false;
+  return PT_OK;
+}
+
 // A scene pt_bvh_build wrote (dynamic scenes): its triangles are decoded on the device (decode_tris: the host
 // decode's built-ins, the same records), and its own tree (an LBVH, not the reference's SAH tree) serves every walk:
 // the packed binary tree (also the any-hit tree), the leaf list and the greedy 4-wide form of that tree are the ones
@@ -1483,6 +1524,8 @@ int get_scene(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU*
   size_t nnodes = nodes->host.size() / (12 * sizeof(float));
   if (tris->lbvh && nodes->lbvh) return get_scene_lbvh(tris, nodes, sg, out);
   drop_borrowed(sg);
+  if (const int rc = refresh_host(tris)) return rc;  // a refitted buffer paired with a host-written one
+  if (const int rc = refresh_host(nodes)) return rc;
   const float* te = (const float*)tris->host.data();
   std::vector<float4> geom(ntris * 4), shade(ntris * 9);
   for (size_t i = 0; i < ntris; ++i) {
@@ -2418,6 +2461,7 @@ static int texbuffer_take(Texture* t, const void* dev_src, size_t bytes) {
   }
   t->version++;
   t->lbvh = true;
+  t->host_stale = false;
   return PT_OK;
 }
 
@@ -2464,6 +2508,7 @@ int pt_shutdown(void) {
     if (t->aux) (void)hipFree(t->aux);
     if (t->tflags) (void)hipFree(t->tflags);
     free_trees(t);
+    free_refit(t);
   }
   for (auto& kv : g.passes) {
     Pass* p = kv.second.get();
@@ -2471,6 +2516,7 @@ int pt_shutdown(void) {
     if (p->raster.nrm) (void)hipFree(p->raster.nrm);
     if (p->raster.disp) (void)hipFree(p->raster.disp);
     if (p->raster.bvh) (void)hipFree(p->raster.bvh);
+    free_raster_refit(p->raster);
     if (p->bins.base) (void)hipFree(p->bins.base);
     if (p->wf.base) (void)hipFree(p->wf.base);
     if (p->wf.spill) (void)hipFree(p->wf.spill);
@@ -2774,8 +2820,14 @@ int pt_bvh_build(uint32_t tri_in, int leaf_n, int ploc_radius, uint32_t tri_out,
     (void)hipEventRecord(e0, g.stream);
   }
   int nodes = 0;
-  int rc = ptk::lbvh_build(g_lbvh, (const float*)ti->dev, ptk::kTriEncoded, n, leaf_n, ploc_radius, tbuf, nbuf,
-                           nullptr, &nodes, g.stream);
+  // what a later pt_bvh_refit needs is kept with the node texture: the leaf order the build writes and the parent
+  // links of its output nodes (the allocation of the previous build is reused while the triangle count holds)
+  if (!no->refit) no->refit = new ptk::LbvhRefit;
+  int rc = ptk::lbvh_refit_alloc(*no->refit, n);
+  if (rc == 0)
+    rc = ptk::lbvh_build(g_lbvh, (const float*)ti->dev, ptk::kTriEncoded, n, leaf_n, ploc_radius, tbuf, nbuf,
+                         no->refit->order, &nodes, g.stream);
+  if (rc == 0) rc = ptk::lbvh_refit_link(*no->refit, nbuf, nodes, g.stream);
   // the walk trees of the new nodes, derived where they lie; their counters arrive with the final sync below
   std::unique_ptr<ptk::LbvhTrees> trees(new ptk::LbvhTrees);
   int trc = rc == 0 ? ptk::lbvh_trees_launch(g_lbvh, nbuf, nodes, *trees, g.stream) : 0;
@@ -2799,13 +2851,92 @@ int pt_bvh_build(uint32_t tri_in, int leaf_n, int ploc_radius, uint32_t tri_out,
   if (rc == PT_OK) {
     trees->version = no->version;
     no->trees = trees.release();
+    no->refit_tri = tri_out;
+    no->refit_tri_ver = to->version;
+    no->refit_node_ver = no->version;
   } else {
     ptk::lbvh_trees_free(*trees);
+    free_refit(no);
   }
   (void)hipFree(tbuf);
   (void)hipFree(nbuf);
   if (rc == PT_OK && out_nodes) *out_nodes = nodes;
   return rc;
+}
+
+int pt_bvh_refit(uint32_t tri_in, uint32_t tri_out, uint32_t node_out, float* out_ms) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  Texture *ti = tex_of(tri_in), *to = tex_of(tri_out), *no = tex_of(node_out);
+  if (!ti || !to || !no || ti->target != PT_TEXTURE_BUFFER || to->target != PT_TEXTURE_BUFFER ||
+      no->target != PT_TEXTURE_BUFFER)
+    return err(PT_ERR_ARG, "pt_bvh_refit: tri_in, tri_out and node_out must be texture buffers");
+  if (tri_in == tri_out || tri_in == node_out || tri_out == node_out)
+    return err(PT_ERR_ARG, "pt_bvh_refit: tri_in, tri_out and node_out must be three different buffers");
+  ptk::LbvhRefit* rf = no->refit;
+  if (!to->lbvh || !no->lbvh || !rf || !rf->base || rf->nnodes < 2 || !no->trees || no->refit_tri != tri_out ||
+      no->refit_tri_ver != to->version || no->refit_node_ver != no->version || no->trees->version != no->version ||
+      !to->dev || !no->dev || to->bytes != (size_t)rf->n * 45 * sizeof(float) ||
+      no->bytes != (size_t)rf->nnodes * 12 * sizeof(float))
+    return err(PT_ERR_STATE, "pt_bvh_refit: tri_out and node_out are not the untouched pair of one pt_bvh_build");
+  if (ti->bytes == 0 || ti->bytes % (45 * sizeof(float)) || !ti->dev)
+    return err(PT_ERR_ARG, "pt_bvh_refit: tri_in must hold whole Triangle_encoded records (45 floats)");
+  if (ti->bytes != to->bytes) return err(PT_ERR_ARG, "pt_bvh_refit: tri_in holds another triangle count than the build");
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (out_ms) {
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, g.stream);
+  }
+  // both buffers are written where they lie: no staging, no copy (the host mirrors turn lazy, refresh_host)
+  int rc = ptk::lbvh_refit_reorder(*rf, (const float*)ti->dev, (float*)to->dev, g.stream);
+  if (rc == 0) rc = ptk::lbvh_refit_nodes(*rf, (float*)no->dev, (const float*)ti->dev, ptk::kTriEncoded, g.stream);
+  std::unique_ptr<ptk::LbvhTrees> trees(new ptk::LbvhTrees);
+  int trc = rc == 0 ? ptk::lbvh_trees_launch(g_lbvh, (const float*)no->dev, rf->nnodes, *trees, g.stream, rf->err) : 0;
+  if (out_ms) {
+    (void)hipEventRecord(e1, g.stream);
+    (void)hipEventSynchronize(e1);
+    (void)hipEventElapsedTime(out_ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  rc = rc == 0 ? PT_OK : hip_err((hipError_t)rc, "pt_bvh_refit");
+  {  // also after a failure: the stage's counters are copied into `trees`
+    hipError_t e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess && rc == PT_OK) rc = hip_err(e, "pt_bvh_refit");
+  }
+  if (rc == PT_OK && trc == 0) trc = ptk::lbvh_trees_finish(*trees);
+  if (rc == PT_OK && trc != 0) rc = err(PT_ERR_HIP, "pt_bvh_refit: deriving the walk trees failed");
+  // the contents changed whatever came of it: the old trees go, and every consumer re-reads
+  to->version++;
+  no->version++;
+  to->host_stale = no->host_stale = true;
+  free_trees(no);
+  if (rc == PT_OK) {
+    trees->version = no->version;
+    no->trees = trees.release();
+    no->refit_tri_ver = to->version;
+    no->refit_node_ver = no->version;
+  } else {
+    ptk::lbvh_trees_free(*trees);
+    free_refit(no);
+  }
+  return rc;
+}
+
+int pt_debug_lbvh_order(uint32_t node_tex, int* host_out, size_t cap, size_t* n) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  Texture* t = tex_of(node_tex);
+  if (!t || t->target != PT_TEXTURE_BUFFER) return err(PT_ERR_INVALID_HANDLE, "pt_debug_lbvh_order: not a texture buffer");
+  if (!t->lbvh || !t->refit || !t->refit->base || t->refit_node_ver != t->version)
+    return err(PT_ERR_STATE, "pt_debug_lbvh_order: not a node buffer pt_bvh_build wrote");
+  if (n) *n = (size_t)t->refit->n;
+  if (!host_out) return PT_OK;
+  if (cap < (size_t)t->refit->n) return err(PT_ERR_ARG, "pt_debug_lbvh_order: host_out is too small");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(host_out, t->refit->order, sizeof(int) * (size_t)t->refit->n, hipMemcpyDeviceToHost));
+  return PT_OK;
 }
 
 int pt_texture_readback_aux(uint32_t tex, float* host_out, size_t cap, size_t* bytes) {
@@ -2843,6 +2974,7 @@ int pt_debug_lbvh_trees(uint32_t node_tex, int source, int which, void* host_out
     n = which == 0 ? (size_t)tr.nbin() * 4 : which == 1 ? (size_t)tr.nleaves() * 2 : (size_t)tr.nwide() * ptk::kWideStride;
   } else {
     // the host functions over the host mirror of the texels: what the device stage has to equal
+    TRY(refresh_host(t));
     const float* ne = (const float*)t->host.data();
     const int nnodes = (int)(t->host.size() / (12 * sizeof(float)));
     std::vector<float4> bin, leaves, wide;
@@ -2966,6 +3098,7 @@ int pt_texture_destroy(uint32_t tex) {
   if (it->second->aux) (void)hipFree(it->second->aux);
   if (it->second->tflags) (void)hipFree(it->second->tflags);
   free_trees(it->second.get());  // the scenes that borrowed them are dropped below
+  free_refit(it->second.get());
   g.textures.erase(it);
   for (auto hm = g.hdr_merged.begin(); hm != g.hdr_merged.end();) {  // merged environments built from it
     if (hm->first.first == tex || hm->first.second == tex) {
@@ -3029,6 +3162,7 @@ int pt_raster_pass_bind(uint32_t pass, const float* verts, size_t n_floats) {
   if (n_floats % 18) return err(PT_ERR_ARG, "vertex list must be whole triangles of pos3+nrm3");
   int ntris = (int)(n_floats / 18);
   drop_disp(p);  // the triangle order changes
+  free_raster_refit(p->raster);  // a host-built tree is not refitted
   p->raster.ntris = ntris;
   p->raster_src = 0;
   p->bound = true;
@@ -3093,18 +3227,28 @@ int pt_raster_pass_bind_device(uint32_t pass, const void* dverts, size_t n_float
   p->raster.ntris = ntris;
   p->raster_src = 0;
   p->bound = true;
+  free_raster_refit(p->raster);  // of the bind this one replaces
   if (ntris == 0) return PT_OK;
   float* nbuf = nullptr;
-  int* order = nullptr;
+  // the encoded nodes, the leaf order and the parent links stay with the pass after a device bind
+  // (pt_raster_pass_refit_device)
+  std::unique_ptr<ptk::LbvhRefit> rf(new ptk::LbvhRefit);
   HIPCHK(hipMalloc(&nbuf, (size_t)2 * ntris * 12 * sizeof(float)));
-  if (hipMalloc(&order, (size_t)ntris * sizeof(int)) != hipSuccess) {
+  if (ptk::lbvh_refit_alloc(*rf, ntris) != 0) {
     (void)hipFree(nbuf);
     return err(PT_ERR_HIP, "pt_raster_pass_bind_device: out of device memory");
   }
-  auto release = [&]() { (void)hipFree(nbuf); (void)hipFree(order); };
+  const int* order = rf->order;
+  bool keep = false;
+  auto release = [&]() {
+    if (keep) return;
+    (void)hipFree(nbuf);
+    ptk::lbvh_refit_free(*rf);
+  };
   int nodes = 0;
   int rc = ptk::lbvh_build(g_lbvh, (const float*)dverts, ptk::kRasterVerts, ntris, 8, ploc_radius, nullptr, nbuf,
-                           order, &nodes, g.stream);
+                           rf->order, &nodes, g.stream);
+  if (rc == 0) rc = ptk::lbvh_refit_link(*rf, nbuf, nodes, g.stream);
   if (rc) { release(); return hip_err((hipError_t)rc, "raster lbvh_build"); }
   // the packed binary tree (pack_bvh's records) and its depth come from the device stage: no node readback
   ptk::LbvhTrees trees;
@@ -3147,9 +3291,57 @@ int pt_raster_pass_bind_device(uint32_t pass, const void* dverts, size_t n_float
   p->raster.stack_need = need;
   // draws of other frames may run on other streams: the records are complete when this returns
   const hipError_t e = hipStreamSynchronize(g.stream);
+  if (e == hipSuccess) {
+    p->raster.enc_nodes = nbuf;
+    p->raster.refit = rf.release();
+    p->raster.bvh_records = std::max(1, trees.nbin());
+    keep = true;
+  }
   release();
   release_trees();
   if (e != hipSuccess) return hip_err(e, "pt_raster_pass_bind_device");
+  return PT_OK;
+}
+
+int pt_raster_pass_refit_device(uint32_t pass, const void* dverts, size_t n_floats) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (g.programs[p->program] != PK_RASTER) return err(PT_ERR_ARG, "not a rasterize pass");
+  if (p->raster_src) return err(PT_ERR_ARG, "pt_raster_pass_refit_device: the pass shares another pass's triangles");
+  RasterScene& rs = p->raster;
+  if (!p->bound || !rs.refit || !rs.refit->base || !rs.enc_nodes || !rs.geom || !rs.nrm || !rs.bvh ||
+      rs.refit->n != rs.ntris)
+    return err(PT_ERR_STATE, "pt_raster_pass_refit_device: the pass was not bound by pt_raster_pass_bind_device "
+                             "(or took its host fallback): bind again");
+  if (n_floats != (size_t)rs.ntris * 18)
+    return err(PT_ERR_ARG, "pt_raster_pass_refit_device: not the bound triangle count");
+  if (!dverts) return err(PT_ERR_ARG, "null device vertex list");
+  drop_disp(p);  // their values are stale
+  ptk::LbvhRefit& rf = *rs.refit;
+  // records in the kept leaf order (the original index in geom[4k].w stays), boxes of the kept nodes, then the
+  // packed tree from the device stage as in the bind; its size is the bind's (same topology): copied in place
+  int rc = ptk::decode_raster((const float*)dverts, rf.order, rs.ntris, rs.geom, rs.nrm, g.stream);
+  if (rc == 0) rc = ptk::lbvh_refit_nodes(rf, rs.enc_nodes, (const float*)dverts, ptk::kRasterVerts, g.stream);
+  ptk::LbvhTrees trees;
+  if (rc == 0) rc = ptk::lbvh_trees_launch(g_lbvh, rs.enc_nodes, rf.nnodes, trees, g.stream, rf.err);
+  if (hipStreamSynchronize(g.stream) != hipSuccess && rc == 0) rc = (int)hipErrorUnknown;
+  if (rc == 0) rc = ptk::lbvh_trees_finish(trees);
+  if (rc == 0 && (trees.dev_info[1] != rs.stack_need || std::max(1, trees.nbin()) != rs.bvh_records))
+    rc = (int)hipErrorInvalidValue;  // the topology is the bind's: the same depth and as many records
+  if (rc == 0) {
+    const size_t bvh_bytes = (size_t)std::max(1, trees.nbin()) * 4 * sizeof(float4);
+    rc = (int)hipMemcpyAsync(rs.bvh, trees.bin, bvh_bytes, hipMemcpyDeviceToDevice, g.stream);
+    rs.root_ref = trees.dev_info[0];
+    // draws of other frames may run on other streams: the records are complete when this returns
+    if (rc == 0) rc = (int)hipStreamSynchronize(g.stream);
+  }
+  ptk::lbvh_trees_free(trees);
+  if (rc != 0) {
+    free_raster_refit(rs);  // the records may be half written: the caller binds again
+    return hip_err((hipError_t)rc, "pt_raster_pass_refit_device");
+  }
   return PT_OK;
 }
 
@@ -3463,6 +3655,7 @@ int pt_pass_destroy(uint32_t pass) {
   if (p->raster.nrm) (void)hipFree(p->raster.nrm);
   if (p->raster.disp) (void)hipFree(p->raster.disp);
   if (p->raster.bvh) (void)hipFree(p->raster.bvh);
+  free_raster_refit(p->raster);
   if (p->bins.base) (void)hipFree(p->bins.base);
   if (p->wf.base) (void)hipFree(p->wf.base);
   if (p->wf.spill) (void)hipFree(p->wf.spill);

@@ -532,13 +532,15 @@ __device__ __forceinline__ float tex_area(const float* __restrict__ nodes, int i
 
 __global__ void __launch_bounds__(256) trees_local(const float* __restrict__ nodes, int nn, int* __restrict__ parent,
                                                     int4* __restrict__ ch, int2* __restrict__ sz,
-                                                    int* __restrict__ leaf, int* __restrict__ info) {
+                                                    int* __restrict__ leaf, int* __restrict__ info,
+                                                    const int* __restrict__ refit_err) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= nn) return;
   sz[i] = int2{0, 0};
   ch[i] = int4{-1, -1, -1, -1};
   if (i == 0) {
     leaf[0] = 0;
+    if (refit_err && *refit_err) atomicOr(&info[kInfoErr], 4);  // a refit before this stage met a bad index
     return;
   }
   const NodeTex t = node_tex(nodes, i);
@@ -777,6 +779,98 @@ __global__ void __launch_bounds__(256) trees_emit(const float* __restrict__ node
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Refit (lbvh_refit_nodes): geometry that moved but kept its triangles and their order keeps the tree's topology;
+// only the boxes are recomputed, in the node texels where they lie. Defined by tests/lbvh_refit_ref.py.
+
+// parent[child] = node for every interior node of a built tree (parent pre-set to -1: the root keeps it)
+__global__ void __launch_bounds__(256) refit_link(const float* __restrict__ nodes, int nn, int* __restrict__ parent,
+                                                   int* __restrict__ err) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < 1 || i >= nn) return;
+  const NodeTex t = node_tex(nodes, i);
+  if (t.n > 0) return;
+  if (!node_ok(t.left, nn) || !node_ok(t.right, nn) || t.left == t.right) {
+    atomicOr(err, 1);
+    return;
+  }
+  parent[t.left] = i;
+  parent[t.right] = i;
+}
+
+// One thread per output node. A leaf folds its triangles' boxes in leaf order, starting from the first, stores AA / BB
+// and climbs: lbvh_refit's arrive-second pattern over flags (zeroed by the host), the second child to arrive at a node
+// storing gmin / gmax (left, right) of its children's texels. Interior nodes do nothing at entry. Every index read from
+// a texel or a kept array is checked before it is followed; the climb is bounded by the depth (and by nn).
+__global__ void __launch_bounds__(256) refit_nodes(float* nodes, int nn, const float* __restrict__ tri, int ntris,
+                                                    TriLayout lay, const int* __restrict__ order,
+                                                    const int* __restrict__ parent, int* flags, int* __restrict__ err) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < 1 || i >= nn) return;
+  float* f = nodes + (size_t)i * kNodeFloats;
+  const int count = (int)f[3], first = (int)f[4];
+  if (count <= 0) return;
+  if (first < 0 || count > ntris || first > ntris - count) {
+    atomicOr(err, 1);
+    return;
+  }
+  float lo[3], hi[3];
+  for (int j = 0; j < count; ++j) {
+    const int o = order[first + j];
+    if (o < 0 || o >= ntris) {
+      atomicOr(err, 1);
+      return;
+    }
+    const float* t = tri + (size_t)o * lay.stride;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {  // BVH.h:54-66: min(p1, min(p2, p3)) per axis
+      const float tl = gmin(t[a], gmin(t[lay.o2 + a], t[lay.o3 + a]));
+      const float th = gmax(t[a], gmax(t[lay.o2 + a], t[lay.o3 + a]));
+      lo[a] = j == 0 ? tl : gmin(lo[a], tl);
+      hi[a] = j == 0 ? th : gmax(hi[a], th);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    f[6 + a] = lo[a];
+    f[9 + a] = hi[a];
+  }
+  int node = parent[i];
+  for (int step = 0; step < nn && node_ok(node, nn); ++step) {
+    // the first child to arrive stops; the second sees both boxes (acq_rel orders the box stores and loads)
+    if (__hip_atomic_fetch_add(&flags[node], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
+    float* p = nodes + (size_t)node * kNodeFloats;
+    const int l = (int)p[0], r = (int)p[1];
+    if (!node_ok(l, nn) || !node_ok(r, nn)) {
+      atomicOr(err, 1);
+      return;
+    }
+    const float* lf = nodes + (size_t)l * kNodeFloats;
+    const float* rf = nodes + (size_t)r * kNodeFloats;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = gmin(lf[6 + a], rf[6 + a]);
+      hi[a] = gmax(lf[9 + a], rf[9 + a]);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      p[6 + a] = lo[a];
+      p[9 + a] = hi[a];
+    }
+    node = parent[node];
+  }
+}
+
+// the moved triangles in the build's leaf order
+__global__ void __launch_bounds__(256) refit_reorder(const float* __restrict__ tri, const int* __restrict__ order,
+                                                      int n, float* __restrict__ out) {
+  const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (f >= (size_t)n * kTriFloats) return;
+  const int p = (int)(f / kTriFloats), q = (int)(f - (size_t)p * kTriFloats);
+  const int o = order[p];
+  if (o >= 0 && o < n) out[f] = tri[(size_t)o * kTriFloats + q];
+}
+
 }  // namespace
 
 int decode_raster(const float* verts, const int* order, int n, float4* geom, float4* nrm, hipStream_t s) {
@@ -952,7 +1046,8 @@ void lbvh_trees_free(LbvhTrees& t) {
   t = LbvhTrees{};
 }
 
-int lbvh_trees_launch(LbvhWork& w, const float* nodes, int nnodes, LbvhTrees& out, hipStream_t s) {
+int lbvh_trees_launch(LbvhWork& w, const float* nodes, int nnodes, LbvhTrees& out, hipStream_t s,
+                      const int* refit_err) {
   if (nnodes < 2 || out.base) return (int)hipErrorInvalidValue;
   const size_t nn = (size_t)nnodes;
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -1003,7 +1098,7 @@ int lbvh_trees_launch(LbvhWork& w, const float* nodes, int nnodes, LbvhTrees& ou
   if ((e = hipMemsetAsync(out.leaves, 0, sizeof(float4) * 2, s)) != hipSuccess) return (int)e;
   if ((e = hipMemsetAsync(out.wide, 0, sizeof(float4) * kWideStride, s)) != hipSuccess) return (int)e;
   const dim3 grid((unsigned)((nn + 255) / 256)), block(256);
-  hipLaunchKernelGGL(trees_local, grid, block, 0, s, nodes, nnodes, parent, ch, sz, leaf, info);
+  hipLaunchKernelGGL(trees_local, grid, block, 0, s, nodes, nnodes, parent, ch, sz, leaf, info, refit_err);
   size_t sb = scan_bytes;
   if ((e = rocprim::exclusive_scan(scratch, sb, leaf, leafpos, 0, nn, rocprim::plus<int>(), s)) != hipSuccess)
     return (int)e;
@@ -1015,6 +1110,59 @@ int lbvh_trees_launch(LbvhWork& w, const float* nodes, int nnodes, LbvhTrees& ou
   static_assert(sizeof(out.dev_info) == kInfoInts * sizeof(int), "dev_info holds the stage's counters");
   if ((e = hipMemcpyAsync(out.dev_info, info, sizeof(out.dev_info), hipMemcpyDeviceToHost, s)) != hipSuccess)
     return (int)e;
+  return (int)hipGetLastError();
+}
+
+int lbvh_refit_alloc(LbvhRefit& r, int n) {
+  if (n < 1) return (int)hipErrorInvalidValue;
+  if (r.base && r.n == n) return 0;
+  lbvh_refit_free(r);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_order = up(sizeof(int) * (size_t)n), b_nodes = up(sizeof(int) * 2 * (size_t)n);
+  const hipError_t e = hipMalloc(&r.base, b_order + 2 * b_nodes + 256);
+  if (e != hipSuccess) {
+    r.base = nullptr;
+    return (int)e;
+  }
+  r.order = (int*)r.base;
+  r.parent = (int*)((char*)r.base + b_order);
+  r.flags = (int*)((char*)r.base + b_order + b_nodes);
+  r.err = (int*)((char*)r.base + b_order + 2 * b_nodes);
+  r.n = n;
+  r.nnodes = 0;
+  return 0;
+}
+
+void lbvh_refit_free(LbvhRefit& r) {
+  if (r.base) (void)hipFree(r.base);
+  r = LbvhRefit{};
+}
+
+int lbvh_refit_link(LbvhRefit& r, const float* nodes, int nnodes, hipStream_t s) {
+  if (!r.base || nnodes < 2 || nnodes > 2 * r.n) return (int)hipErrorInvalidValue;
+  hipError_t e;
+  if ((e = hipMemsetAsync(r.parent, 0xff, sizeof(int) * (size_t)nnodes, s)) != hipSuccess) return (int)e;
+  if ((e = hipMemsetAsync(r.err, 0, sizeof(int), s)) != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(refit_link, dim3((nnodes + 255) / 256), dim3(256), 0, s, nodes, nnodes, r.parent, r.err);
+  r.nnodes = nnodes;
+  return (int)hipGetLastError();
+}
+
+int lbvh_refit_nodes(LbvhRefit& r, float* nodes, const float* tri, TriLayout lay, hipStream_t s) {
+  if (!r.base || r.nnodes < 2 || r.nnodes > 2 * r.n) return (int)hipErrorInvalidValue;
+  // flags start at 0 for every refit; err keeps what lbvh_refit_link found (a tree with a bad link is not climbed
+  // into a fault, every index is checked again, but it stays reported)
+  const hipError_t e = hipMemsetAsync(r.flags, 0, sizeof(int) * (size_t)r.nnodes, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(refit_nodes, dim3((r.nnodes + 255) / 256), dim3(256), 0, s, nodes, r.nnodes, tri, r.n, lay,
+                     r.order, r.parent, r.flags, r.err);
+  return (int)hipGetLastError();
+}
+
+int lbvh_refit_reorder(const LbvhRefit& r, const float* tri, float* tri_out, hipStream_t s) {
+  if (!r.base) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(refit_reorder, dim3((unsigned)(((size_t)r.n * kTriFloats + 255) / 256)), dim3(256), 0, s, tri,
+                     r.order, r.n, tri_out);
   return (int)hipGetLastError();
 }
 

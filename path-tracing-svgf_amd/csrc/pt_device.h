@@ -573,7 +573,7 @@ struct LbvhTrees {
   int cap_bin = 0, cap_leaves = 0, cap_wide = 0;  // records each part has room for
   // what the device reports (one copy): root_ref, need (deepest interior level), leaves, root4, need4, 4-wide nodes,
   // NaN flag (a child box of the 4-wide tree has a NaN coordinate), [7] unused; packed binary nodes; error bits
-  // (1: a child index out of range, 2: a record past its part's room)
+  // (1: a child index out of range, 2: a record past its part's room, 4: the refit before the stage met a bad index)
   int dev_info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   float stage_ms = 0.0f;  // device time of the stage
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -585,9 +585,31 @@ struct LbvhTrees {
 // Launches the stage on s over `nodes` (nnodes x 12 floats on the device, dummy node 0, root node 1) and the copy of
 // dev_info; nothing is read back before lbvh_trees_finish, which the caller runs after its next synchronisation of s
 // (it fails when the texels were no tree). Only ever run on lbvh_build's own output. Scratch comes from w.
-int lbvh_trees_launch(LbvhWork& w, const float* nodes, int nnodes, LbvhTrees& out, hipStream_t s);
+// refit_err (may be null): the error word of an lbvh_refit_nodes launched before on s; when set, the stage reports
+// error bit 4 with its own (dev_info[9]) and lbvh_trees_finish fails.
+int lbvh_trees_launch(LbvhWork& w, const float* nodes, int nnodes, LbvhTrees& out, hipStream_t s,
+                      const int* refit_err = nullptr);
 int lbvh_trees_finish(LbvhTrees& t);
 void lbvh_trees_free(LbvhTrees& t);
+
+// What a refit of a built tree needs beside its node texels (DESIGN.md "Refit"): the build's leaf order, a parent
+// index per output node and the climb's arrival counters. One allocation, sized for the n triangles of the build
+// (a tree over them has at most 2n nodes) and kept with the tree; reused by every refit.
+struct LbvhRefit {
+  void* base = nullptr;  // order[n] | parent[2n] | flags[2n] | err (the owner frees it: lbvh_refit_free)
+  int *order = nullptr, *parent = nullptr, *flags = nullptr, *err = nullptr;
+  int n = 0, nnodes = 0;  // triangles; output nodes (set by lbvh_refit_link)
+};
+int lbvh_refit_alloc(LbvhRefit& r, int n);  // no-op when r already holds room for exactly n triangles
+void lbvh_refit_free(LbvhRefit& r);
+// After lbvh_build(..., r.order, ...) wrote `nodes`: the parent links of its nnodes output nodes.
+int lbvh_refit_link(LbvhRefit& r, const float* nodes, int nnodes, hipStream_t s);
+// Recomputes every AA / BB of `nodes` in place for the moved triangles `tri` (r.n records of layout lay, in the order
+// of the build's input); childs and leafInfo are only read. Leaf boxes fold their triangles in leaf order from the
+// first, interior boxes are gmin / gmax (left, right): tests/lbvh_refit_ref.py. Index errors set *r.err.
+int lbvh_refit_nodes(LbvhRefit& r, float* nodes, const float* tri, TriLayout lay, hipStream_t s);
+// tri_out[p] = tri[r.order[p]] (Triangle_encoded records): the moved triangles in the build's leaf order
+int lbvh_refit_reorder(const LbvhRefit& r, const float* tri, float* tri_out, hipStream_t s);
 
 }  // namespace ptk
 #endif

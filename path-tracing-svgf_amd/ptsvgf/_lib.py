@@ -92,6 +92,7 @@ _PT_SIGS = [
     ("pt_texture2d_wrap", C.c_int, [_vp, C.c_int, C.c_int, _u32p]),
     ("pt_texbuffer_create", C.c_int, [_vp, C.c_size_t, _u32, _u32p]),
     ("pt_bvh_build", C.c_int, [_u32, C.c_int, C.c_int, _u32, _u32, C.POINTER(C.c_int), _fp]),
+    ("pt_bvh_refit", C.c_int, [_u32, _u32, _u32, _fp]),
     ("pt_texarray_create", C.c_int, [C.c_int, C.c_int, C.c_int, _u32p]),
     ("pt_texarray_upload_layer", C.c_int, [_u32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     ("pt_texture_readback", C.c_int, [_u32, _fp, C.c_size_t]),
@@ -105,6 +106,7 @@ _PT_SIGS = [
     ("pt_pass_bind", C.c_int, [_u32, C.c_int]),
     ("pt_raster_pass_bind", C.c_int, [_u32, _fp, C.c_size_t]),
     ("pt_raster_pass_bind_device", C.c_int, [_u32, _vp, C.c_size_t, C.c_int]),
+    ("pt_raster_pass_refit_device", C.c_int, [_u32, _vp, C.c_size_t]),
     ("pt_raster_pass_set_prev_vertices", C.c_int, [_u32, _vp, _vp, C.c_size_t]),
     ("pt_raster_pass_share", C.c_int, [_u32, _u32]),
     ("pt_raster_pass_adopt", C.c_int, [_u32, C.c_int, C.c_int]),
@@ -133,6 +135,8 @@ _PT_SIGS = [
     # include/ptsvgf_debug.h
     ("pt_debug_lbvh_trees", C.c_int, [_u32, C.c_int, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.POINTER(C.c_int)]),
+    # include/ptsvgf_debug_refit.h
+    ("pt_debug_lbvh_order", C.c_int, [_u32, C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_size_t)]),
 ]
 
 _PTS_SIGS = [

@@ -107,6 +107,26 @@ def bvh_build(tri_in: int, tri_out: int, node_out: int, leaf_n: int = 8, ploc_ra
     return n.value, ms.value
 
 
+def bvh_refit(tri_in: int, tri_out: int, node_out: int) -> float:
+    """pt_bvh_refit: the triangles of tri_in (those of the bvh_build that wrote tri_out / node_out, in its input order,
+    at new positions) permuted into tri_out, and node_out's boxes recomputed over the unchanged topology; the walk
+    trees are derived again. Returns the device ms, that derivation included."""
+    ms = C.c_float()
+    check(pt().pt_bvh_refit(tri_in, tri_out, node_out, C.byref(ms)))
+    return ms.value
+
+
+def lbvh_order(node_tex: int) -> np.ndarray:
+    """pt_debug_lbvh_order (include/ptsvgf_debug_refit.h): the leaf order of the bvh_build that wrote node_tex, order[p] =
+    the index in its tri_in of the triangle at position p of its tri_out."""
+    n = C.c_size_t()
+    check(pt().pt_debug_lbvh_order(node_tex, None, 0, C.byref(n)))
+    out = np.zeros(n.value, np.int32)
+    if n.value:
+        check(pt().pt_debug_lbvh_order(node_tex, out.ctypes.data_as(C.POINTER(C.c_int)), n.value, C.byref(n)))
+    return out
+
+
 LBVH_INFO_KEYS = ("root_ref", "need", "nleaves", "root4", "need4", "wide_nodes", "nan", "stage_us")
 
 
@@ -326,6 +346,11 @@ class Rasterize_RenderPass(RenderPass):
     def rebind_vertices_device(self, device_ptr: int, n_floats: int, ploc_radius: int = 16) -> None:
         """pt_raster_pass_bind_device: the vertex list already in device memory, its tree built on the GPU."""
         check(pt().pt_raster_pass_bind_device(self._handle(), C.c_void_p(device_ptr), n_floats, ploc_radius))
+
+    def refit_vertices_device(self, device_ptr: int, n_floats: int) -> None:
+        """pt_raster_pass_refit_device: the same triangles in the same order at new positions (a device vertex list)
+        for a pass rebind_vertices_device bound: records decoded again, the tree's boxes recomputed, topology kept."""
+        check(pt().pt_raster_pass_refit_device(self._handle(), C.c_void_p(device_ptr), n_floats))
 
     def adopt(self, y0: int, y1: int) -> None:
         """pt_raster_pass_adopt: the attachments' rows [y0, y1) were written elsewhere (another rank's draw of the same

@@ -1022,6 +1022,52 @@ class Renderer:
                 p.share_vertices(self.init_pass[0])
         return nodes, ms
 
+    def refit_bvh(self, tri_enc, raster=None, prev_raster=None) -> float:
+        """Dynamic scenes, geometry that moved but kept its triangles and their order (deformation, rigid motion):
+        refit the tree rebuild_bvh built instead of building another (pt_bvh_refit). `tri_enc` holds the scene's
+        Triangle_encoded rows in the order of that rebuild_bvh call's rows, at the new positions; the topology stays
+        and every box is recomputed, so nNodes does not change. `raster` (the vertex list at the new positions, same
+        triangles, same order) refits the G-buffer pass rebuild_bvh(raster=...) bound on the device
+        (pt_raster_pass_refit_device); `prev_raster` arms object motion vectors for exactly the next frame, as in
+        rebuild_bvh (True: the list of the previous rebuild_bvh / refit_bvh call). A refitted tree keeps the
+        topology chosen for the old positions: rebuild once the geometry has moved far (DESIGN.md "Refit").
+        Frames already issued finish first. Returns the device ms of the path tracer's refit, the walk trees'
+        derivation included. Raises PtError (PT_ERR_STATE) when the scene buffers are not rebuild_bvh's."""
+        from ._lib import PtError
+
+        if self._streams is not None:
+            import torch
+
+            self.flush()
+            torch.cuda.synchronize()
+        src = gl.texture_buffer(np.asarray(tri_enc, np.float32))
+        try:
+            ms = gl.bvh_refit(src, self.trianglesTextureBuffer, self.nodesTextureBuffer)
+        except PtError as e:
+            if e.code == -9:  # PT_ERR_STATE
+                raise PtError(e.code, "refit_bvh: the scene buffers were not built by rebuild_bvh (call it once "
+                                      "before the first refit, and again after a change of topology)") from e
+            raise
+        finally:
+            gl.destroy_texture(src)
+        if raster is not None:
+            import torch
+
+            cur = np.ascontiguousarray(raster, np.float32).reshape(-1)
+            if prev_raster is True:
+                prev_raster = self._last_raster
+            self._last_raster = cur
+            v = torch.from_numpy(cur).cuda()
+            torch.cuda.synchronize()
+            self.init_pass[0].refit_vertices_device(v.data_ptr(), v.numel())  # drops displacement records
+            self._motion_records = self._motion_pending = False
+            if prev_raster is not None:
+                pv = torch.from_numpy(np.ascontiguousarray(prev_raster, np.float32).reshape(-1)).cuda()
+                torch.cuda.synchronize()
+                self.init_pass[0].set_prev_vertices(pv.data_ptr(), v.data_ptr(), v.numel())
+                self._motion_records = self._motion_pending = True
+        return ms
+
     def set_lbvh_wide(self, on: bool) -> None:
         """Pass uniform lbvh_wide on every path-tracing slot: whether a scene rebuild_bvh built is walked through
         the 4-wide tree derived with it (the default) or through its binary tree alone. Same image either way."""
