@@ -213,6 +213,35 @@ int pt_raster_pass_refit_device(uint32_t pass, const void* device_vertices, size
  * are complete when the call returns; a bind drops them; passes sharing this pass's triangles read them too.
  * PT_ERR_ARG for a wrong size, a sharing pass, an unbound pass or a non-raster pass. */
 int pt_raster_pass_set_prev_vertices(uint32_t pass, const void* device_prev, const void* device_cur, size_t n_floats);
+
+/* ---- posed objects (dynamic scenes, no GL counterpart) ---------------------- */
+/* Rigid (or any affine) motion of whole objects without vertex data crossing the bus: a pose keeps the rest-pose
+ * triangles and raster vertices on the device and places them by one matrix per object (tests/pose_ref.py restates
+ * it: positions by glm's mat4 * vec4, normals by the normalised cofactor matrix; a record whose objIndex names no
+ * object, and every record of an object whose matrix is the identity, keeps its bits).
+ * pt_pose_create copies the device contents of the texbuffer tri_rest (whole Triangle_encoded records in the order of
+ * the tri_in pt_bvh_build received; the caller may destroy it afterwards), uploads the rest raster list (pos3 + nrm3
+ * per vertex, n_floats a multiple of 18) with one object index per raster triangle (pts_scene_raster_objects), and
+ * allocates the posed triangle list and two posed raster lists, the current one starting as a copy of the rest list.
+ * raster_rest may be NULL with n_floats 0: the pose then serves the path tracer only. Released by pt_pose_destroy
+ * and by pt_shutdown. */
+int pt_pose_create(uint32_t tri_rest, const float* raster_rest, size_t n_floats, const int* raster_obj,
+                   uint32_t* out_pose);
+/* Poses the rest lists by mats16 (n_obj in [1, 4096] glm column-major mat4s, object k's at mats16 + 16 k; absolute:
+ * every call poses the rest pose) and refits tri_out / node_out exactly as pt_bvh_refit would with the posed list as
+ * tri_in (its version, host-mirror and walk-tree rules hold). With raster_pass != 0 the pass is refitted as
+ * pt_raster_pass_refit_device would with the newly posed raster list; motion != 0 then binds displacement records
+ * from the pose's current list to the new one, as pt_raster_pass_set_prev_vertices(pass, current, new, n) would,
+ * motion == 0 leaves the pass without records; the new list becomes the current one. Synchronous on the library
+ * stream, one synchronisation in all; the caller has no draw in flight that reads the buffers or the pass.
+ * out_ms: device time from the first pose kernel to the end of the tree derivations (NULL: skipped).
+ * All checks run before the first launch: on an error the pose, the buffers, their trees and the pass are unchanged.
+ * PT_ERR_INVALID_HANDLE: an unknown pose. PT_ERR_ARG: null mats16, n_obj out of range, a handle used twice, a
+ * non-texbuffer, raster_pass given for a pose without a raster list, a sharing or non-raster pass, a triangle count
+ * that differs from the pose's. PT_ERR_STATE: whatever pt_bvh_refit or pt_raster_pass_refit_device report so. */
+int pt_pose_apply(uint32_t pose, const float* mats16, int n_obj, uint32_t tri_out, uint32_t node_out,
+                  uint32_t raster_pass, int motion, float* out_ms);
+int pt_pose_destroy(uint32_t pose);
 /* A rasterize pass drawing another (bound) rasterize pass's triangles and tree: the reference has one G-buffer pass;
  * a driver with several G-buffer targets (frames in flight) binds one and shares it. Rebinding `pass` ends the share;
  * destroying `src_pass` first makes `pass`'s draws fail with PT_ERR_STATE. */

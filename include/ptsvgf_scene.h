@@ -74,6 +74,12 @@ int pts_scene_root_aabb(const pts_scene* s, float* out6);
  * Any output pointer may be NULL. Sizes: tris*45, nodes*12, raster floats. */
 int pts_scene_encode(const pts_scene* s, float* tri_out, float* node_out, float* raster_out);
 
+/* The object of every raster triangle, in the raster list's (emission) order: the obj_index its add call gave
+ * (pts_scene_add_raw with obj_index < 0: the running index, as in its triangles). The raster list carries no
+ * objIndex of its own and the BVH build's permutation is not kept; posing objects by matrix needs this
+ * (pt_pose_create). n_tris must be counts[5] / 18. */
+int pts_scene_raster_objects(const pts_scene* s, int* out, int64_t n_tris);
+
 /* glm::mat4 getTransformMatrix(rotateCtrl(deg), translateCtrl, scaleCtrl) -> out16 column-major */
 void pts_transform_matrix(const float* rot3_deg, const float* trans3, const float* scale3, float* out16);
 

@@ -27,6 +27,7 @@
 
 #include "../../include/ptsvgf.h"
 #include "../../include/ptsvgf_debug.h"
+#include "../../include/ptsvgf_debug_pose.h"
 #include "../../include/ptsvgf_debug_refit.h"
 #include "../../include/ptsvgf_scene.h"
 #include "glsl_builtins.h"
@@ -349,6 +350,32 @@ void free_hdr_merged(HdrMerged& m) {
   m = HdrMerged{};
 }
 
+// Posed objects (pt_pose_create): the rest-pose lists on the device and what pt_pose_apply writes from them
+struct Pose {
+  int ntris = 0;               // Triangle_encoded records
+  float* tri_rest = nullptr;   // in the order of the build's tri_in
+  float* tri_posed = nullptr;  // staging: the posed list, pt_bvh_refit's tri_in
+  int rtris = 0;               // raster triangles (0: the pose serves the path tracer only)
+  float* r_rest = nullptr;
+  int* r_obj = nullptr;        // one object per raster triangle
+  float* r_list[2] = {nullptr, nullptr};  // posed raster lists; r_list[cur] is what the pass holds
+  int cur = 0;
+  float* mats_dev = nullptr;   // kPoseMaxObjects x kPoseMatFloats
+  float* mats_host = nullptr;  // pinned staging of the same size
+  float4* disp_spare = nullptr;  // displacement records taken off the pass by a pose without motion, for the next
+};
+constexpr int kPoseMaxObjects = 4096;
+
+void free_pose(Pose& p) {
+  float* dev[] = {p.tri_rest, p.tri_posed, p.r_rest, p.r_list[0], p.r_list[1], p.mats_dev};
+  for (float* d : dev)
+    if (d) (void)hipFree(d);
+  if (p.r_obj) (void)hipFree(p.r_obj);
+  if (p.disp_spare) (void)hipFree(p.disp_spare);
+  if (p.mats_host) (void)hipHostFree(p.mats_host);
+  p = Pose{};
+}
+
 struct Lib {
   bool init = false;
   int device = 0;
@@ -357,6 +384,7 @@ struct Lib {
   std::map<uint32_t, int> programs;
   std::map<uint32_t, std::unique_ptr<Texture>> textures;
   std::map<uint32_t, std::unique_ptr<Pass>> passes;
+  std::map<uint32_t, std::unique_ptr<Pose>> poses;
   std::map<std::pair<uint32_t, uint32_t>, SceneGPU> scenes;
   std::map<std::pair<uint32_t, uint32_t>, HdrMerged> hdr_merged;  // keyed by (hdrMap, hdrCache) handles
   std::map<hipStream_t, ptk::WfFork> forks;  // per draw stream: the path tracer's side stream (uniform trace_fork)
@@ -2525,6 +2553,7 @@ int pt_shutdown(void) {
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
   }
+  for (auto& kv : g.poses) free_pose(*kv.second);
   for (auto& kv : g.scenes) free_scene(kv.second);
   for (auto& kv : g.hdr_merged) free_hdr_merged(kv.second);
   g.hdr_merged.clear();
@@ -3374,6 +3403,235 @@ int pt_raster_pass_set_prev_vertices(uint32_t pass, const void* dprev, const voi
     return hip_err(e, "pt_raster_pass_set_prev_vertices");
   }
   p->raster.disp = disp;
+  return PT_OK;
+}
+
+int pt_pose_create(uint32_t tri_rest, const float* raster_rest, size_t n_floats, const int* raster_obj,
+                   uint32_t* out_pose) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  if (!out_pose) return err(PT_ERR_ARG, "pt_pose_create: null out_pose");
+  Texture* t = tex_of(tri_rest);
+  if (!t || t->target != PT_TEXTURE_BUFFER) return err(PT_ERR_ARG, "pt_pose_create: tri_rest must be a texture buffer");
+  if (t->bytes == 0 || t->bytes % (45 * sizeof(float)) || !t->dev)
+    return err(PT_ERR_ARG, "pt_pose_create: tri_rest must hold whole Triangle_encoded records (45 floats)");
+  const size_t nt = t->bytes / (45 * sizeof(float));
+  if (nt > (1u << 24)) return err(PT_ERR_ARG, "pt_pose_create: more than 2^24 triangles");
+  if (n_floats % 18) return err(PT_ERR_ARG, "pt_pose_create: the raster list must be whole triangles of pos3+nrm3");
+  if (n_floats / 18 > (1u << 24)) return err(PT_ERR_ARG, "pt_pose_create: more than 2^24 raster triangles");
+  if (n_floats && (!raster_rest || !raster_obj))
+    return err(PT_ERR_ARG, "pt_pose_create: a raster list needs its vertices and one object per triangle");
+  std::unique_ptr<Pose> ps(new Pose);
+  ps->ntris = (int)nt;
+  ps->rtris = (int)(n_floats / 18);
+  const size_t rbytes = n_floats * sizeof(float), mbytes = (size_t)kPoseMaxObjects * ptk::kPoseMatFloats * sizeof(float);
+  hipError_t e = hipMalloc((void**)&ps->tri_rest, t->bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&ps->tri_posed, t->bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&ps->mats_dev, mbytes);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&ps->mats_host, mbytes, hipHostMallocDefault);
+  if (e == hipSuccess && ps->rtris) {
+    e = hipMalloc((void**)&ps->r_rest, rbytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&ps->r_list[0], rbytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&ps->r_list[1], rbytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&ps->r_obj, (size_t)ps->rtris * sizeof(int));
+  }
+  // on the library stream: tri_rest may have been written there
+  if (e == hipSuccess) e = hipMemcpyAsync(ps->tri_rest, t->dev, t->bytes, hipMemcpyDeviceToDevice, g.stream);
+  if (e == hipSuccess && ps->rtris) {
+    e = hipMemcpyAsync(ps->r_rest, raster_rest, rbytes, hipMemcpyHostToDevice, g.stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(ps->r_obj, raster_obj, (size_t)ps->rtris * sizeof(int), hipMemcpyHostToDevice, g.stream);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k)
+      e = hipMemcpyAsync(ps->r_list[k], ps->r_rest, rbytes, hipMemcpyDeviceToDevice, g.stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+  if (e != hipSuccess) {
+    free_pose(*ps);
+    return hip_err(e, "pt_pose_create");
+  }
+  const uint32_t h = g.next++;
+  g.poses[h] = std::move(ps);
+  *out_pose = h;
+  return PT_OK;
+}
+
+int pt_pose_destroy(uint32_t pose) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  auto it = g.poses.find(pose);
+  if (it == g.poses.end()) return err(PT_ERR_INVALID_HANDLE, "pt_pose_destroy: unknown pose");
+  (void)hipDeviceSynchronize();  // a pt_pose_apply has completed; nothing else reads the lists
+  free_pose(*it->second);
+  g.poses.erase(it);
+  return PT_OK;
+}
+
+int pt_pose_apply(uint32_t pose, const float* mats16, int n_obj, uint32_t tri_out, uint32_t node_out,
+                  uint32_t raster_pass, int motion, float* out_ms) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  auto pit = g.poses.find(pose);
+  if (pit == g.poses.end()) return err(PT_ERR_INVALID_HANDLE, "pt_pose_apply: unknown pose");
+  Pose& ps = *pit->second;
+  if (!mats16) return err(PT_ERR_ARG, "pt_pose_apply: null mats16");
+  if (n_obj < 1 || n_obj > kPoseMaxObjects) return err(PT_ERR_ARG, "pt_pose_apply: n_obj must be in [1, 4096]");
+  // the pair: pt_bvh_refit's checks, the posed list standing for tri_in
+  Texture *to = tex_of(tri_out), *no = tex_of(node_out);
+  if (!to || !no || to->target != PT_TEXTURE_BUFFER || no->target != PT_TEXTURE_BUFFER)
+    return err(PT_ERR_ARG, "pt_pose_apply: tri_out and node_out must be texture buffers");
+  if (tri_out == node_out) return err(PT_ERR_ARG, "pt_pose_apply: tri_out and node_out must be two different buffers");
+  ptk::LbvhRefit* rf = no->refit;
+  if (!to->lbvh || !no->lbvh || !rf || !rf->base || rf->nnodes < 2 || !no->trees || no->refit_tri != tri_out ||
+      no->refit_tri_ver != to->version || no->refit_node_ver != no->version || no->trees->version != no->version ||
+      !to->dev || !no->dev || to->bytes != (size_t)rf->n * 45 * sizeof(float) ||
+      no->bytes != (size_t)rf->nnodes * 12 * sizeof(float))
+    return err(PT_ERR_STATE, "pt_pose_apply: tri_out and node_out are not the untouched pair of one pt_bvh_build");
+  if (rf->n != ps.ntris) return err(PT_ERR_ARG, "pt_pose_apply: the pose holds another triangle count than the build");
+  // the pass: pt_raster_pass_refit_device's checks
+  Pass* p = nullptr;
+  if (raster_pass) {
+    if (!ps.rtris) return err(PT_ERR_ARG, "pt_pose_apply: the pose was created without a raster list");
+    p = pass_of(raster_pass);
+    if (!p) return err(PT_ERR_INVALID_HANDLE, "pt_pose_apply: invalid pass");
+    if (g.programs[p->program] != PK_RASTER) return err(PT_ERR_ARG, "pt_pose_apply: not a rasterize pass");
+    if (p->raster_src) return err(PT_ERR_ARG, "pt_pose_apply: the pass shares another pass's triangles");
+    const RasterScene& rs = p->raster;
+    if (!p->bound || !rs.refit || !rs.refit->base || !rs.enc_nodes || !rs.geom || !rs.nrm || !rs.bvh ||
+        rs.refit->n != rs.ntris || rs.bvh_records < 1)
+      return err(PT_ERR_STATE, "pt_pose_apply: the pass was not bound by pt_raster_pass_bind_device (or took its "
+                               "host fallback): bind again");
+    if (rs.ntris != ps.rtris) return err(PT_ERR_ARG, "pt_pose_apply: the pose holds another raster triangle count");
+  }
+  // displacement records: the pass's own are rewritten where they lie, else the pair a pose without motion set aside
+  float4* disp = nullptr;
+  if (p && motion) {
+    disp = p->raster.disp ? p->raster.disp : ps.disp_spare;
+    if (!disp && hipMalloc((void**)&disp, (size_t)ps.rtris * 3 * sizeof(float4)) != hipSuccess)
+      return err(PT_ERR_HIP, "pt_pose_apply: out of device memory");
+    if (disp == ps.disp_spare) ps.disp_spare = nullptr;
+  }
+  // the table: each matrix with the cofactor columns of its upper 3x3 (cross products of its columns), once per object
+  for (int k = 0; k < n_obj; ++k) {
+    const float* m = mats16 + (size_t)k * 16;
+    float* o = ps.mats_host + (size_t)k * ptk::kPoseMatFloats;
+    memcpy(o, m, 16 * sizeof(float));
+    const glsl::v3 c0 = glsl::mk(m[0], m[1], m[2]), c1 = glsl::mk(m[4], m[5], m[6]), c2 = glsl::mk(m[8], m[9], m[10]);
+    const glsl::v3 a[3] = {glsl::cross(c1, c2), glsl::cross(c2, c0), glsl::cross(c0, c1)};
+    for (int j = 0; j < 3; ++j) {
+      o[16 + 3 * j] = a[j].x;
+      o[17 + 3 * j] = a[j].y;
+      o[18 + 3 * j] = a[j].z;
+    }
+  }
+  hipStream_t s = g.stream;
+  int rc = (int)hipMemcpyAsync(ps.mats_dev, ps.mats_host, (size_t)n_obj * ptk::kPoseMatFloats * sizeof(float),
+                               hipMemcpyHostToDevice, s);
+  if (rc != 0) {
+    if (disp && disp != p->raster.disp) ps.disp_spare = disp;
+    return hip_err((hipError_t)rc, "pt_pose_apply");
+  }
+  if (p) {
+    if (motion) {
+      p->raster.disp = disp;
+    } else if (p->raster.disp) {  // left without records, as a refit leaves it; no draw reads them (see the header)
+      if (ps.disp_spare) (void)hipFree(ps.disp_spare);
+      ps.disp_spare = p->raster.disp;
+      p->raster.disp = nullptr;
+    }
+  }
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (out_ms) {
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, s);
+  }
+  const int nxt = ps.cur ^ 1;
+  rc = ptk::pose_tris_launch(ps.tri_rest, ps.ntris, ps.mats_dev, n_obj, ps.tri_posed, s);
+  if (rc == 0 && ps.rtris)
+    rc = ptk::pose_raster_launch(ps.r_rest, ps.r_obj, ps.rtris, ps.mats_dev, n_obj, ps.r_list[nxt], s);
+  // pt_bvh_refit with the posed list as tri_in
+  if (rc == 0) rc = ptk::lbvh_refit_reorder(*rf, ps.tri_posed, (float*)to->dev, s);
+  if (rc == 0) rc = ptk::lbvh_refit_nodes(*rf, (float*)no->dev, ps.tri_posed, ptk::kTriEncoded, s);
+  std::unique_ptr<ptk::LbvhTrees> trees(new ptk::LbvhTrees);
+  const bool launched = rc == 0;
+  int trc = launched ? ptk::lbvh_trees_launch(g_lbvh, (const float*)no->dev, rf->nnodes, *trees, s, rf->err) : 0;
+  // pt_raster_pass_refit_device with the new list; the packed tree has the bind's size (same topology), so its copy is
+  // issued before the counters are back, and they are checked after the one synchronisation
+  ptk::LbvhTrees rtrees;
+  int rrc = 0;
+  const bool raster_launched = p && launched && trc == 0;
+  if (raster_launched) {
+    RasterScene& rs = p->raster;
+    ptk::LbvhRefit& rrf = *rs.refit;
+    rrc = ptk::decode_raster(ps.r_list[nxt], rrf.order, rs.ntris, rs.geom, rs.nrm, s);
+    if (rrc == 0) rrc = ptk::lbvh_refit_nodes(rrf, rs.enc_nodes, ps.r_list[nxt], ptk::kRasterVerts, s);
+    if (rrc == 0) rrc = ptk::lbvh_trees_launch(g_lbvh, rs.enc_nodes, rrf.nnodes, rtrees, s, rrf.err);
+  }
+  if (out_ms) (void)hipEventRecord(e1, s);
+  if (raster_launched && rrc == 0) {
+    RasterScene& rs = p->raster;
+    rrc = (int)hipMemcpyAsync(rs.bvh, rtrees.bin, (size_t)rs.bvh_records * 4 * sizeof(float4), hipMemcpyDeviceToDevice, s);
+    if (rrc == 0 && motion)
+      rrc = ptk::raster_disp(rs.geom, ps.r_list[ps.cur], ps.r_list[nxt], rs.ntris, rs.disp, s);
+  }
+  rc = rc == 0 ? PT_OK : hip_err((hipError_t)rc, "pt_pose_apply");
+  {  // the one synchronisation; also after a failure: the stages' counters are copied into the trees
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess && rc == PT_OK) rc = hip_err(e, "pt_pose_apply");
+  }
+  if (out_ms) {
+    *out_ms = 0.0f;
+    if (rc == PT_OK) (void)hipEventElapsedTime(out_ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  if (rc == PT_OK && trc == 0) trc = ptk::lbvh_trees_finish(*trees);
+  if (rc == PT_OK && trc != 0) rc = err(PT_ERR_HIP, "pt_pose_apply: deriving the walk trees failed");
+  // as pt_bvh_refit: the contents changed whatever came of it, the old trees go, and every consumer re-reads
+  to->version++;
+  no->version++;
+  to->host_stale = no->host_stale = true;
+  free_trees(no);
+  if (rc == PT_OK) {
+    trees->version = no->version;
+    no->trees = trees.release();
+    no->refit_tri_ver = to->version;
+    no->refit_node_ver = no->version;
+  } else {
+    ptk::lbvh_trees_free(*trees);
+    free_refit(no);
+  }
+  if (ps.rtris && launched) ps.cur = nxt;
+  if (p) {
+    RasterScene& rs = p->raster;
+    if (rc == PT_OK && rrc == 0) rrc = ptk::lbvh_trees_finish(rtrees);
+    if (rc == PT_OK && rrc == 0 &&
+        (rtrees.dev_info[1] != rs.stack_need || std::max(1, rtrees.nbin()) != rs.bvh_records))
+      rrc = (int)hipErrorInvalidValue;  // the topology is the bind's: the same depth and as many records
+    if (rc == PT_OK && rrc == 0) rs.root_ref = rtrees.dev_info[0];
+    ptk::lbvh_trees_free(rtrees);
+    if (rc != PT_OK || rrc != 0) {
+      drop_disp(p);
+      free_raster_refit(rs);  // the records may be half written: the caller binds again
+      if (rc == PT_OK) rc = hip_err((hipError_t)rrc, "pt_pose_apply: refitting the rasterize pass");
+    }
+  }
+  return rc;
+}
+
+int pt_debug_pose_raster(uint32_t pose, int which, float* host_out, size_t cap, size_t* n) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  auto it = g.poses.find(pose);
+  if (it == g.poses.end()) return err(PT_ERR_INVALID_HANDLE, "pt_debug_pose_raster: unknown pose");
+  if (which < 0 || which > 1) return err(PT_ERR_ARG, "pt_debug_pose_raster: which 0 (current) or 1 (previous)");
+  const Pose& ps = *it->second;
+  const size_t floats = (size_t)ps.rtris * 18;
+  if (n) *n = floats;
+  if (!host_out || !floats) return PT_OK;
+  if (cap < floats) return err(PT_ERR_ARG, "pt_debug_pose_raster: host_out is too small");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(host_out, ps.r_list[ps.cur ^ which], floats * sizeof(float), hipMemcpyDeviceToHost));
   return PT_OK;
 }
 

@@ -871,7 +871,104 @@ __global__ void __launch_bounds__(256) refit_reorder(const float* __restrict__ t
   if (o >= 0 && o < n) out[f] = tri[(size_t)o * kTriFloats + q];
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Posed objects (pose_tris, pose_raster): rest-pose records placed by one matrix per object, defined by
+// tests/pose_ref.py. The table holds kPoseMatFloats per object: the glm column-major mat4, then the cofactor columns
+// a0, a1, a2 of its upper 3x3 (computed once per object by the caller). Every float32 operation is spelled as the
+// definition evaluates it (-ffp-contract=off); a record of no object, or of an object whose matrix is the identity,
+// is copied bit for bit. The only index read from memory is the record's object, checked before it is used.
+
+// the object of a record's objIndex among n_obj, or -1 (a NaN compares false throughout)
+__device__ __forceinline__ int pose_object(float f, int n_obj) {
+  return (f >= 0.0f && f < (float)n_obj && f == floorf(f)) ? (int)f : -1;
+}
+
+// all 16 floats compare == to the identity's (pts_transform_matrix's I)
+__device__ __forceinline__ bool pose_identity(const float* __restrict__ m) {
+  bool id = true;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) id = id && m[j] == (j % 5 == 0 ? 1.0f : 0.0f);
+  return id;
+}
+
+// glm mat4 * vec4(p, 1) (scene_prep.cpp xform_point): (m0 x + m1 y) + (m2 z + m3 1)
+__device__ __forceinline__ glsl::v3 pose_point(const float* __restrict__ m, glsl::v3 p) {
+  float r[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float mul0 = m[0 + k] * p.x, mul1 = m[4 + k] * p.y, mul2 = m[8 + k] * p.z, mul3 = m[12 + k] * 1.0f;
+    const float add0 = mul0 + mul1, add1 = mul2 + mul3;
+    r[k] = add0 + add1;
+  }
+  return glsl::mk(r[0], r[1], r[2]);
+}
+
+// normalize(cofactor matrix * n): the inverse transpose up to a scale of either sign; a = the 9 cofactor floats
+__device__ __forceinline__ glsl::v3 pose_normal(const float* __restrict__ a, glsl::v3 n) {
+  float v[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) v[k] = (a[0 + k] * n.x + a[3 + k] * n.y) + a[6 + k] * n.z;
+  return glsl::normalize(glsl::mk(v[0], v[1], v[2]));
+}
+
+// One thread per 12-byte texel of a Triangle_encoded record (15 per record), so a wave loads and stores 768
+// contiguous bytes: texels 0-2 are p1-p3, 3-5 n1-n3, the rest is copied; the object comes from texel 14 of the record.
+__global__ void __launch_bounds__(256) pose_tris(const float* __restrict__ rest, int n, const float* __restrict__ mats,
+                                                  int n_obj, float* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)n * 15) return;
+  const size_t rec = t / 15;
+  const int tex = (int)(t - rec * 15);
+  glsl::v3 v = glsl::mk(rest[3 * t], rest[3 * t + 1], rest[3 * t + 2]);
+  if (tex < 6) {
+    const int k = pose_object(rest[rec * kTriFloats + 42], n_obj);
+    if (k >= 0) {
+      const float* m = mats + (size_t)k * kPoseMatFloats;
+      if (!pose_identity(m)) v = tex < 3 ? pose_point(m, v) : pose_normal(m + 16, v);
+    }
+  }
+  out[3 * t] = v.x;
+  out[3 * t + 1] = v.y;
+  out[3 * t + 2] = v.z;
+}
+
+// One thread per vertex of the raster list (pos3 + nrm3, 24 bytes); obj holds one int per triangle.
+__global__ void __launch_bounds__(256) pose_raster(const float* __restrict__ rest, const int* __restrict__ obj,
+                                                    int ntris, const float* __restrict__ mats, int n_obj,
+                                                    float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)ntris * 3) return;
+  const float* f = rest + 6 * i;
+  glsl::v3 p = glsl::mk(f[0], f[1], f[2]), nv = glsl::mk(f[3], f[4], f[5]);
+  const int k = obj[i / 3];
+  if (k >= 0 && k < n_obj) {
+    const float* m = mats + (size_t)k * kPoseMatFloats;
+    if (!pose_identity(m)) {
+      p = pose_point(m, p);
+      nv = pose_normal(m + 16, nv);
+    }
+  }
+  float* o = out + 6 * i;
+  o[0] = p.x; o[1] = p.y; o[2] = p.z;
+  o[3] = nv.x; o[4] = nv.y; o[5] = nv.z;
+}
+
 }  // namespace
+
+int pose_tris_launch(const float* rest, int n, const float* mats, int n_obj, float* out, hipStream_t s) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(pose_tris, dim3((unsigned)(((size_t)n * 15 + 255) / 256)), dim3(256), 0, s, rest, n, mats, n_obj,
+                     out);
+  return (int)hipGetLastError();
+}
+
+int pose_raster_launch(const float* rest, const int* obj, int ntris, const float* mats, int n_obj, float* out,
+                       hipStream_t s) {
+  if (ntris <= 0) return 0;
+  hipLaunchKernelGGL(pose_raster, dim3((unsigned)(((size_t)ntris * 3 + 255) / 256)), dim3(256), 0, s, rest, obj, ntris,
+                     mats, n_obj, out);
+  return (int)hipGetLastError();
+}
 
 int decode_raster(const float* verts, const int* order, int n, float4* geom, float4* nrm, hipStream_t s) {
   if (n <= 0) return 0;

@@ -611,5 +611,16 @@ int lbvh_refit_nodes(LbvhRefit& r, float* nodes, const float* tri, TriLayout lay
 // tri_out[p] = tri[r.order[p]] (Triangle_encoded records): the moved triangles in the build's leaf order
 int lbvh_refit_reorder(const LbvhRefit& r, const float* tri, float* tri_out, hipStream_t s);
 
+// Posed objects (DESIGN.md "Posed objects", tests/pose_ref.py): out = the rest-pose records placed by their object's
+// matrix. mats holds kPoseMatFloats per object: the glm column-major mat4, then the cofactor columns a0, a1, a2 of
+// its upper 3x3. Records of no object (objIndex outside [0, n_obj) or no integer) and of identity matrices are
+// copied bit for bit.
+constexpr int kPoseMatFloats = 25;
+// n Triangle_encoded records (objIndex: float 42): positions and normals posed, every other float copied
+int pose_tris_launch(const float* rest, int n, const float* mats, int n_obj, float* out, hipStream_t s);
+// ntris raster triangles (3 vertices of pos3 + nrm3 each); obj: one int per triangle
+int pose_raster_launch(const float* rest, const int* obj, int ntris, const float* mats, int n_obj, float* out,
+                       hipStream_t s);
+
 }  // namespace ptk
 #endif

@@ -74,6 +74,7 @@ inline v3 gnormalize(v3 a) { return glsl::normalize(a); }
 struct pts_scene {
   std::vector<Tri> tris;
   std::vector<float> raster;
+  std::vector<int> raster_obj;  // per raster triangle, in emission order: the objIndex it was added with
   std::vector<Node> nodes;
   bool built = false;
 };
@@ -117,6 +118,7 @@ static void emit_triangles(pts_scene* s, const std::vector<v3>& vertices, const 
       t.n3 = gnormalize(normals[indices[i + 2]]);
     }
     memcpy(t.mat, material, sizeof(t.mat));
+    s->raster_obj.push_back(objIndex);
     const v3* pv[3] = {&t.p1, &t.p2, &t.p3};
     const v3* nv[3] = {&t.n1, &t.n2, &t.n3};
     for (int k = 0; k < 3; ++k) {
@@ -383,6 +385,7 @@ int pts_scene_add_raw(pts_scene* s, const float* v, int n_tris, const float* mat
     memcpy(t.mat, material18, sizeof(t.mat));
     t.objID = obj_index < 0 ? i : obj_index;
     s->raster.insert(s->raster.end(), q, q + 18);
+    s->raster_obj.push_back(t.objID);
   }
   s->built = false;
   return 0;
@@ -460,6 +463,13 @@ int pts_scene_encode(const pts_scene* s, float* tri_out, float* node_out, float*
     }
   }
   if (raster_out) memcpy(raster_out, s->raster.data(), s->raster.size() * sizeof(float));
+  return 0;
+}
+
+int pts_scene_raster_objects(const pts_scene* s, int* out, int64_t n_tris) {
+  if (!s || !out) return fail("pts_scene_raster_objects: null argument");
+  if (n_tris != (int64_t)s->raster_obj.size()) return fail("pts_scene_raster_objects: not the raster triangle count");
+  if (n_tris) memcpy(out, s->raster_obj.data(), s->raster_obj.size() * sizeof(int));
   return 0;
 }
 

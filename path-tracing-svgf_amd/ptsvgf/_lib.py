@@ -108,6 +108,9 @@ _PT_SIGS = [
     ("pt_raster_pass_bind_device", C.c_int, [_u32, _vp, C.c_size_t, C.c_int]),
     ("pt_raster_pass_refit_device", C.c_int, [_u32, _vp, C.c_size_t]),
     ("pt_raster_pass_set_prev_vertices", C.c_int, [_u32, _vp, _vp, C.c_size_t]),
+    ("pt_pose_create", C.c_int, [_u32, _fp, C.c_size_t, C.POINTER(C.c_int), _u32p]),
+    ("pt_pose_apply", C.c_int, [_u32, _fp, C.c_int, _u32, _u32, _u32, C.c_int, _fp]),
+    ("pt_pose_destroy", C.c_int, [_u32]),
     ("pt_raster_pass_share", C.c_int, [_u32, _u32]),
     ("pt_raster_pass_adopt", C.c_int, [_u32, C.c_int, C.c_int]),
     ("pt_tiles_count", C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int64)]),
@@ -137,6 +140,8 @@ _PT_SIGS = [
                                       C.POINTER(C.c_int)]),
     # include/ptsvgf_debug_refit.h
     ("pt_debug_lbvh_order", C.c_int, [_u32, C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_size_t)]),
+    # include/ptsvgf_debug_pose.h
+    ("pt_debug_pose_raster", C.c_int, [_u32, C.c_int, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
 ]
 
 _PTS_SIGS = [
@@ -149,6 +154,7 @@ _PTS_SIGS = [
     ("pts_scene_counts", C.c_int, [_vp, C.POINTER(C.c_int64)]),
     ("pts_scene_root_aabb", C.c_int, [_vp, _fp]),
     ("pts_scene_encode", C.c_int, [_vp, _fp, _fp, _fp]),
+    ("pts_scene_raster_objects", C.c_int, [_vp, C.POINTER(C.c_int), C.c_int64]),
     ("pts_transform_matrix", None, [_fp, _fp, _fp, _fp]),
     ("pts_hdr_cache", C.c_int, [_fp, C.c_int, C.c_int, _fp]),
     ("pts_gen_plant", C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.POINTER(C.c_int)]),

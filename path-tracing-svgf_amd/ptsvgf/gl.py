@@ -127,6 +127,48 @@ def lbvh_order(node_tex: int) -> np.ndarray:
     return out
 
 
+def pose_create(tri_rest: int, raster_rest=None, raster_obj=None) -> int:
+    """pt_pose_create: a pose over the device triangles of the texbuffer tri_rest (the rows a bvh_build received, in
+    its input order; it may be destroyed afterwards) and, optionally, the rest raster vertex list with one object
+    index per raster triangle. Returns the pose handle."""
+    h = C.c_uint32()
+    if raster_rest is None:
+        check(pt().pt_pose_create(tri_rest, None, 0, None, C.byref(h)))
+        return h.value
+    v = np.ascontiguousarray(raster_rest, np.float32).reshape(-1)
+    o = np.ascontiguousarray(raster_obj, np.int32).reshape(-1)
+    if o.size * 18 != v.size:
+        raise ValueError(f"pose_create: {o.size} raster objects for {v.size / 18:g} raster triangles")
+    check(pt().pt_pose_create(tri_rest, fptr(v), v.size, o.ctypes.data_as(C.POINTER(C.c_int)), C.byref(h)))
+    return h.value
+
+
+def pose_apply(pose: int, mats, tri_out: int, node_out: int, raster_pass: int = 0, motion: bool = True) -> float:
+    """pt_pose_apply: the rest lists of `pose` placed by mats ((n_obj, 16), glm column-major, absolute), tri_out /
+    node_out refitted as bvh_refit would with the posed triangles, the rasterize pass (handle, 0: none) refitted with
+    the posed raster list and, with motion, given displacement records from the previous pose. Returns device ms."""
+    m = np.ascontiguousarray(mats, np.float32).reshape(-1, 16)
+    ms = C.c_float()
+    check(pt().pt_pose_apply(pose, fptr(m), m.shape[0], tri_out, node_out, raster_pass, 1 if motion else 0,
+                             C.byref(ms)))
+    return ms.value
+
+
+def pose_destroy(pose: int) -> None:
+    check(pt().pt_pose_destroy(pose))
+
+
+def pose_raster(pose: int, which: int = 0) -> np.ndarray:
+    """pt_debug_pose_raster (include/ptsvgf_debug_pose.h): the pose's current (which = 0) or previous (1) posed
+    raster vertex list as flat float32."""
+    n = C.c_size_t()
+    check(pt().pt_debug_pose_raster(pose, which, None, 0, C.byref(n)))
+    out = np.zeros(n.value, np.float32)
+    if n.value:
+        check(pt().pt_debug_pose_raster(pose, which, fptr(out), out.size, C.byref(n)))
+    return out
+
+
 LBVH_INFO_KEYS = ("root_ref", "need", "nleaves", "root4", "need4", "wide_nodes", "nan", "stage_us")
 
 

@@ -282,8 +282,10 @@ class Renderer:
         self.gbuf = []
         # object motion (rebuild_bvh(prev_raster=...)): records bound on init_pass[0]; the next frame draws with them
         self.object_motion = True
+        self._pose = None       # pose_objects: the pt_pose handle, and the rest pose the last rebuild_bvh received
+        self._pose_rest = None
         self._motion_records = self._motion_pending = False
-        self._last_raster = np.ascontiguousarray(scene.raster, np.float32).reshape(-1)
+        self._last_raster =np.ascontiguousarray(scene.raster, np.float32).reshape(-1)
         raster_prog = _prog("rasterize_frag.frag", "rasterize_vert.vert")
         for b in range(nbuf):
             g = dict(world=tex(W, H), normal_depth=tex(W, H), velocity=tex(W, H), fwidth=tex(W, H))
@@ -974,7 +976,8 @@ class Renderer:
             self._slot_free[f % self.K] = ev
 
     # --------------------------------------------------------- accessors ---
-    def rebuild_bvh(self, tri_enc=None, raster=None, leaf_n: int = 3, ploc_radius: int = 32, prev_raster=None):
+    def rebuild_bvh(self, tri_enc=None, raster=None, leaf_n: int = 3, ploc_radius: int = 32, prev_raster=None,
+                    raster_obj=None):
         """Dynamic scenes: rebuild the path tracer's BVH on the GPU (pt_bvh_build) into the scene
         buffers the passes are bound to. `tri_enc` (Triangle_encoded rows, any order; default: the scene's
         triangles) carries moved vertices; `raster` (the pre-BVH vertex list, obj_loader.h:143-160) moves the
@@ -987,17 +990,23 @@ class Renderer:
         the first frame issued after the rebuild draws its G-buffer with object_motion = 1, so SVGF and TAA fetch a
         moved object's history from where it was; later frames draw with 0 (the geometry is stationary again, the
         planes those of a plain bind). `self.object_motion = False` keeps every frame at 0.
+        What this call receives is also the rest pose of pose_objects: `tri_enc`, `raster` and `raster_obj` (one
+        object index per raster triangle; default: the scene's raster_obj); a pose of an earlier call is released.
         Frames already issued finish first. Returns (nodes, device ms, that derivation included)."""
         if self._streams is not None:
             import torch
 
             self.flush()
             torch.cuda.synchronize()
-        src = gl.texture_buffer(self.scene.tri_enc if tri_enc is None else np.asarray(tri_enc, np.float32))
+        self._drop_pose()  # the order changes
+        rest = np.asarray(self.scene.tri_enc if tri_enc is None else tri_enc, np.float32)
+        src = gl.texture_buffer(rest)
         try:
             nodes, ms = gl.bvh_build(src, self.trianglesTextureBuffer, self.nodesTextureBuffer, leaf_n, ploc_radius)
         finally:
             gl.destroy_texture(src)
+        self._pose_rest = (rest, None if raster is None else np.ascontiguousarray(raster, np.float32).reshape(-1),
+                           self.scene.raster_obj if raster_obj is None else raster_obj)
         for p, _ in self.pt_slots:
             p.set_uniform_int("nNodes", nodes)
         if raster is not None:
@@ -1040,6 +1049,7 @@ class Renderer:
 
             self.flush()
             torch.cuda.synchronize()
+        self._drop_pose()  # its current list would no longer be the pass's: pose_objects needs a rebuild_bvh first
         src = gl.texture_buffer(np.asarray(tri_enc, np.float32))
         try:
             ms = gl.bvh_refit(src, self.trianglesTextureBuffer, self.nodesTextureBuffer)
@@ -1068,6 +1078,74 @@ class Renderer:
                 self._motion_records = self._motion_pending = True
         return ms
 
+    _NOT_REBUILT = ("the scene buffers were not built by rebuild_bvh (call it once before the first refit, and again "
+                    "after a change of topology)")
+
+    def _drop_pose(self) -> None:
+        """Release the pose and forget its rest pose (rebuild_bvh sets a new one)."""
+        if getattr(self, "_pose", None):
+            gl.pose_destroy(self._pose)
+        self._pose = None
+        self._pose_rest = None
+
+    def pose_objects(self, mats, motion: bool = True) -> float:
+        """Dynamic scenes, rigid (or any affine) motion of whole objects: place every object by one matrix, on the
+        device (pt_pose_apply). `mats` is {obj_index: 4x4 or 16 floats} or an (n_obj, 16) array, the floats glm
+        column-major as scene.transform returns them; objects not named keep the identity. Matrices are absolute:
+        each call poses the rest pose, which is what the last rebuild_bvh call received (its tri_enc, its raster, its
+        raster_obj), so posing with identities restores it bit for bit. Positions are transformed by glm's
+        mat4 * vec4, normals by the normalised cofactor matrix (tests/pose_ref.py; DESIGN.md "Posed objects").
+        The path tracer's tree is refitted as refit_bvh would with the posed rows; if rebuild_bvh was given a `raster`,
+        the G-buffer pass is refitted with the posed vertex list, and with `motion` (and self.object_motion) the next
+        frame gets object motion vectors from the previous pose to this one, as refit_bvh(prev_raster=True) arms them.
+        No vertex data crosses the bus and the call synchronises once. The first call after a rebuild_bvh creates the
+        pose (one upload of the rest lists); rebuild_bvh, refit_bvh and close() release it. Mixing with refit_bvh
+        needs a rebuild_bvh in between: after a refit_bvh this raises until rebuild_bvh has run again.
+        Like a refitted tree, a posed one keeps the topology chosen for the rest pose; there is no rebuild policy
+        for poses far from it (compare `frame alone` against a fresh rebuild_bvh, DESIGN.md "Refit").
+        Frames already issued finish first. Returns the device ms of the pose: both pose kernels, both refits and
+        the walk trees' derivation. Raises PtError (PT_ERR_STATE) when rebuild_bvh has not run."""
+        from ._lib import PtError
+
+        if getattr(self, "_pose_rest", None) is None:
+            raise PtError(-9, "refit_bvh: " + self._NOT_REBUILT)
+        rest, raster, raster_obj = self._pose_rest
+        if isinstance(mats, dict):
+            n_obj = max([int(k) for k in mats] + [0]) + 1
+            if raster_obj is not None and len(raster_obj):
+                n_obj = max(n_obj, int(np.max(raster_obj)) + 1)
+            table = np.tile(np.eye(4, dtype=np.float32).reshape(1, 16), (n_obj, 1))
+            for k, m in mats.items():
+                if int(k) < 0:
+                    raise ValueError("pose_objects: negative object index")
+                table[int(k)] = np.asarray(m, np.float32).reshape(16)
+        else:
+            table = np.ascontiguousarray(mats, np.float32).reshape(-1, 16)
+        if self._streams is not None:
+            import torch
+
+            self.flush()
+            torch.cuda.synchronize()
+        if raster is not None and raster_obj is None:
+            raise ValueError("pose_objects: no raster_obj (Scene.raster_obj or rebuild_bvh(raster_obj=...))")
+        if self._pose is None:
+            src = gl.texture_buffer(rest)
+            try:
+                self._pose = gl.pose_create(src, raster, raster_obj)
+            finally:
+                gl.destroy_texture(src)
+        raster_pass = 0 if raster is None else self.init_pass[0]._handle()
+        arm = bool(motion) and raster is not None
+        try:
+            ms = gl.pose_apply(self._pose, table, self.trianglesTextureBuffer, self.nodesTextureBuffer, raster_pass, arm)
+        except PtError as e:
+            if e.code == -9:  # PT_ERR_STATE
+                raise PtError(e.code, "refit_bvh: " + self._NOT_REBUILT) from e
+            raise
+        if raster is not None:
+            self._motion_records = self._motion_pending = arm
+        return ms
+
     def set_lbvh_wide(self, on: bool) -> None:
         """Pass uniform lbvh_wide on every path-tracing slot: whether a scene rebuild_bvh built is walked through
         the 4-wide tree derived with it (the default) or through its binary tree alone. Same image either way."""
@@ -1093,6 +1171,7 @@ class Renderer:
                     q = q[0]  # pt_slots entries: (pass, outputs)
                 if isinstance(q, RenderPass):
                     q.destroy()
+        self._drop_pose()
         for t in self._owned:
             gl.destroy_texture(t)
         self._owned = []

@@ -57,6 +57,7 @@ class Scene:
     cache: np.ndarray          # (h, w, 3)
     counts: dict = field(default_factory=dict)
     textures: np.ndarray | None = None  # material_array (layers, h, w, 4) uint8, or None (no texture path)
+    raster_obj: np.ndarray | None = None  # (N,) int32: the object of each raster triangle (Renderer.pose_objects)
 
     @property
     def ntris(self) -> int:
@@ -110,6 +111,12 @@ class SceneBuilder:
         raster = np.zeros(c["raster_floats"], np.float32)
         check_host(pts().pts_scene_encode(self._s, fptr(tri), fptr(node), fptr(raster)))
         return tri, node, raster
+
+    def raster_objects(self) -> np.ndarray:
+        """pts_scene_raster_objects: per triangle of the raster vertex list, the obj_index it was added with."""
+        out = np.zeros(self.counts()["raster_floats"] // 18, np.int32)
+        check_host(pts().pts_scene_raster_objects(self._s, out.ctypes.data_as(C.POINTER(C.c_int)), out.size))
+        return out
 
 
 def _gen(fn, *args):
@@ -225,4 +232,4 @@ def build_scene(name: str = "table_clock_plant", hdr_size=(2048, 1024), plant_le
     tri, node, raster = b.encode()
     hdr = env_map(*hdr_size)
     tex = material_layers() if name == "textured" else None
-    return Scene(name, tri, node, raster, POINT_LIGHTS.copy(), hdr, hdr_cache(hdr), b.counts(), tex)
+    return Scene(name, tri, node, raster, POINT_LIGHTS.copy(), hdr, hdr_cache(hdr), b.counts(), tex, b.raster_objects())
