@@ -298,7 +298,10 @@ int pt_pass_set_motion_bound(uint32_t pass, void* device_u32);
  * device_u64 holds `count` counters: counters past count are not written
  * (pt_trace_stats_count() = how many this library has; count above it is
  * capped, count <= 0 with a buffer is PT_ERR_ARG).
- * Wave-aggregated atomics; NULL disables (the default). */
+ * Wave-aggregated atomics; NULL disables (the default).
+ * A draw with the int uniform "spp" = N > 1 (below) traces the primary rays
+ * once: the primary counters (rays, visits, slots, retries) count one sample,
+ * the bounce and shadow counters the rays of all N samples. */
 int pt_pass_set_trace_stats_n(uint32_t pass, void* device_u64, int count);
 /* The first form of the call: a buffer of PT_TRACE_STATS_V1 (12) counters,
  * the first 12 above; the two shadow-split counters are not written. */
@@ -331,7 +334,22 @@ int pt_pass_draw(uint32_t pass);
  * those of drawing each pass alone. passes[0] owns the shared wavefront state,
  * sized for max(count, its "trace_batch" uniform) frames; the batch is timed as
  * its draw. Accumulation (lastFrame) is refused; tile subsets are batched when every pass traces the same one
- * ("tile_stride" / "tile_offset"). */
+ * ("tile_stride" / "tile_offset").
+ *
+ * Samples per pixel: the int uniform "spp" = N of a path-tracing pass (default 1,
+ * 1 .. 8) makes pt_pass_draw take N samples per pixel. Sample s is the
+ * reference's main() with frameCounter replaced by F * N + s (uint32, wrapping;
+ * F the pass's "frameCounter") and accumulation off; the colour attachment
+ * receives (c_0 + c_1 + ... + c_{N-1}) / float(N) summed in that order in
+ * float32, alpha 1, then (uniform "accumulate") mixed with lastFrame at
+ * 1 / float(F + 1u); emission and albedo are those of one sample (the primary
+ * ray does not depend on it, so the primary hit is traced once). N = 1 is the
+ * plain draw, launch for launch. The samples run as the frames of a batch do
+ * (one traversal launch per bounce takes every sample's rays); the pass's
+ * wavefront state is sized for max(N, "trace_batch") frames plus N colour
+ * planes of its band. PT_ERR_ARG, before anything is launched and with every
+ * plane untouched: N outside 1 .. 8, N > 1 with "pt_kernel" != 0, and a pass
+ * with N > 1 inside pt_pass_draw_batch. */
 int pt_pass_draw_batch(const uint32_t* passes, int count);
 /* Time the last draw of this pass (ms, HIP events on the library stream; syncs). */
 int pt_pass_last_ms(uint32_t pass, float* ms);

@@ -32,6 +32,7 @@
 #include "../../include/ptsvgf_scene.h"
 #include "glsl_builtins.h"
 #include "pt_device.h"
+#include "spp_params.h"
 
 namespace {
 
@@ -141,6 +142,8 @@ struct WFBuffers {
   int nb = 1;            // frames (pt_pass_draw_batch): per-pixel arrays for nb * n pixels, lists and counters per frame
   WFState stb[kMaxBatch]{};  // frame b's state: per-pixel arrays at pid offset b * n; stb[0] == st
   WFState st{};
+  float4* spp = nullptr;  // the sample planes of an spp draw: nsp planes of n texels (SppResolve::samples)
+  int nsp = 0;
   int* spill = nullptr;  // deep reference trees: stack entries past the LDS stack (WFState::spill)
   int spill_levels = 0;
   size_t spill_cols = 0;
@@ -174,9 +177,10 @@ int wf_spill(WFBuffers& b, int need) {
   return PT_OK;
 }
 
-int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1) {
+// nsp: sample planes of an spp draw (0: none; such a draw has nb >= nsp frames of state, one per sample)
+int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1, int nsp = 0) {
   const size_t n = (size_t)W * (size_t)rows;
-  if (b.base && b.n == n && b.nb == nb) return PT_OK;
+  if (b.base && b.n == n && b.nb == nb && b.nsp == nsp) return PT_OK;
   if (b.base) { (void)hipFree(b.base); b.base = nullptr; }
   const size_t m = n * (size_t)nb;  // pixels of the batch
   const size_t f4 = m * 16, al = 256;
@@ -184,7 +188,7 @@ int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1) {
   auto up = [&](size_t v) { return (v + al - 1) / al * al; };
   const size_t lists = up(nl * 4 * kLiveBins) * 2 + up(nl * 4 * (1 + kPointBins));
   size_t total = up(f4) * 10 + up(m * 8) + up(m * 4) + up(m) * 2 + lists * nb + up(m * 8) + up(m * 4) +
-                 up((size_t)nb * kWfCounters * 4);
+                 up((size_t)nb * kWfCounters * 4) + (nsp ? up((size_t)nsp * n * 16) : 0);
   if (hipMalloc(&b.base, total) != hipSuccess) { b.base = nullptr; return PT_ERR_HIP; }
   char* c = (char*)b.base;
   WFState s0{};
@@ -223,9 +227,11 @@ int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1) {
     st.shadow_list = (int*)c; c += up(nl * 4 * (1 + kPointBins));
     b.stb[f] = st;
   }
+  b.spp = nsp ? (float4*)c : nullptr;
   b.st = b.stb[0];
   b.n = n;
   b.nb = nb;
+  b.nsp = nsp;
   return PT_OK;
 }
 
@@ -1700,16 +1706,6 @@ void rows_of(Pass* p, int* y0, int* y1) {
 }
 
 // sobol (path_tracing.frag:480-495): a per-frame uniform value
-float sobol_host(uint32_t d, uint32_t i) {
-  static const uint32_t V[8 * 32] = {
-#include "sobol_v.inc"
-  };
-  uint32_t r = 0u;
-  for (uint32_t j = 0u; i > 0u; i >>= 1u, j++)
-    if ((i & 1u) == 1u) r ^= V[j + d * 32u];
-  return (float)r * (1.0f / (float)0xFFFFFFFFu);
-}
-
 int copy_plane(Texture* dst, Texture* src, Pass* p, int y0, int y1) {
   if (!src || !dst || !src->dev || !dst->dev) return err(PT_ERR_MISSING_TEXTURE, "copy: unbound texture");
   if (src->W != dst->W || src->H != dst->H) return err(PT_ERR_ARG, "copy: size mismatch");
@@ -2008,7 +2004,7 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg) {
   k.hdrResolution = ui(p, "hdrResolution", hm->W);
   k.pointLightSize = ui(p, "pointLightSize", 0);
   TRY(point_bins_for(p, sg, lt, lh, k));
-  k.frameCounter = uu(p, "frameCounter", 0);
+  pt_counter_params(k, uu(p, "frameCounter", 0));  // and the bounces' Sobol points (spp_params.h)
   const Uniform* cr = U(p, "cameraRotate", 6);
   if (cr) memcpy(k.camRot, cr->f, 64);
   else { k.camRot[0] = k.camRot[5] = k.camRot[10] = k.camRot[15] = 1.0f; }
@@ -2020,12 +2016,6 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg) {
   k.prune = ui(p, "prune", 1);
   // A/B switch: 1 = wavefront closest-hit rays walk bvh_any (ties re-walked on the reference tree)
   k.closest_tree = (k.prune && k.scene.bvh_any) ? ui(p, "closest_tree", 1) : 0;
-  for (int b = 0; b < 4; ++b) {
-    uint32_t i = k.frameCounter + 1u;
-    uint32_t gc = i ^ (i >> 1);
-    k.sobol_u[b] = sobol_host(2u * b, gc);
-    k.sobol_v[b] = sobol_host(2u * b + 1u, gc);
-  }
   if (k.accumulate) {
     Texture* lf = sampler(p, "lastFrame");
     if (lf) TRY(plane_of(lf, p, &k.last, "lastFrame"));
@@ -2140,11 +2130,60 @@ int note_hdr_read(Pass* p) {
   return PT_OK;
 }
 
+// Samples per pixel of a path-tracing pass's draw (int uniform spp, default 1): 1 .. kMaxBatch, checked before
+// anything is launched or bound for the draw.
+int pass_spp(Pass* p, int* spp) {
+  *spp = ui(p, "spp", 1);
+  if (*spp >= 1 && *spp <= kMaxBatch) return PT_OK;
+  p->hdr_reads = nullptr;
+  p->pbins_reads = nullptr;
+  return err(PT_ERR_ARG, "spp must lie in 1 .. 8 (samples per pixel per draw)");
+}
+
+// An spp draw (spp = n > 1): the n samples as the frames of a batch over one primary hit (launch_wavefront).
+int draw_pathtrace_spp(Pass* p, PTParams& k, SceneGPU* sg, int n) {
+  const int rows = std::max(0, k.y1 - k.y0);
+  // state for every sample; a pass that also heads frame batches keeps one size for both uses
+  const int nb = std::max(n, std::min(kMaxBatch, ui(p, "trace_batch", 1)));
+  TRY(wf_alloc(p->wf, k.W, rows, nb, n));
+  if (wf_spill(p->wf, k.stack_need) != PT_OK) return err(PT_ERR_HIP, "spill stack allocation failed");
+  TRY(pt_wf_setup(p, k, sg, p->wf.stb[0]));
+  PTParams ks[kMaxBatch];
+  for (int s = 0; s < n; ++s) spp_sample_params(k, n, s, p->wf.stb[s], p->wf.spp, &ks[s]);
+  ptk::SppResolve rs{};
+  rs.n = n;
+  rs.samples = p->wf.spp;
+  rs.stride = p->wf.n;
+  rs.color = k.color;
+  rs.last = k.last;
+  rs.accumulate = k.accumulate;
+  rs.frameCounter = k.frameCounter;
+  rs.W = k.W;
+  rs.y0 = k.y0;
+  rs.y1 = k.y1;
+  rs.tile_stride = k.tile_stride;
+  rs.tile_offset = k.tile_offset;
+  int rc;
+  const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
+  if (rc) return rc;
+  rc = launch_pathtrace_wavefront_spp(ks, rs, g.stream, fk);
+  if (!rc && k.tiles.cost) p->order.ordered = true;
+  return rc ? hip_err((hipError_t)rc, "pathtrace spp launch") : PT_OK;
+}
+
 int draw_pathtrace(Pass* p) {
+  int spp;
+  TRY(pass_spp(p, &spp));
+  if (spp > 1 && ui(p, "pt_kernel", 0) != 0)
+    return err(PT_ERR_ARG, "spp > 1 needs the wavefront path tracer (pt_kernel = 0)");
   PTParams k;
   SceneGPU* sg = nullptr;
   TRY(pt_params(p, k, sg));
   int rc;
+  if (spp > 1) {
+    TRY(draw_pathtrace_spp(p, k, sg, spp));
+    return note_hdr_read(p);
+  }
   if (ui(p, "pt_kernel", 0) == 1) {  // 1: single megakernel (kernels_pt.hip), kept for A/B
     if (k.tile_stride != 1) return err(PT_ERR_ARG, "tile subsets need the wavefront path tracer");
     if (k.stack_need >= kStack)
@@ -2170,6 +2209,11 @@ int draw_pathtrace_batch(Pass** ps, int n) {
   Pass* h = ps[0];
   PTParams k[kMaxBatch];
   SceneGPU* sg = nullptr;
+  for (int b = 0; b < n; ++b) {  // before the first pass's parameters launch or bind anything
+    int spp;
+    TRY(pass_spp(ps[b], &spp));
+    if (spp > 1) return err(PT_ERR_ARG, "a pass with spp > 1 cannot be part of a batch: its samples are its batch");
+  }
   for (int b = 0; b < n; ++b) {
     SceneGPU* sb = nullptr;
     TRY(pt_params(ps[b], k[b], sb));

@@ -1730,14 +1730,16 @@ __global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bo
       }
       if (hr.x < 0) {  // miss (:1084-1087)
         light = add(light, mul(hdr_color(p, d), red));
-        if (first) {
+        // (folded, null planes: a sample after the first of an spp draw, whose first-hit planes are sample 0's; the
+        // unfolded instantiation keeps its code: launch_wavefront points such a sample's stores elsewhere)
+        if (first && (!FOLD || p.emission.p)) {
           pst(p.emission, x, y, f4(0.0f, 0.0f, 0.0f, 1.0f));
           pst(p.albedo, x, y, f4(0.0f, 0.0f, 0.0f, 1.0f));
         }
         if (FOLD) terminal_write(p, x, y, light);
       } else {
         Hit h = decode_hit(p.scene, hr.x, __int_as_float(hr.y), S, d);
-        if (first) {
+        if (first && (!FOLD || p.emission.p)) {
           pst(p.emission, x, y, f4(h.m.emissive.x, h.m.emissive.y, h.m.emissive.z, 1.0f));
           pst(p.albedo, x, y, f4(h.m.baseColor.x, h.m.baseColor.y, h.m.baseColor.z, 1.0f));
         }
@@ -1753,7 +1755,9 @@ __global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bo
         float xi3 = u32_to_unit(wang_hash(&seed));
         v3 V = neg(h.viewDir);
         v3 L = sample_brdf(xi1, xi2, xi3, V, h.normal, h.m);
-        if (dot(h.normal, L) > 0.0f) {
+        // the reference ends the path on NdotL <= 0 (:1016, :1098): a NaN NdotL (a NaN vertex normal) goes on, its
+        // radiance turns NaN and the pixel ends at 0 (:1110-1113); `> 0` ended such a path with what it had gathered
+        if (!(dot(h.normal, L) <= 0.0f)) {
           push = true;
                   v3 brdf = brdf_eval(V, h.normal, L, h.m);
           float bpdf = brdf_pdf(V, h.normal, L, h.m);
@@ -1856,6 +1860,29 @@ __global__ void __launch_bounds__(256) wf_finalize(PTParams p) {
   terminal_write(p, x, y, xyz(ldnt(&p.wf.light[k])));
 }
 
+// ------------------------------------------------------ samples per pixel ---
+// The mean of an spp draw's samples (tests/spp_ref.py): sum = c_0, then sum + c_s in sample order, one IEEE division
+// by float(n), alpha 1; with accumulation the mix with lastFrame at the frame's own counter (terminal_write's
+// statement). One thread per pixel of the drawn tile subset, block b the subset's tile b as in the bounce-0 shade
+// (raster order: the resolve has no slow tiles to start first), so pixels outside the subset or the band's rows keep
+// their contents. Every index comes from the launch geometry; 16 (n + 1) bytes per pixel, each touched once.
+__global__ void __launch_bounds__(256) wf_spp_resolve(SppResolve r) {
+  const int ntx = (r.W + 15) / 16;
+  const int tile = (int)blockIdx.x * r.tile_stride + r.tile_offset;
+  const int x = (tile % ntx) * 16 + (threadIdx.x & 15), ly = (tile / ntx) * 16 + (threadIdx.x >> 4);
+  if (x >= r.W || ly >= r.y1 - r.y0) return;
+  const size_t pid = (size_t)ly * r.W + x;
+  v3 sum = xyz(ldnt(&r.samples[pid]));
+  for (int s = 1; s < r.n; ++s) sum = add(sum, xyz(ldnt(&r.samples[(size_t)s * r.stride + pid])));
+  v3 color = divs(sum, (float)r.n);
+  const int y = r.y0 + ly;
+  if (r.accumulate && r.last.p) {  // :1116-1119
+    float4 lc = pld(r.last, x, y);
+    color = mixv(xyz(lc), color, 1.0f / (float)(r.frameCounter + 1u));
+  }
+  pst(r.color, x, y, f4(color.x, color.y, color.z, 1.0f));
+}
+
 // A producer block appends at most 256 items to the segment blockIdx % kSeg; the most blocks
 // an appending launch has is the larger of the per-pixel grid and the bounce-0 tile grid.
 int wf_list_capacity(int W, int rows) {
@@ -1879,6 +1906,9 @@ int wf_subset_tiles(int W, int rows, int stride, int offset) {
 // launch per bounce for the list-driven traversals of every frame's rays (lane-refill kernels; the one-ray-per-lane
 // kernels run per frame). Frame b's wavefront state lies at pid offset b * N of ps[0]'s, its counters at
 // ps[0].wf.counters + b * kWfCounters; the batched launches use frame 0's work-queue heads and straggler lists.
+// rs (an spp draw, launch_pathtrace_wavefront_spp): the nb "frames" are the samples of one frame. The primary stage
+// runs for sample 0 alone and every sample's bounce-0 shade reads sample 0's hit; each path's end writes its sample's
+// plane (ps[s].color) and wf_spp_resolve folds the planes into rs->color after the last finish.
 // Grid of the list-driven shade (bounces > 0) and finish launches: until round 6 one block per 256 pixels (32 400 at
 // 4K), most of them past the list's end, reading its counts and leaving. Now at most PTSVGF_LIST_BLOCKS (read once;
 // default 2 048, a multiple of kSeg; 0 = one per 256 pixels) striding over 256-item chunks.
@@ -1893,7 +1923,7 @@ static int list_blocks(int n_items_max, int grid = 0) {
   return c > 0 && need > c ? c : need;
 }
 template <int KS, bool DEEP>
-int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk) {
+int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk, const SppResolve* rs = nullptr) {
   const PTParams& p = ps[0];
   const int rows = p.y1 - p.y0;
   if (rows <= 0) return 0;
@@ -1903,7 +1933,7 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
   if (e != hipSuccess) return (int)e;
   const int ntiles = wf_subset_tiles(p.W, rows, p.tile_stride, p.tile_offset);
   if (ntiles <= 0) return 0;
-  for (int b = 0; b < nb; ++b) {
+  for (int b = 0; b < (rs ? 1 : nb); ++b) {  // (the primary ray does not depend on the sample: :1060-1062)
     const PTParams& f = ps[b];
     if (f.primary_raster) {  // triangles (2) or leaves binned to every tile of the band; the subset's tiles rasterised
       const bool tris = f.primary_raster == 2;
@@ -1985,7 +2015,20 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
       if (e != hipSuccess) return (int)e;
     }
     for (int b = 0; b < nb; ++b) {
-      const PTParams& f = ps[b];
+      PTParams shared;
+      if (rs && i == 0 && b > 0) {
+        // Sample b's bounce-0 shade reads sample 0's primary hit (and, the samples being copies of one pass, its
+        // tiles.perm_next). ps[0].wf.hit is next written by closest(1), sample 0's own bounce-1 trace, which is issued
+        // on `s` after this loop has issued all nb bounce-0 shades on `s`: stream order puts every read before that
+        // write. The side stream of a trace_fork runs only the bounce-0 shadow walks and finish, which do not touch
+        // `hit`. The first-hit planes are sample 0's alone: the folded shade skips the stores of null planes; the
+        // unfolded one (shade_fold = 0, A/B) has no such branch and stores into the sample's own colour plane, every
+        // texel of which its wf_finalize writes afterwards on `s`.
+        shared = ps[b];
+        shared.wf.hit = ps[0].wf.hit;
+        shared.emission = shared.albedo = fold ? Plane{} : ps[b].color;
+      }
+      const PTParams& f = rs && i == 0 && b > 0 ? shared : ps[b];
       const int* live_in = f.wf.counters + kWfCtr * (i > 0 ? i - 1 : 0);
 #define PT_SHADE_LAUNCH(FOLD, FIRST, LAST)                                                                          \
   hipLaunchKernelGGL((wf_shade<FOLD, FIRST, LAST>), dim3(i == 0 ? gS0 : gL), dim3(256), 0, s, f, i,                  \
@@ -2067,6 +2110,9 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
   }
   if (!fold)
     for (int b = 0; b < nb; ++b) hipLaunchKernelGGL(wf_finalize, dim3(gN), dim3(256), 0, s, ps[b]);
+  // every sample's colour is written by now on `s` (the last bounce's finish or wf_finalize; a trace_fork joined
+  // before the bounce-1 shade)
+  if (rs) hipLaunchKernelGGL(wf_spp_resolve, dim3(ntiles), dim3(256), 0, s, *rs);
   return (int)hipGetLastError();
 }
 
@@ -2082,6 +2128,13 @@ int launch_pathtrace_wavefront_batch(const PTParams* ps, int nb, hipStream_t s, 
   if (ps[0].wf.spill) return launch_wavefront<kSpillKS, true>(ps, nb, s, fk);
   return ps[0].stack_need <= kStackSmall ? launch_wavefront<kStackSmall, false>(ps, nb, s, fk)
                                          : launch_wavefront<kStack, false>(ps, nb, s, fk);
+}
+
+int launch_pathtrace_wavefront_spp(const PTParams* ps, const SppResolve& rs, hipStream_t s, const WfFork* fk) {
+  if (rs.n < 2 || rs.n > kMaxBatch) return (int)hipErrorInvalidValue;
+  if (ps[0].wf.spill) return launch_wavefront<kSpillKS, true>(ps, rs.n, s, fk, &rs);
+  return ps[0].stack_need <= kStackSmall ? launch_wavefront<kStackSmall, false>(ps, rs.n, s, fk, &rs)
+                                         : launch_wavefront<kStack, false>(ps, rs.n, s, fk, &rs);
 }
 
 }  // namespace ptk

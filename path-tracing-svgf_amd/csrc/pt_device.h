@@ -185,6 +185,21 @@ struct ListBatch {
   const int* counts[kMaxBatch];
 };
 
+// Several samples per pixel in one draw (uniform spp = n, DESIGN.md "Samples per pixel"): the n samples run as the n
+// "frames" of a batch over one shared primary hit, each path's end writes its sample's colour to plane s of
+// `samples` (float4 per band pixel, n planes `stride` texels apart), and wf_spp_resolve folds them in sample order
+// into the pass's colour attachment.
+struct SppResolve {
+  int n;                  // samples, 2 .. kMaxBatch
+  const float4* samples;  // sample s of band pixel pid: samples[s * stride + pid]
+  size_t stride;          // band pixels
+  Plane color, last;      // the pass's colour attachment; lastFrame (read when accumulate != 0 and last.p)
+  int accumulate;
+  uint32_t frameCounter;  // the frame's own counter F (the accumulation weight), not a sample's
+  int W, y0, y1;          // the band, and the tile subset the draw traced (PTParams::tile_stride)
+  int tile_stride, tile_offset;
+};
+
 // Screen-tile binning of items (the G-buffer's triangles, the path tracer's BVH leaves) for the tile rasterisers:
 // an item-specific setup kernel writes each item's pixel box and counts it into the 16 x 16 tiles of the band it
 // covers (bins_count_item); launch_bins then bins the large items, scans and scatters (kernels_pt.hip).
@@ -417,6 +432,9 @@ int launch_bins(const Bins& b, hipStream_t s);  // after the item setup kernel: 
 int launch_tri_leaf_map(const float4* leaves, int nleaves, int* tri_leaf, int ntris, hipStream_t s);
 // nb frames' path tracing with batched traversal launches (ps[b]: frame b, its wavefront state at pid offset b * n)
 int launch_pathtrace_wavefront_batch(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk = nullptr);
+// rs.n samples of one frame (ps[s]: sample s, built by spp_sample_params, spp_params.h): the primary stage runs for
+// sample 0 alone, every sample's bounce-0 shade reads its hit, and wf_spp_resolve writes rs.color after the last finish
+int launch_pathtrace_wavefront_spp(const PTParams* ps, const SppResolve& rs, hipStream_t s, const WfFork* fk = nullptr);
 int launch_reproject(const ReprojParams& p, hipStream_t s);
 int launch_variance(const VarianceParams& p, hipStream_t s);
 int launch_atrous_exact(const AtrousParams& p, hipStream_t s);

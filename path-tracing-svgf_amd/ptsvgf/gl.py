@@ -355,6 +355,10 @@ class RenderPass:
         pt_trace_stats_count() = 14, and none past `count`) on every draw (0 disables)."""
         check(pt().pt_pass_set_trace_stats_n(self._handle(), C.c_void_p(device_ptr or None), count))
 
+    def set_spp(self, n: int) -> None:
+        """Path-tracing pass: samples per pixel of every draw (int uniform spp, 1 .. 8; the draw refuses others)."""
+        self.set_uniform_int("spp", n)
+
     def set_motion_bound(self, device_ptr: int) -> None:
         """G-buffer pass: store the largest |motion.y| of every draw into a device uint32 (float bits; 0 disables)."""
         check(pt().pt_pass_set_motion_bound(self._handle(), C.c_void_p(device_ptr or None)))

@@ -52,6 +52,7 @@ def main(argv=None) -> int:
     ap.add_argument("--mode", default="fast", choices=("fast", "reference"))
     ap.add_argument("--png", default="render.png")
     ap.add_argument("--pfm", default=None, help="also write the selected plane's floats")
+    ap.add_argument("--spp", type=int, default=1, help="path-tracing samples per pixel per frame (1 .. 8)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
 
@@ -62,7 +63,8 @@ def main(argv=None) -> int:
         scene.cache = hdr_cache(scene.hdr)
     gl.init(a.device)
     try:
-        r = Renderer(scene, a.width, a.height, parameter_config(), mode=a.mode, run_taa=True, run_output=True)
+        r = Renderer(scene, a.width, a.height, parameter_config(), mode=a.mode, run_taa=True, run_output=True,
+                     spp=a.spp)
         r.set_view(a.view)
         for _ in range(a.frames):
             if a.orbit:

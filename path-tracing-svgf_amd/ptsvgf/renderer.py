@@ -151,7 +151,7 @@ class Renderer:
                  halo=None, gbuffer_rows=None, frames_in_flight: int = 1, after_gbuffer=None, back_lag: int = 0,
                  trace_batch: int = 1, front_streams: int | None = None, pt_source=None, pt_flush=None,
                  stage_rows=None, early_history=None, draw_gbuffer: bool = True, fuse_modulate: bool = True,
-                 host_pace: bool = False):
+                 host_pace: bool = False, spp: int = 1):
         """band = (y0, y1, row0, rows) for screen-band sharding; tex_factory(w, h) -> handle allocates the
         frame-sized planes (ptsvgf.dist wraps torch tensors); halo(stage, {plane name: handle}) is called before
         the SVGF passes that read rows beyond the band (dist.HALO_SCHEDULE names the planes); after_gbuffer(set,
@@ -188,7 +188,13 @@ class Renderer:
         host_pace (frames in flight only): before issuing frame f's front end the host waits for the back end of
         frame f - K, which that front end waits for on the GPU anyway. Without it the host queues frames as fast as it
         can issue them and each frame's camera reaches the GPU long before its G-buffer runs (camera-to-modulate ≈ 8
-        frames at K = 4); with it at most K frames are queued."""
+        frames at K = 4); with it at most K frames are queued.
+
+        spp = N (1 .. 8, either driver; also the settable property `spp`): every path-tracing draw takes N samples
+        per pixel over one primary hit, sample s with the counter frameCounter * N + s, and writes their mean (in
+        sample order) to the colour plane the SVGF chain reads; emission / albedo are unchanged (DESIGN.md "Samples
+        per pixel"). The samples fill the traversal launches as a batch's frames do, so frames are not batched
+        (trace_batch) while N > 1."""
         if mode not in ("fast", "reference"):
             raise ValueError(mode)
         self.mode = mode
@@ -240,6 +246,7 @@ class Renderer:
         if self.K < 1 or (self.K > 1 and mode != "fast"):
             raise ValueError("frames_in_flight must be >= 1, and > 1 only with the fast driver")
         self.B = int(trace_batch)
+        self._spp = self._check_spp(spp)
         if not 1 <= self.B <= min(self.K, 8) or (self.B > 1 and mode != "fast"):
             raise ValueError(f"trace_batch must be in [1, min(frames_in_flight, 8)] (fast driver), got {trace_batch}")
         self.lag = max(int(back_lag), self.B - 1)
@@ -453,6 +460,7 @@ class Renderer:
             p.set_uniform_int("shadow_budget", VISIT_BUDGET)
             p.set_uniform_int("closest_budget", VISIT_BUDGET)
             p.set_uniform_int("trace_batch", self.B)
+            p.set_spp(self._spp)
             self.pt_slots.append((p, outs))
         self.pass_path_tracing = PassGroup([p for p, _ in self.pt_slots])  # settings apply to every slot
 
@@ -549,7 +557,28 @@ class Renderer:
         self._draw(pt, "pathtrace")
 
     def _batching(self) -> bool:
-        return self.B > 1 and self.mode == "fast" and not self.cfg.accumulate_color
+        return self.B > 1 and self.mode == "fast" and not self.cfg.accumulate_color and self._spp == 1
+
+    @staticmethod
+    def _check_spp(n) -> int:
+        if int(n) != n or not 1 <= int(n) <= 8:
+            raise ValueError(f"spp must be an integer in [1, 8], got {n!r}")
+        return int(n)
+
+    @property
+    def spp(self) -> int:
+        """Samples per pixel of every path-tracing draw (the int uniform spp of every slot's pass)."""
+        return self._spp
+
+    @spp.setter
+    def spp(self, n) -> None:
+        n = self._check_spp(n)
+        if n == self._spp:
+            return
+        self._issue_batch()  # frames of an open batch were set up at the old count
+        self._spp = n
+        for p, _ in self.pt_slots:
+            p.set_spp(n)
 
     def _issue_batch(self) -> None:
         """Draw the open batch's path tracers on the stream of its last frame, after all its G-buffers."""
