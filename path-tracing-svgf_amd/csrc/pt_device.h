@@ -21,36 +21,12 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-#else
-struct float4 {
-  float x, y, z, w;
-};
-struct int2 {
-  int x, y;
-};
-#endif
+
+#include "pt_layout.h"  // kStack, kWideStride, kNoneRef and the PT_KSTACK / PT_WIDE_STRIDE / PT_WIDE_ORDER defaults
 
 namespace ptk {
 
-#ifndef PT_KSTACK
-#define PT_KSTACK 32
-#endif
-// float4s per node of the 4-wide tree (pack_wide): 7 hold the four child boxes and refs. PT_WIDE_STRIDE = 8 pads a
-// node to one 128-B cache line (at 7, 112-B nodes straddle two lines for most indices): measured SLOWER, 211.5 ->
-// 202.6 fps at 4K and 69.2 -> 62.9 on the surface view (three alternating repetitions, profiles/r04/wide_stride_ab.log).
-#ifndef PT_WIDE_STRIDE
-#define PT_WIDE_STRIDE 7
-#endif
-constexpr int kWideStride = PT_WIDE_STRIDE;
-// PT_WIDE_ORDER = 1 (default): pack_wide stores a node's largest child first, i.e. right after the node, where the
-// node's own fetch already brings most of it into L1 (capi.hip). Same box, three alternating repetitions
-// (profiles/r04/wide_order_ab.log): 4K 210.6 / 212.2 / 210.4 -> 213.0 / 214.2 / 213.0 fps, surface view
-// 68.6 / 68.9 / 68.5 -> 69.7 / 69.7 / 69.7.
-#ifndef PT_WIDE_ORDER
-#define PT_WIDE_ORDER 1
-#endif
 // PT_WIDE_SIGNED = 1 (default since round 5): the 4-wide walks pick each child's near / far planes by the ray's
 // direction signs (which float4 is loaded) instead of slab's 6 min / max per child (pt_shading.h wide_step): 99 -> 92
 // VALU per shadow node step in the ISA. Same bits. With the traversal kernels at 7 waves per SIMD (kernels_wavefront.hip
@@ -60,7 +36,6 @@ constexpr int kWideStride = PT_WIDE_STRIDE;
 #ifndef PT_WIDE_SIGNED
 #define PT_WIDE_SIGNED 1
 #endif
-constexpr int kStack = PT_KSTACK;  // traversal stack depth (host checks BVH depth < kStack)
 // Traversal counters: a node visit counts PT_NODE_VISIT (1; a diagnostic build with 0 counts triangle tests only)
 #ifndef PT_NODE_VISIT
 #define PT_NODE_VISIT 1
@@ -74,7 +49,6 @@ constexpr int kStackSmall = 24;    // smaller LDS stack (more resident waves) fo
 #endif
 constexpr int kSpillKS = PT_SPILL_KS;
 constexpr int kBlock = 256;      // threads per block for per-pixel kernels
-constexpr int kNoneRef = (int)0x80000000;
 constexpr int kPointBins = 4;     // point-light shadow lists, one per light index mod 4 (coherent waves)
 constexpr int kLiveBins = 1;  // live-ray lists (by direction octant, 8 of them, measured 4 % slower: one list)
 // wavefront list counters per bounce (8 segments each): live bins, HDR shadow, point bins, straggler count
@@ -118,7 +92,7 @@ struct SceneDev {
   const float4* bvh4;   // 4-wide collapse of bvh for any-hit rays (7 x float4 / node), may be null
   int root4;
   int root4c;           // root of the closest-hit walks' 4-wide tree in bvh4 (= root4 unless PTSVGF_WIDE_COLLAPSE 2 / 3)
-  const float4* bvh_any;  // binary any-hit tree over bvh's leaves (capi.hip build_anyhit_tree), may be null
+  const float4* bvh_any;  // binary any-hit tree over bvh's leaves (host_trees.cpp build_anyhit_tree), may be null
   int root_any;
   int ntris;
   const float* lights;  // 6 floats per light (PointLight: position, radiance)
@@ -583,7 +557,7 @@ int lbvh_build(LbvhWork& w, const float* tri, TriLayout lay, int n, int leaf_n, 
                float* node_out, int* order, int* nnodes, hipStream_t s);
 
 // The walk trees of a tree lbvh_build wrote, derived on the device from its BVHNode_encoded texels (lbvh_trees):
-// the packed binary tree (capi.hip pack_bvh's records), the leaf list (upload_leaves') and the 4-wide tree
+// the packed binary tree (host_trees.cpp pack_bvh's records), the leaf list (upload_leaves') and the 4-wide tree
 // (pack_wide's greedy collapse), bit for bit what those host functions make of the same texels.
 struct LbvhTrees {
   void* base = nullptr;  // one allocation: bin | leaves | wide (the owner frees it)

@@ -393,6 +393,79 @@ def test_merged_environment_rebuilds_with_frames_in_flight(gpu, scene_small):
     assert not np.array_equal(outs[1][0], outs[1][1])
 
 
+def test_merged_environment_rebuilds_while_frames_read_it(gpu, scene_small):
+    """The variant of the test above without the host's wait: a new environment is uploaded while frames are in flight
+    on two streams (the upload waits for its own stream only, so the other stream's frame may still be reading the
+    merged copy), and the next frame rebuilds the merged copy at once. The rebuild must not write the buffer those
+    frames read: it is retired with its build's and its readers' events and a fresh or an idle one is written; which
+    of the two depends on the timing, the bits must not. The frames in flight across an upload read an environment
+    that is being replaced (GL would order the upload after them), so only frames issued after an upload are
+    compared: every one equals the two-fetch path's frame of the same sequence."""
+    gl = gpu
+    W, H = 64, 48
+    envs = (scene_small.hdr, scene_small.hdr[::-1].copy())
+    outs = []
+    for merge in (0, 1):
+        r = _renderer(scene_small, W, H, mode="fast", run_taa=False, run_output=False, frames_in_flight=2)
+        r.pass_path_tracing.set_uniform_int("hdr_merge", merge)  # (every frame slot's pass)
+        got = []
+        for env in (1, 0, 1):
+            for _ in range(4):
+                r.frame()
+            gl.upload_rgb32f(r.hdrMap, envs[env])  # no torch.cuda.synchronize() first
+            for _ in range(3):
+                r.frame()
+            got.append(gl.readback(r.planes()["color"]))
+        r.close()
+        outs.append(got)
+    for a, b in zip(*outs):
+        assert np.array_equal(a, b)
+    assert not np.array_equal(outs[1][0], outs[1][1])
+
+
+def test_failed_draw_leaves_no_merged_environment_behind(gpu, scene_small):
+    """A draw that fails between its parameter set-up (which builds the merged environment and names it as read by this
+    draw) and its launch keeps nothing of that: the hdrMap is destroyed (its merged copy goes with it) and bound anew
+    with the same contents, and the pass's next draws, with hdr_merge off and then on, equal those of a renderer that
+    never took the detour."""
+    from ptsvgf._lib import PtError
+
+    gl = gpu
+    W, H = 64, 48
+
+    def two_frames(r):
+        out = []
+        for merge in (0, 1):
+            r.pass_path_tracing.set_uniform_int("hdr_merge", merge)
+            r.frame()
+            out.append(gl.readback(r.planes()["color"]))
+        return out
+
+    a = _renderer(scene_small, W, H, mode="fast", run_taa=False, run_output=False)
+    want = two_frames(a)
+    a.close()
+    b = _renderer(scene_small, W, H, mode="fast", run_taa=False, run_output=False)
+    pt = b.pass_path_tracing
+    pt.set_uniform_int("hdr_merge", 1)
+    pt.set_uniform_int("pt_kernel", 1)
+    pt.set_uniform_int("tile_stride", 2)
+    b.camera.update()
+    with pytest.raises(PtError) as e:  # an argument error found after pt_params: nothing is launched
+        b._path_trace()
+    assert e.value.code == -6 and "tile subsets need the wavefront path tracer" in str(e.value)
+    old = b.hdrMap
+    gl.destroy_texture(old)
+    hh, hw = scene_small.hdr.shape[:2]
+    b.hdrMap = gl.getTextureRGB32F(hw, hh)
+    b._owned[b._owned.index(old)] = b.hdrMap
+    gl.upload_rgb32f(b.hdrMap, scene_small.hdr)
+    pt.set_uniform_int("pt_kernel", 0)
+    pt.set_uniform_int("tile_stride", 1)
+    got = two_frames(b)
+    b.close()
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
 def test_fast_driver_equals_reference_driver(gpu, scene_small):
     """Pointer-swapped fast driver == main.cpp call sequence with copies, bit for bit."""
     gl = gpu
@@ -669,7 +742,7 @@ def test_wide_tree_is_result_preserving(gpu, scene_name, request):
 
 
 def test_far_eye_walks_reference_tree(gpu, scene_small):
-    """the fine leaf boxes (capi.hip refine_leaves) are padded for ray origins within kFineEyeReach = 64 x
+    """the fine leaf boxes (host_trees.cpp refine_leaves) are padded for ray origins within kFineEyeReach = 64 x
     the scene's largest vertex coordinate. An eye beyond that (here 200 units from a unit-sized scene) makes pt_params
     walk the reference tree: the default settings then give exactly the bits of the reference-tree walk
     (closest_tree = 0, shadow_tree = 0), for a camera both inside and far outside the reach."""

@@ -1,4 +1,4 @@
-"""The trees the library derives from the reference tree (capi.hip build_anyhit_tree: SAH tree over the reference
+"""The trees the library derives from the reference tree (host_trees.cpp build_anyhit_tree: SAH tree over the reference
 leaves, treelet restructuring, fine leaves, 4-wide collapse greedy or by dynamic program), checked on the host through
 pt_tree_check (no device): the properties every walk's result preservation rests on (DESIGN.md "Closest-hit rays on
 the SAH tree", "The traversal in round 6"):

@@ -1,4 +1,4 @@
-"""One process of the 4-wide collapse A/B (capi.hip pack_wide, PTSVGF_WIDE_COLLAPSE read once per process): renders
+"""One process of the 4-wide collapse A/B (host_trees.cpp pack_wide, PTSVGF_WIDE_COLLAPSE read once per process): renders
 the bench scene, prints the traversal counters of one frame (node + triangle visits per kind) and a digest of the
 path tracer's planes, so two runs with PTSVGF_WIDE_COLLAPSE = 0 / 1 show the visits each tree costs and that the
 bits are the same. PTSVGF_WIDE_STATS=1 also prints the tree's summed node area.

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Tree-build A/B (VAR = PTSVGF_WIDE_COLLAPSE by default, capi.hip pack_wide; or PTSVGF_TREELET, treelet_optimize):
+# Tree-build A/B (VAR = PTSVGF_WIDE_COLLAPSE by default, host_trees.cpp pack_wide; or PTSVGF_TREELET, treelet_optimize):
 # visits and bits per value (tools/wide_collapse_ab.py), the wide-tree parity tests under MODES' last value, then the
 # bench alternating the values on both views, REPS times. Logs: gpurun_out/${TAG:-wide_ab}/.
 # usage: MODES="0 2 1" REPS=2 bash tools/wide_collapse_ab.sh; VAR=PTSVGF_TREELET MODES="0 1" TAG=treelet_ab bash ...
