@@ -280,6 +280,39 @@ int pt_pass_set_rows(uint32_t pass, int y_begin, int y_end);
  * device_counts[row - y_begin] (uint32 per computed row; caller zeroes it).
  * NULL disables. No reference counterpart (multi-GPU band planning). */
 int pt_pass_set_row_cost(uint32_t pass, void* device_counts);
+/* Per-pixel sample counts (path-tracing pass, wavefront kernel, spp = N > 1):
+ * while set, a draw reads device_u8[y * width + x] (one uint8 per frame pixel,
+ * global rows; the caller fills it before the draw on the drawing stream) and
+ * takes n = min(max(c, 1), N) samples at that pixel: sample s exists iff
+ * s < n, keeps the counter F * N + s, and the colour is the mean of the first
+ * n samples in sample order. A sample that does not exist traces no ray.
+ * Ignored at spp = 1. NULL unbinds. A draw with the plane bound under an
+ * active pt_set_band partition fails with PT_ERR_STATE before it launches
+ * anything. No reference counterpart. */
+int pt_pass_set_sample_counts(uint32_t pass, void* device_u8);
+/* Per-pixel sample statistics (path-tracing pass, wavefront kernel, spp > 1):
+ * while set, the resolve of a draw stores for every pixel it resolves the pair
+ * device_f32x2[y * width + x] = (m, v): mean and unbiased variance of the
+ * luminances (svgf_reproject.frag's) of the pixel's n samples, (l_0, -1) when
+ * n < 2. Pixels outside the drawn rows or tile subset keep their contents.
+ * Ignored at spp = 1. NULL unbinds. PT_ERR_STATE under an active pt_set_band
+ * partition, as above. No reference counterpart. */
+int pt_pass_set_sample_stats(uint32_t pass, void* device_f32x2);
+/* The next draw's sample counts from a draw's statistics, on the library's
+ * current stream: for every pixel of the frame out_u8 = 1 where nd_tex.w == 1
+ * (background); else the statistics are looked up at the texel holding
+ * (pixel centre) - lag * motion_tex.xy * (width, height) and the count is the
+ * largest, over the 3 x 3 texels around it inside the frame, of nmax where
+ * v < 0 or m or v is NaN, else ceil(v / (tolerance * max(m, 1e-4))^2) held to
+ * 2 .. nmax; nmax where that position is non-finite or outside the frame.
+ * stats: width * height float pairs (pt_pass_set_sample_stats); motion_tex,
+ * nd_tex: this frame's gMotion and gNormalAndLinearZ textures; lag: frames
+ * since the statistics' draw; out_u8: width * height bytes. PT_ERR_ARG for a
+ * tolerance that is not > 0, nmax outside 2 .. 8, null planes or textures of
+ * different sizes; PT_ERR_STATE for textures created under an active
+ * pt_set_band partition. Nothing is launched on an error. */
+int pt_sample_counts_derive(const void* stats, uint32_t motion_tex, uint32_t nd_tex, float lag, float tolerance,
+                            int nmax, void* out_u8);
 /* Motion bound (G-buffer pass): while set, every draw first zeroes *device_u32 and
  * then stores there the largest |motion.y| (UV units, the bits of a non-negative
  * float; +inf for a non-finite motion) over the surface pixels it computes. The

@@ -261,6 +261,8 @@ struct Pass {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
   uint32_t* row_cost = nullptr;  // pt_pass_set_row_cost (not owned)
+  uint8_t* sample_counts = nullptr;  // pt_pass_set_sample_counts (not owned)
+  float2* sample_stats = nullptr;    // pt_pass_set_sample_stats (not owned)
   uint32_t* motion_max = nullptr;  // pt_pass_set_motion_bound (not owned)
   unsigned long long* stats = nullptr;  // pt_pass_set_trace_stats (not owned)
   int stats_n = 0;                      // counters that buffer holds (pt_pass_set_trace_stats_n)
@@ -784,6 +786,12 @@ int att_plane(Pass* p, int k, Plane* out) {
     if (rc_ != PT_OK) return rc_; \
   } while (0)
 
+// pt_set_band holds a partition of W x H frames: a band or stored rows that are not the whole frame
+bool band_partition(int W, int H) {
+  return g.band_h > 0 && W == g.band_w && H == g.band_h &&
+         (g.band_y0 != 0 || g.band_y1 != H || g.band_row0 != 0 || g.band_rows != H);
+}
+
 void rows_of(Pass* p, int* y0, int* y1) {
   if (p->y_begin >= 0) {
     *y0 = p->y_begin;
@@ -1200,10 +1208,11 @@ int draw_pathtrace_spp(Pass* p, PTParams& k, SceneGPU* sg, int n) {
   rs.y1 = k.y1;
   rs.tile_stride = k.tile_stride;
   rs.tile_offset = k.tile_offset;
+  const ptk::SppAdaptive ad{p->sample_counts, p->sample_stats};
   int rc;
   const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
   if (rc) return rc;
-  rc = launch_pathtrace_wavefront_spp(ks, rs, g.stream, fk);
+  rc = launch_pathtrace_wavefront_spp(ks, rs, g.stream, fk, &ad);
   if (!rc && k.tiles.cost) p->order.ordered = true;
   return rc ? hip_err((hipError_t)rc, "pathtrace spp launch") : PT_OK;
 }
@@ -1213,6 +1222,9 @@ int draw_pathtrace(Pass* p) {
   TRY(pass_spp(p, &spp));
   if (spp > 1 && ui(p, "pt_kernel", 0) != 0)
     return err(PT_ERR_ARG, "spp > 1 needs the wavefront path tracer (pt_kernel = 0)");
+  // the count and statistics planes hold whole frames in global rows; a band partition's planes do not
+  if (spp > 1 && (p->sample_counts || p->sample_stats) && band_partition(p->W, p->H))
+    return err(PT_ERR_STATE, "sample counts / statistics cannot be bound under a pt_set_band partition");
   PTParams k;
   SceneGPU* sg = nullptr;
   DrawReads reads;
@@ -2872,6 +2884,53 @@ int pt_pass_set_row_cost(uint32_t pass, void* device_counts) {
   if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
   p->row_cost = (uint32_t*)device_counts;
   return PT_OK;
+}
+
+int pt_pass_set_sample_counts(uint32_t pass, void* device_u8) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (device_u8 && g.programs[p->program] != PK_PATHTRACE) return err(PT_ERR_ARG, "sample counts need a path-tracing pass");
+  p->sample_counts = (uint8_t*)device_u8;
+  return PT_OK;
+}
+
+int pt_pass_set_sample_stats(uint32_t pass, void* device_f32x2) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (device_f32x2 && g.programs[p->program] != PK_PATHTRACE)
+    return err(PT_ERR_ARG, "sample statistics need a path-tracing pass");
+  p->sample_stats = (float2*)device_f32x2;
+  return PT_OK;
+}
+
+int pt_sample_counts_derive(const void* stats, uint32_t motion_tex, uint32_t nd_tex, float lag, float tolerance,
+                            int nmax, void* out_u8) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  if (!stats || !out_u8) return err(PT_ERR_ARG, "pt_sample_counts_derive: null plane");
+  if (!(tolerance > 0.0f)) return err(PT_ERR_ARG, "pt_sample_counts_derive: the tolerance must be > 0");
+  if (nmax < 2 || nmax > kMaxBatch) return err(PT_ERR_ARG, "pt_sample_counts_derive: nmax must lie in 2 .. 8");
+  Texture* mt = tex_of(motion_tex);
+  Texture* nt = tex_of(nd_tex);
+  if (!mt || !nt || mt->target != PT_TEXTURE_2D || nt->target != PT_TEXTURE_2D || !mt->dev || !nt->dev)
+    return err(PT_ERR_MISSING_TEXTURE, "pt_sample_counts_derive needs the 2-D textures gMotion and gNormalAndLinearZ");
+  if (mt->W != nt->W || mt->H != nt->H) return err(PT_ERR_ARG, "pt_sample_counts_derive: textures of different sizes");
+  if (band_partition(mt->W, mt->H) || mt->row0 != 0 || nt->row0 != 0 || mt->rows != mt->H || nt->rows != nt->H)
+    return err(PT_ERR_STATE, "pt_sample_counts_derive: not under a pt_set_band partition");
+  ptk::SppCountsParams c{};
+  c.stats = (const float2*)stats;
+  c.motion = (const float4*)mt->dev;
+  c.nd = (const float4*)nt->dev;
+  c.out = (uint8_t*)out_u8;
+  c.W = mt->W;
+  c.H = mt->H;
+  c.nmax = nmax;
+  c.lag = lag;
+  c.tol = tolerance;
+  const int rc = launch_spp_counts(c, g.stream);
+  return rc ? hip_err((hipError_t)rc, "sample counts launch") : PT_OK;
 }
 
 int pt_pass_set_trace_stats_n(uint32_t pass, void* device_u64, int count) {

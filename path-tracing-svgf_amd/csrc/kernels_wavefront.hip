@@ -1673,11 +1673,15 @@ __device__ __forceinline__ void finish_apply(const PTParams& p, int pid, v3* red
 // bounce does not have and the stores nothing reads after the last: ray_d and seed. `red` and `light` are still
 // stored on the last bounce's continuing paths, whose wf_finish<true> reads both. The statements and their order
 // per path are those of the unfolded launches, so every plane keeps its bits.
-template <bool FOLD, bool FIRST, bool LAST>
-__global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bounce_rt, const int* __restrict__ list_in,
-                                                const int* __restrict__ counts_in, int* __restrict__ list_out,
-                                                int* __restrict__ counts_out, int* __restrict__ shadow_out,
-                                                int* __restrict__ shadow_counts, int cap) {
+// COUNTED (wf_shade_counted: sample `sample` >= 1 of an spp draw with a count plane bound, DESIGN.md "Adaptive sample
+// counts"): a bounce-0 pixel whose count c has max(c, 1) <= sample is no pixel of this launch: it reads and stores
+// nothing and appends to no list. sample_counts: one uint8 per frame pixel, global rows.
+template <bool FOLD, bool FIRST, bool LAST, bool COUNTED>
+__device__ __forceinline__ void shade_body(const PTParams& p, int bounce_rt, const int* __restrict__ list_in,
+                                           const int* __restrict__ counts_in, int* __restrict__ list_out,
+                                           int* __restrict__ counts_out, int* __restrict__ shadow_out,
+                                           int* __restrict__ shadow_counts, int cap,
+                                           const uint8_t* __restrict__ sample_counts, int sample) {
   // folded: bounce_rt is any bounce of the instantiation's kind; only `bounce == 0` is decided at compile time
   const int bounce = FOLD && FIRST ? 0 : bounce_rt;
   const bool first = FOLD ? FIRST : bounce == 0;
@@ -1699,6 +1703,7 @@ __global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bo
       const int x = (tile % ntx) * 16 + (threadIdx.x & 15), ly = (tile / ntx) * 16 + (threadIdx.x >> 4);
       valid = x < p.W && ly < p.y1 - p.y0;
       pid = ly * p.W + x;
+      if (COUNTED && valid) valid = sample < max((int)sample_counts[(size_t)(p.y0 + ly) * p.W + x], 1);
     } else {
       valid = bins_get(list_in, counts_in, kLiveBins, cap, k, &pid);
     }
@@ -1823,6 +1828,28 @@ __global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bo
   }
 }
 
+template <bool FOLD, bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade(PTParams p, int bounce_rt, const int* __restrict__ list_in,
+                                                const int* __restrict__ counts_in, int* __restrict__ list_out,
+                                                int* __restrict__ counts_out, int* __restrict__ shadow_out,
+                                                int* __restrict__ shadow_counts, int cap) {
+  shade_body<FOLD, FIRST, LAST, false>(p, bounce_rt, list_in, counts_in, list_out, counts_out, shadow_out, shadow_counts,
+                                       cap, nullptr, 0);
+}
+
+// The bounce-0 shade of sample `sample` >= 1 of an spp draw with a count plane bound (the unfolded one: FOLD = LAST =
+// false, as wf_shade<false, false, false> at bounce 0). Launched in place of wf_shade only then.
+template <bool FOLD, bool LAST>
+__global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade_counted(PTParams p, int* __restrict__ list_out,
+                                                                      int* __restrict__ counts_out,
+                                                                      int* __restrict__ shadow_out,
+                                                                      int* __restrict__ shadow_counts, int cap,
+                                                                      const uint8_t* __restrict__ sample_counts,
+                                                                      int sample) {
+  shade_body<FOLD, FOLD, LAST, true>(p, 0, nullptr, nullptr, list_out, counts_out, shadow_out, shadow_counts, cap,
+                                     sample_counts, sample);
+}
+
 // ----------------------------------------------------------------- finish ---
 // TERMINAL (the last bounce's finish with shade_fold): the path ends here, so its pixel's `color` is written
 // (terminal_write) and neither `red` nor `light` is stored.
@@ -1883,6 +1910,108 @@ __global__ void __launch_bounds__(256) wf_spp_resolve(SppResolve r) {
   pst(r.color, x, y, f4(color.x, color.y, color.z, 1.0f));
 }
 
+// luminance of svgf_reproject.frag (kernels_svgf.hip lum), of a sample's colour
+__device__ __forceinline__ float spp_lum(v3 c) { return (0.2125f * c.x + 0.7154f * c.y) + 0.0721f * c.z; }
+
+// wf_spp_resolve with a count plane and / or a statistics plane bound (tests/adaptive_ref.py; DESIGN.md "Adaptive
+// sample counts"). COUNTS: the pixel folds its first n = min(max(c, 1), N) samples, in sample order, and divides by
+// float(n); the planes of samples that do not exist are not read. STATS: the samples' luminances stay in registers
+// (the loops are unrolled over kMaxBatch and predicated on s < n) and one 8-byte store writes (m, v): the mean in
+// sample order over float(n) and sum (l_s - m)^2 in sample order over float(n - 1); (l_0, -1) at n < 2. Block and
+// thread indices as wf_spp_resolve; no LDS, no atomics; 16 (n + 1) + 1 + 8 bytes per pixel, each touched once.
+template <bool COUNTS, bool STATS>
+__global__ void __launch_bounds__(256) wf_spp_resolve_adaptive(SppResolve r, SppAdaptive a) {
+  const int ntx = (r.W + 15) / 16;
+  const int tile = (int)blockIdx.x * r.tile_stride + r.tile_offset;
+  const int x = (tile % ntx) * 16 + (threadIdx.x & 15), ly = (tile / ntx) * 16 + (threadIdx.x >> 4);
+  if (x >= r.W || ly >= r.y1 - r.y0) return;
+  const size_t pid = (size_t)ly * r.W + x;
+  const int y = r.y0 + ly;
+  const size_t gp = (size_t)y * r.W + x;  // the count and statistics planes hold the frame's rows
+  int n = r.n;
+  if (COUNTS) n = min(max((int)a.counts[gp], 1), r.n);
+  float l[kMaxBatch];
+  v3 sum = xyz(ldnt(&r.samples[pid]));
+  l[0] = spp_lum(sum);
+#pragma unroll
+  for (int s = 1; s < kMaxBatch; ++s) {
+    l[s] = 0.0f;
+    if (s < n) {
+      const v3 c = xyz(ldnt(&r.samples[(size_t)s * r.stride + pid]));
+      sum = add(sum, c);
+      if (STATS) l[s] = spp_lum(c);
+    }
+  }
+  v3 color = divs(sum, (float)n);
+  if (r.accumulate && r.last.p) {  // :1116-1119
+    float4 lc = pld(r.last, x, y);
+    color = mixv(xyz(lc), color, 1.0f / (float)(r.frameCounter + 1u));
+  }
+  pst(r.color, x, y, f4(color.x, color.y, color.z, 1.0f));
+  if (STATS) {
+    float m = l[0], v = -1.0f;
+    if (n >= 2) {
+#pragma unroll
+      for (int s = 1; s < kMaxBatch; ++s)
+        if (s < n) m = m + l[s];
+      m = m / (float)n;
+      float m2 = (l[0] - m) * (l[0] - m);
+#pragma unroll
+      for (int s = 1; s < kMaxBatch; ++s)
+        if (s < n) m2 = m2 + (l[s] - m) * (l[s] - m);
+      v = m2 / (float)(n - 1);
+    }
+    a.stats[gp] = make_float2(m, v);
+  }
+}
+
+// pt_sample_counts_derive (tests/adaptive_ref.py derive_counts): one thread per frame pixel, one byte stored. A
+// background pixel (nd.w == 1) takes 1 sample. A surface pixel looks its statistics up where it was `lag` frames ago,
+// q = floor(pixel centre - lag * motion * size), and takes the largest need of the 3 x 3 texels around q inside the
+// frame: N where there is no estimate (v < 0, NaN), else ceil(v / (tol * max(m, 1e-4))^2) held to 2 .. N. A
+// non-finite position or a q outside the frame gives N. Every read is of a texel the rule has tested to lie in the
+// frame; the nine 8-byte reads of neighbouring threads overlap, so all but the first come from L1 / L2.
+__global__ void __launch_bounds__(256) spp_counts_kernel(SppCountsParams c) {
+  const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (x >= c.W || y >= c.H) return;
+  const size_t i = (size_t)y * c.W + x;
+  int count;
+  if (c.nd[i].w == 1.0f) {
+    count = 1;
+  } else {
+    const float4 mv = c.motion[i];
+    const float fx = ((float)x + 0.5f) - (c.lag * mv.x) * (float)c.W;
+    const float fy = ((float)y + 0.5f) - (c.lag * mv.y) * (float)c.H;
+    count = c.nmax;
+    // (NaN fails every comparison; the bounds hold in float before the conversion, so no int overflows)
+    if (fx >= 0.0f && fx < (float)c.W && fy >= 0.0f && fy < (float)c.H) {
+      const int qx = (int)floorf(fx), qy = (int)floorf(fy);
+      count = 0;
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+          const int sx = qx + dx, sy = qy + dy;
+          if (sx < 0 || sx >= c.W || sy < 0 || sy >= c.H) continue;
+          const float2 mvv = c.stats[(size_t)sy * c.W + sx];
+          const float m = mvv.x, v = mvv.y;
+          int r = c.nmax;
+          if (!(v < 0.0f) && !f_isnan(m) && !f_isnan(v)) {
+            const float d = c.tol * fmaxf(m, 1e-4f);
+            const float k = ceilf(v / (d * d));
+            if (k < (float)c.nmax) r = max(2, (int)k);
+          }
+          count = max(count, r);
+        }
+    }
+  }
+  c.out[i] = (uint8_t)count;
+}
+
+int launch_spp_counts(const SppCountsParams& c, hipStream_t s) {
+  if (c.W <= 0 || c.H <= 0) return 0;
+  hipLaunchKernelGGL(spp_counts_kernel, dim3((c.W + 15) / 16, (c.H + 15) / 16), dim3(256), 0, s, c);
+  return (int)hipGetLastError();
+}
+
 // A producer block appends at most 256 items to the segment blockIdx % kSeg; the most blocks
 // an appending launch has is the larger of the per-pixel grid and the bounce-0 tile grid.
 int wf_list_capacity(int W, int rows) {
@@ -1909,6 +2038,8 @@ int wf_subset_tiles(int W, int rows, int stride, int offset) {
 // rs (an spp draw, launch_pathtrace_wavefront_spp): the nb "frames" are the samples of one frame. The primary stage
 // runs for sample 0 alone and every sample's bounce-0 shade reads sample 0's hit; each path's end writes its sample's
 // plane (ps[s].color) and wf_spp_resolve folds the planes into rs->color after the last finish.
+// ad (with rs; DESIGN.md "Adaptive sample counts"): with ad->counts the bounce-0 shades of samples >= 1 are
+// wf_shade_counted, and with either plane the resolve is wf_spp_resolve_adaptive; every other launch is unchanged.
 // Grid of the list-driven shade (bounces > 0) and finish launches: until round 6 one block per 256 pixels (32 400 at
 // 4K), most of them past the list's end, reading its counts and leaving. Now at most PTSVGF_LIST_BLOCKS (read once;
 // default 2 048, a multiple of kSeg; 0 = one per 256 pixels) striding over 256-item chunks.
@@ -1923,7 +2054,8 @@ static int list_blocks(int n_items_max, int grid = 0) {
   return c > 0 && need > c ? c : need;
 }
 template <int KS, bool DEEP>
-int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk, const SppResolve* rs = nullptr) {
+int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk, const SppResolve* rs = nullptr,
+                     const SppAdaptive* ad = nullptr) {
   const PTParams& p = ps[0];
   const int rows = p.y1 - p.y0;
   if (rows <= 0) return 0;
@@ -2035,12 +2167,22 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
                      (const int*)lst(f, i + 1), live_in, lst(f, i), f.wf.counters + kWfCtr * i, f.wf.shadow_list, \
                      f.wf.counters + kWfCtr * i + kCtrHdr, cap)
       const bool last = i + 1 == p.max_depth;
+      // a count plane: samples after the first skip the pixels that do not take them (sample 0 exists everywhere)
+#define PT_SHADE_COUNTED(FOLD, LAST)                                                                               \
+  hipLaunchKernelGGL((wf_shade_counted<FOLD, LAST>), dim3(gS0), dim3(256), 0, s, f, lst(f, i), f.wf.counters,     \
+                     f.wf.shadow_list, f.wf.counters + kCtrHdr, cap, ad->counts, b)
+      if (rs && ad && ad->counts && i == 0 && b > 0) {
+        if (!fold) PT_SHADE_COUNTED(false, false);
+        else if (last) PT_SHADE_COUNTED(true, true);
+        else PT_SHADE_COUNTED(true, false);
+      } else
       if (!fold) PT_SHADE_LAUNCH(false, false, false);
       else if (i == 0 && last) PT_SHADE_LAUNCH(true, true, true);
       else if (i == 0) PT_SHADE_LAUNCH(true, true, false);
       else if (last) PT_SHADE_LAUNCH(true, false, true);
       else PT_SHADE_LAUNCH(true, false, false);
 #undef PT_SHADE_LAUNCH
+#undef PT_SHADE_COUNTED
     }
     hipStream_t ss = s;  // the shadow walk's and finish's stream
     if (i == 0 && split) {
@@ -2112,7 +2254,13 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
     for (int b = 0; b < nb; ++b) hipLaunchKernelGGL(wf_finalize, dim3(gN), dim3(256), 0, s, ps[b]);
   // every sample's colour is written by now on `s` (the last bounce's finish or wf_finalize; a trace_fork joined
   // before the bounce-1 shade)
-  if (rs) hipLaunchKernelGGL(wf_spp_resolve, dim3(ntiles), dim3(256), 0, s, *rs);
+  if (rs && ad && ad->counts && ad->stats)
+    hipLaunchKernelGGL((wf_spp_resolve_adaptive<true, true>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+  else if (rs && ad && ad->counts)
+    hipLaunchKernelGGL((wf_spp_resolve_adaptive<true, false>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+  else if (rs && ad && ad->stats)
+    hipLaunchKernelGGL((wf_spp_resolve_adaptive<false, true>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+  else if (rs) hipLaunchKernelGGL(wf_spp_resolve, dim3(ntiles), dim3(256), 0, s, *rs);
   return (int)hipGetLastError();
 }
 
@@ -2130,11 +2278,13 @@ int launch_pathtrace_wavefront_batch(const PTParams* ps, int nb, hipStream_t s, 
                                          : launch_wavefront<kStack, false>(ps, nb, s, fk);
 }
 
-int launch_pathtrace_wavefront_spp(const PTParams* ps, const SppResolve& rs, hipStream_t s, const WfFork* fk) {
+int launch_pathtrace_wavefront_spp(const PTParams* ps, const SppResolve& rs, hipStream_t s, const WfFork* fk,
+                                   const SppAdaptive* ad) {
   if (rs.n < 2 || rs.n > kMaxBatch) return (int)hipErrorInvalidValue;
-  if (ps[0].wf.spill) return launch_wavefront<kSpillKS, true>(ps, rs.n, s, fk, &rs);
-  return ps[0].stack_need <= kStackSmall ? launch_wavefront<kStackSmall, false>(ps, rs.n, s, fk, &rs)
-                                         : launch_wavefront<kStack, false>(ps, rs.n, s, fk, &rs);
+  if (ad && !ad->counts && !ad->stats) ad = nullptr;
+  if (ps[0].wf.spill) return launch_wavefront<kSpillKS, true>(ps, rs.n, s, fk, &rs, ad);
+  return ps[0].stack_need <= kStackSmall ? launch_wavefront<kStackSmall, false>(ps, rs.n, s, fk, &rs, ad)
+                                         : launch_wavefront<kStack, false>(ps, rs.n, s, fk, &rs, ad);
 }
 
 }  // namespace ptk

@@ -174,6 +174,26 @@ struct SppResolve {
   int tile_stride, tile_offset;
 };
 
+// Per-pixel sample counts and statistics of an spp draw (DESIGN.md "Adaptive sample counts"), both addressed by frame
+// pixel in global rows (y * W + x) and either one optional. counts: pixel's samples n = min(max(c, 1), N); sample s
+// exists iff s < n. stats: the resolve writes (mean, unbiased variance) of the samples' luminances, (l_0, -1) at n < 2.
+struct SppAdaptive {
+  const uint8_t* counts;
+  float2* stats;
+};
+
+// pt_sample_counts_derive: the next draw's count plane from a draw's statistics, followed along this frame's motion
+// vectors (spp_counts_kernel). motion / nd: gMotion / gNormalAndLinearZ of the whole W x H frame.
+struct SppCountsParams {
+  const float2* stats;
+  const float4* motion;
+  const float4* nd;
+  uint8_t* out;
+  int W, H, nmax;
+  float lag, tol;
+};
+int launch_spp_counts(const SppCountsParams& c, hipStream_t s);
+
 // Screen-tile binning of items (the G-buffer's triangles, the path tracer's BVH leaves) for the tile rasterisers:
 // an item-specific setup kernel writes each item's pixel box and counts it into the 16 x 16 tiles of the band it
 // covers (bins_count_item); launch_bins then bins the large items, scans and scatters (kernels_pt.hip).
@@ -408,7 +428,9 @@ int launch_tri_leaf_map(const float4* leaves, int nleaves, int* tri_leaf, int nt
 int launch_pathtrace_wavefront_batch(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk = nullptr);
 // rs.n samples of one frame (ps[s]: sample s, built by spp_sample_params, spp_params.h): the primary stage runs for
 // sample 0 alone, every sample's bounce-0 shade reads its hit, and wf_spp_resolve writes rs.color after the last finish
-int launch_pathtrace_wavefront_spp(const PTParams* ps, const SppResolve& rs, hipStream_t s, const WfFork* fk = nullptr);
+// ad (optional): the draw's count and statistics planes; without it, or with both null, the launches are the plain ones
+int launch_pathtrace_wavefront_spp(const PTParams* ps, const SppResolve& rs, hipStream_t s, const WfFork* fk = nullptr,
+                                   const SppAdaptive* ad = nullptr);
 int launch_reproject(const ReprojParams& p, hipStream_t s);
 int launch_variance(const VarianceParams& p, hipStream_t s);
 int launch_atrous_exact(const AtrousParams& p, hipStream_t s);

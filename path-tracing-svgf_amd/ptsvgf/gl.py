@@ -248,6 +248,15 @@ def draw_batch(passes) -> None:
     check(pt().pt_pass_draw_batch(hs, len(passes)))
 
 
+def sample_counts_derive(stats_ptr: int, motion_tex: int, nd_tex: int, lag: float, tolerance: float, nmax: int,
+                         out_ptr: int) -> None:
+    """pt_sample_counts_derive: the next draw's per-pixel sample counts (W * H uint8 at out_ptr) from a draw's
+    statistics plane (W * H float32 pairs at stats_ptr), followed along this frame's motion vectors, on the
+    library's current stream."""
+    check(pt().pt_sample_counts_derive(C.c_void_p(stats_ptr or None), motion_tex, nd_tex, float(np.float32(lag)),
+                                       float(np.float32(tolerance)), int(nmax), C.c_void_p(out_ptr or None)))
+
+
 def readback(tex: int) -> np.ndarray:
     """Stored rows of an RGBA32F texture as (rows, W, 4) float32."""
     w, rows, _ = texture_info(tex)
@@ -358,6 +367,16 @@ class RenderPass:
     def set_spp(self, n: int) -> None:
         """Path-tracing pass: samples per pixel of every draw (int uniform spp, 1 .. 8; the draw refuses others)."""
         self.set_uniform_int("spp", n)
+
+    def set_sample_counts(self, device_ptr: int) -> None:
+        """Path-tracing pass, spp = N > 1: per-pixel sample counts (W * H uint8 on the device, global rows; a pixel
+        takes min(max(c, 1), N) samples; 0 unbinds)."""
+        check(pt().pt_pass_set_sample_counts(self._handle(), C.c_void_p(device_ptr or None)))
+
+    def set_sample_stats(self, device_ptr: int) -> None:
+        """Path-tracing pass, spp > 1: the resolve writes (mean, variance) of each pixel's sample luminances into
+        W * H float32 pairs on the device (0 unbinds)."""
+        check(pt().pt_pass_set_sample_stats(self._handle(), C.c_void_p(device_ptr or None)))
 
     def set_motion_bound(self, device_ptr: int) -> None:
         """G-buffer pass: store the largest |motion.y| of every draw into a device uint32 (float bits; 0 disables)."""

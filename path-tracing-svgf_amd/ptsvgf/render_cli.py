@@ -53,6 +53,8 @@ def main(argv=None) -> int:
     ap.add_argument("--png", default="render.png")
     ap.add_argument("--pfm", default=None, help="also write the selected plane's floats")
     ap.add_argument("--spp", type=int, default=1, help="path-tracing samples per pixel per frame (1 .. 8)")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="TAU",
+                    help="adaptive sample counts: relative tolerance of a pixel's mean luminance (needs --spp >= 2)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
 
@@ -64,7 +66,7 @@ def main(argv=None) -> int:
     gl.init(a.device)
     try:
         r = Renderer(scene, a.width, a.height, parameter_config(), mode=a.mode, run_taa=True, run_output=True,
-                     spp=a.spp)
+                     spp=a.spp, adaptive=a.adaptive)
         r.set_view(a.view)
         for _ in range(a.frames):
             if a.orbit:

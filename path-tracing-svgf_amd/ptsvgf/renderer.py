@@ -151,7 +151,7 @@ class Renderer:
                  halo=None, gbuffer_rows=None, frames_in_flight: int = 1, after_gbuffer=None, back_lag: int = 0,
                  trace_batch: int = 1, front_streams: int | None = None, pt_source=None, pt_flush=None,
                  stage_rows=None, early_history=None, draw_gbuffer: bool = True, fuse_modulate: bool = True,
-                 host_pace: bool = False, spp: int = 1):
+                 host_pace: bool = False, spp: int = 1, adaptive=None):
         """band = (y0, y1, row0, rows) for screen-band sharding; tex_factory(w, h) -> handle allocates the
         frame-sized planes (ptsvgf.dist wraps torch tensors); halo(stage, {plane name: handle}) is called before
         the SVGF passes that read rows beyond the band (dist.HALO_SCHEDULE names the planes); after_gbuffer(set,
@@ -194,7 +194,14 @@ class Renderer:
         per pixel over one primary hit, sample s with the counter frameCounter * N + s, and writes their mean (in
         sample order) to the colour plane the SVGF chain reads; emission / albedo are unchanged (DESIGN.md "Samples
         per pixel"). The samples fill the traversal launches as a batch's frames do, so frames are not batched
-        (trace_batch) while N > 1."""
+        (trace_batch) while N > 1.
+
+        adaptive = tau (a tolerance > 0; default None; needs spp >= 2; either driver): per-pixel sample counts
+        (DESIGN.md "Adaptive sample counts"). Every path-tracing slot owns a statistics plane its draws' resolve
+        writes and a count plane its draws read. Before a slot's draw, on the front end's stream right after the
+        G-buffer, the count plane is derived on the device from the statistics of the slot's own previous draw, looked
+        up along this frame's motion vectors scaled by the frames since that draw; a slot that has not drawn takes N
+        samples everywhere. sample_counts() / sample_stats() read the planes back."""
         if mode not in ("fast", "reference"):
             raise ValueError(mode)
         self.mode = mode
@@ -247,6 +254,10 @@ class Renderer:
             raise ValueError("frames_in_flight must be >= 1, and > 1 only with the fast driver")
         self.B = int(trace_batch)
         self._spp = self._check_spp(spp)
+        self.adaptive = self._check_adaptive(adaptive, self._spp)
+        self._ad: list = []  # per path-tracing slot: stats / counts (device tensors), last (frame of its last draw)
+        if self.adaptive is not None and pt_source is not None:
+            raise ValueError("adaptive needs the renderer's own path-tracing draws (no pt_source)")
         if not 1 <= self.B <= min(self.K, 8) or (self.B > 1 and mode != "fast"):
             raise ValueError(f"trace_batch must be in [1, min(frames_in_flight, 8)] (fast driver), got {trace_batch}")
         self.lag = max(int(back_lag), self.B - 1)
@@ -461,6 +472,15 @@ class Renderer:
             p.set_uniform_int("closest_budget", VISIT_BUDGET)
             p.set_uniform_int("trace_batch", self.B)
             p.set_spp(self._spp)
+            if self.adaptive is not None:
+                import torch
+
+                ad = dict(stats=torch.zeros((H, W, 2), dtype=torch.float32, device="cuda"),
+                          counts=torch.full((H, W), 255, dtype=torch.uint8, device="cuda"), last=None)
+                torch.cuda.current_stream().synchronize()  # the slot's draws run on the renderer's own streams
+                p.set_sample_stats(ad["stats"].data_ptr())
+                p.set_sample_counts(ad["counts"].data_ptr())
+                self._ad.append(ad)
             self.pt_slots.append((p, outs))
         self.pass_path_tracing = PassGroup([p for p, _ in self.pt_slots])  # settings apply to every slot
 
@@ -498,6 +518,8 @@ class Renderer:
         if self._pt_source is not None:
             self._ready = self._pt_source(self.frame_index, self._slot, self._lib_stream)
             return
+        if self.adaptive is not None:
+            self._derive_counts(self.gbuf[b])
         self._path_trace(self.gbuf[b] if self.mode == "fast" else None)
 
     def _gbuffer(self, b: int):
@@ -556,6 +578,47 @@ class Renderer:
             return  # drawn with its batch (_front_fast)
         self._draw(pt, "pathtrace")
 
+    def _derive_counts(self, g: dict) -> None:
+        """The current slot's count plane from its own previous statistics (library stream, after the G-buffer `g`).
+        That draw's resolve is ordered before this launch by what already orders the slot's reuse (_slot_free; one
+        stream when K = 1)."""
+        ad = self._ad[self._slot]
+        if ad["last"] is not None:
+            gl.sample_counts_derive(ad["stats"].data_ptr(), g["velocity"], g["normal_depth"],
+                                    float(self.frame_index - ad["last"]), self.adaptive, self._spp,
+                                    ad["counts"].data_ptr())
+        ad["last"] = self.frame_index
+
+    def sample_counts(self) -> np.ndarray:
+        """The count plane the last frame's path-tracing draw read, (H, W) uint8: 255 (= N) before the slot's first
+        draw, else pt_sample_counts_derive's values 1 .. N. adaptive only."""
+        return self._ad_read("counts")
+
+    def sample_stats(self) -> np.ndarray:
+        """The (mean, variance) plane the last frame's path-tracing draw wrote, (H, W, 2) float32. adaptive only."""
+        return self._ad_read("stats")
+
+    def _ad_read(self, key: str) -> np.ndarray:
+        if self.adaptive is None:
+            raise ValueError("the renderer was built without adaptive")
+        if self.frame_index < 1:
+            raise ValueError("no frame drawn yet")
+        import torch
+
+        self.flush()
+        torch.cuda.synchronize()
+        return self._ad[(self.frame_index - 1) % len(self.pt_slots)][key].cpu().numpy()
+
+    @staticmethod
+    def _check_adaptive(tau, spp):
+        if tau is None:
+            return None
+        if not float(tau) > 0.0:
+            raise ValueError(f"adaptive must be a tolerance > 0 (or None), got {tau!r}")
+        if spp < 2:
+            raise ValueError("adaptive needs spp >= 2: one sample gives no variance estimate")
+        return float(tau)
+
     def _batching(self) -> bool:
         return self.B > 1 and self.mode == "fast" and not self.cfg.accumulate_color and self._spp == 1
 
@@ -573,6 +636,7 @@ class Renderer:
     @spp.setter
     def spp(self, n) -> None:
         n = self._check_spp(n)
+        self._check_adaptive(self.adaptive, n)
         if n == self._spp:
             return
         self._issue_batch()  # frames of an open batch were set up at the old count
