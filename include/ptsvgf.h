@@ -356,7 +356,8 @@ int pt_trace_stats_total(void);
  * (its rays walk), [1] entries, [2..4] float bits of the light position the
  * bins were built around, [5] float bits of the coordinate magnitude the build
  * assumed, [6] entries of its catch-all list, [7] 0.
- * dims4: cells per cube-face edge, lights, entries a light has room for, 0.
+ * dims4: cells per cube-face edge, lights, entries a light has room for, bytes
+ * per entry (a light's lists hold [1] * that many bytes).
  * *bytes: the allocation. Any output may be NULL. */
 int pt_point_bins_info(uint32_t tri_tex, uint32_t node_tex, int* info8x4, int* dims4, size_t* bytes);
 int pt_pass_draw(uint32_t pass);

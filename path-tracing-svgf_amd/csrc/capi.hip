@@ -27,11 +27,13 @@
 
 #include "../../include/ptsvgf.h"
 #include "../../include/ptsvgf_debug.h"
+#include "../../include/ptsvgf_debug_pointbins.h"
 #include "../../include/ptsvgf_debug_pose.h"
 #include "../../include/ptsvgf_debug_refit.h"
 #include "../../include/ptsvgf_scene.h"
 #include "glsl_builtins.h"
 #include "host_trees.h"
+#include "pb_overlap.h"
 #include "pt_device.h"
 #include "spp_params.h"
 
@@ -363,16 +365,19 @@ struct DrawReads {
 
 // The point-light triangle bins of a scene (ptk::PointBinsDev, kernels_pointbins.hip) for the lights texture a
 // path-tracing draw bound: built on the device by the first such draw, rebuilt when the scene's triangles or tree, the
-// lights texture (handle, device memory, version) or pointLightSize change. Read by the path tracers of every frame
+// lights texture (handle, device memory, version), pointLightSize, R or the binning (point_bins_tight) change. Read
+// by the path tracers of every frame
 // in flight on other streams: a SharedBuf.
-constexpr int kPointBinsR = 64;  // cells per cube-face edge (uniform point_bins_r overrides: A/B)
+// cells per cube-face edge (uniform point_bins_r overrides: A/B). 128 since the lists hold 8-byte entries of the
+// polygon's cells only: its lists are smaller than the 64's were before, and it measured faster
+constexpr int kPointBinsR = 128;
 struct PointBinsGPU {
   SharedBuf sb;
   ptk::PointBinsDev dev{};
   uint64_t tri_ver = 0, node_ver = 0, light_ver = 0;
   uint32_t light_handle = 0;
   const void* light_dev = nullptr;
-  int nl = 0, R = 0, ntris = 0;
+  int nl = 0, R = 0, ntris = 0, tight = 0;
 };
 // drops a scene's point-light bins (the caller has synchronised the streams that read them)
 void free_point_bins(PointBinsGPU& m) {
@@ -933,14 +938,17 @@ int point_bins_for(Pass* p, SceneGPU* sg, Texture* lt, uint32_t lh, PTParams& k,
       !k.scene.lights || nl > k.scene.nlights_buf || !sg->tri_leaf || sg->tri_shared || !sg->leaves || sg->ntris <= 0)
     return PT_OK;
   const int R = std::min(ptk::kPointBinsMaxR, std::max(4, ui(p, "point_bins_r", kPointBinsR)));
+  // point_bins_tight (default 1): list a triangle in the cells its projected polygon reaches; 0: in every cell of
+  // the polygon's box (A/B; same verdicts, longer lists)
+  const int tight = ui(p, "point_bins_tight", 1) ? 1 : 0;
   PointBinsGPU& m = sg->pbins;
   const bool stale = !m.sb.buf || m.tri_ver != sg->tri_ver || m.node_ver != sg->node_ver || m.ntris != sg->ntris ||
                      m.light_handle != lh || m.light_dev != lt->dev || m.light_ver != lt->version || m.nl != nl ||
-                     m.R != R;
+                     m.R != R || m.tight != tight;
   if (stale) {
-    const size_t need = ptk::point_bins_bytes(sg->ntris, nl, R);
+    const size_t need = ptk::point_bins_bytes(sg->ntris, nl, R, tight);
     HIPCHK(m.sb.renew(need));
-    const int rc = ptk::launch_point_bins_build(k.scene, nl, R, m.sb.buf, &m.dev, g.stream);
+    const int rc = ptk::launch_point_bins_build(k.scene, nl, R, tight, m.sb.buf, &m.dev, g.stream);
     if (rc) return hip_err((hipError_t)rc, "point-light bins build");
     HIPCHK(m.sb.mark_built(g.stream));
     m.tri_ver = sg->tri_ver;
@@ -951,6 +959,7 @@ int point_bins_for(Pass* p, SceneGPU* sg, Texture* lt, uint32_t lh, PTParams& k,
     m.light_ver = lt->version;
     m.nl = nl;
     m.R = R;
+    m.tight = tight;
     if (getenv("PTSVGF_SCENE_INFO"))
       fprintf(stderr, "ptsvgf point-light bins: %d lights, R = %d, %zu B allocated (headers %zu B per light)\n", nl, R,
               need, (size_t)(6 * R * R + 1) * sizeof(int2));
@@ -2130,9 +2139,25 @@ int pt_point_bins_info(uint32_t tri_tex, uint32_t node_tex, int* info8x4, int* d
     dims4[0] = m.R;
     dims4[1] = m.nl;
     dims4[2] = m.dev.cap;
-    dims4[3] = 0;
+    dims4[3] = ptk::kPointBinsEntryBytes;
   }
   if (bytes) *bytes = m.sb.bytes;
+  return PT_OK;
+}
+
+int pt_debug_point_bins_overlap(const float* px, const float* py, int n, float fw, int R, int cx0, int cy0, int cx1,
+                                int cy1, uint8_t* kept, size_t cap, int* degenerate) {
+  if (!px || !py || !kept || R < 1 || cx0 < 0 || cy0 < 0 || cx1 >= R || cy1 >= R || cx0 > cx1 || cy0 > cy1)
+    return err(PT_ERR_ARG, "pt_debug_point_bins_overlap: bad box");
+  const int bw = cx1 - cx0 + 1, bh = cy1 - cy0 + 1;
+  if (cap < (size_t)bw * bh) return err(PT_ERR_ARG, "pt_debug_point_bins_overlap: kept is too small");
+  ptk::PbEdges e;
+  e.n = 0;
+  const bool ok = ptk::pb_edges(px, py, n, &e);
+  if (degenerate) *degenerate = ok ? 0 : 1;
+  if (bw * bh <= 2) e.n = 0;  // (as pb_bin: a box of at most two cells keeps both)
+  for (int cy = cy0; cy <= cy1; ++cy)
+    for (int cx = cx0; cx <= cx1; ++cx) kept[(cy - cy0) * bw + (cx - cx0)] = ptk::pb_cell_kept(e, fw, cx, cy, R) ? 1 : 0;
   return PT_OK;
 }
 

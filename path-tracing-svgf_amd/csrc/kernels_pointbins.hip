@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "glsl_builtins.h"
+#include "pb_overlap.h"
 #include "pt_device.h"
 #include "pt_shading.h"
 
@@ -31,20 +32,22 @@ struct PbLayout {
   int cap;
 };
 // entries a light's lists have room for. Measured on the bench scene (30 633 triangles, lights 0.3 .. 1 from the
-// geometry): at most 8.5 / 25 / 84 entries per triangle at R = 32 / 64 / 128; the per-cell term leaves room for the
-// few large triangles that cover whole faces. A light whose entries do not fit gets no bins (its rays walk).
-inline PbLayout pb_layout(int ntris, int nl, int R) {
+// geometry), the largest light's entries per triangle at R = 32 / 64 / 128: 4.6 / 8.9 / 20.0 by the polygon (the test
+// scenes: at most 13.3 at R = 64), 8.5 / 25 / 84 by the box; the per-cell term leaves room for the few large
+// triangles that cover whole faces. A light whose entries do not fit gets no bins (its rays walk).
+inline PbLayout pb_layout(int ntris, int nl, int R, int tight) {
   const size_t ncell1 = (size_t)6 * R * R + 1, al = 256;
   auto up = [&](size_t v) { return (v + al - 1) / al * al; };
   PbLayout l{};
-  const size_t cap = (size_t)(R > 64 ? 96 : 32) * (size_t)std::max(ntris, 1) + 8 * ncell1;
+  const size_t per_tri = tight ? (R > 64 ? 48 : 24) : (R > 64 ? 96 : 32);
+  const size_t cap = per_tri * (size_t)std::max(ntris, 1) + 8 * ncell1;
   l.cap = (int)std::min<size_t>(cap, (size_t)1 << 28);
   l.info = 0;
   l.cnt = up((size_t)(kPointBins + 1) * kPointBinsInfo * sizeof(int));  // (+1: the scene's magnitude)
   l.hdr = l.cnt + up((size_t)nl * ncell1 * sizeof(int));
   l.tmp = l.hdr + up((size_t)nl * ncell1 * sizeof(int2));
   l.ent = l.tmp + up((size_t)l.cap * sizeof(uint4));
-  l.total = l.ent + up((size_t)nl * l.cap * sizeof(uint4));
+  l.total = l.ent + up((size_t)nl * l.cap * sizeof(uint2));
   return l;
 }
 
@@ -54,8 +57,9 @@ struct PbBuild {
   int* cnt;      // nl x (ncell + 1): cell counts, then the scatter's fill counts
   int2* hdr;     // nl x (ncell + 1)
   uint4* tmp;    // cap: one light's entries in scatter order (the lights are scattered and sorted one after another)
-  uint4* ent;    // nl x cap: entries, each cell ascending by near
+  uint2* ent;    // nl x cap: entries (PointBinsDev), each cell ascending by near
   int R, nl, cap;
+  int tight;     // cells by the projected polygon (pb_overlap.h), 0: every cell of its box
   int l0;        // the scatter's and the sort's light (their grids have one light)
 };
 
@@ -135,13 +139,13 @@ __global__ void __launch_bounds__(256) pb_bin(PbBuild b) {
   const float rad = fmaxf(length(sub(v[0], c)), fmaxf(length(sub(v[1], c)), length(sub(v[2], c))));
   const float ds = fmaxf(length(sub(c, L)) - rad * 1.00001f, 0.0f);
   uint32_t box[6];
-  float nearf[6], ext[6][4];  // per face: cell box, near bound, the widened projection's extent in cell coordinates
-  for (int fc = 0; fc < 6 && !catchall; ++fc) {
-    box[fc] = kBoxEmpty;
-    nearf[fc] = 0.0f;
+  float nearf[6], ext[6][4], fwf[6];  // per face: cell box, near bound, the widened projection's extent in cell
+                                      // coordinates, the widening
+  float3 A[16], B[16];
+  // the triangle clipped to face fc's widened frustum, in A: vertices (x, y, w)
+  auto clip_face = [&](int fc) {
     const int a = fc >> 1;
     const float sg = (fc & 1) ? -1.0f : 1.0f;
-    float3 A[16], B[16];
     for (int k = 0; k < 3; ++k) {
       const float q[3] = {v[k].x - L.x, v[k].y - L.y, v[k].z - L.z};
       A[k] = make_float3(q[(a + 1) % 3], q[(a + 2) % 3], sg * q[a]);
@@ -149,14 +153,22 @@ __global__ void __launch_bounds__(256) pb_bin(PbBuild b) {
     int n = clip_plane(A, 3, B, 0, 1.0f);
     n = clip_plane(B, n, A, 0, -1.0f);
     n = clip_plane(A, n, B, 1, 1.0f);
-    n = clip_plane(B, n, A, 1, -1.0f);
+    return clip_plane(B, n, A, 1, -1.0f);
+  };
+  // cell coordinate of the direction (x, y, w): the cell is floor((x / w + 1) R / 2) (wf_shadow_point_bins)
+  auto cell_x = [&](const float3& p) { return (p.x / p.z + 1.0f) * 0.5f * (float)R; };
+  auto cell_y = [&](const float3& p) { return (p.y / p.z + 1.0f) * 0.5f * (float)R; };
+  for (int fc = 0; fc < 6 && !catchall; ++fc) {
+    box[fc] = kBoxEmpty;
+    nearf[fc] = 0.0f;
+    fwf[fc] = 0.0f;
+    const int n = clip_face(fc);
     if (n <= 0) continue;  // nothing of it in this face's widened frustum
     float x0 = 3.0e38f, y0 = 3.0e38f, x1 = -3.0e38f, y1 = -3.0e38f, wmin = 3.0e38f;
     bool bad = false;
     for (int k = 0; k < n; ++k) {
       const float w = A[k].z;
-      // cell coordinate of the direction (x, y, w): the cell is floor((x / w + 1) R / 2) (wf_shadow_point_bins)
-      const float px = (A[k].x / w + 1.0f) * 0.5f * (float)R, py = (A[k].y / w + 1.0f) * 0.5f * (float)R;
+      const float px = cell_x(A[k]), py = cell_y(A[k]);
       bad = bad || !(w > 0.0f) || !(px == px && py == py);
       wmin = fminf(wmin, w);
       x0 = fminf(x0, px); x1 = fmaxf(x1, px);
@@ -176,6 +188,7 @@ __global__ void __launch_bounds__(256) pb_bin(PbBuild b) {
     box[fc] = (uint32_t)cx0 | ((uint32_t)cx1 << 8) | ((uint32_t)cy0 << 16) | ((uint32_t)cy1 << 24);
     ext[fc][0] = fmaxf(x0 - fw, -lim); ext[fc][1] = fminf(x1 + fw, lim);
     ext[fc][2] = fmaxf(y0 - fw, -lim); ext[fc][3] = fminf(y1 + fw, lim);
+    fwf[fc] = fw;
     // a point the ray can be found to hit lies within e of a point of the triangle inside this face's frustum, which
     // is at least max(ds, wmin) from the light
     nearf[fc] = fmaxf(fmaxf(ds, wmin) * 0.99999f - e, 0.0f);
@@ -188,13 +201,27 @@ __global__ void __launch_bounds__(256) pb_bin(PbBuild b) {
     const uint32_t bx = box[fc];
     const int cx0 = bx & 255u, cx1 = (bx >> 8) & 255u, cy0 = (bx >> 16) & 255u, cy1 = bx >> 24;
     if (cx0 > cx1) continue;
-    // the extent inside each cell in 1 / 256 of a cell: (x0, x1, y0, y1), 8 bits each (kernels_wavefront.hip sub_cell)
+    // tight: of the box's cells only those the projected polygon, widened by fw, reaches (pb_overlap.h); the box's
+    // every cell when it has at most two or the polygon is degenerate (edges.n = 0 keeps all)
+    PbEdges edges;
+    edges.n = 0;
+    if (b.tight && (cx1 - cx0 + 1) * (cy1 - cy0 + 1) > 2) {
+      const int n = clip_face(fc);  // (the same arithmetic as above: the same polygon)
+      float px[kPbMaxVerts], py[kPbMaxVerts];
+      for (int k = 0; k < n && k < kPbMaxVerts; ++k) {
+        px[k] = cell_x(A[k]);
+        py[k] = cell_y(A[k]);
+      }
+      pb_edges(px, py, n, &edges);
+    }
+    // the extent inside each cell in 1 / 256 of a cell: (x0, x1, y0, y1), 8 bits each; pb_sort keeps the high 4
     auto q = [](float v) { return (uint32_t)min(max((int)floorf(v * 256.0f), 0), 255); };
     for (int cy = cy0; cy <= cy1; ++cy)
       for (int cx = cx0; cx <= cx1; ++cx)
-        emit((fc * R + cy) * R + cx, nearf[fc],
-             q(ext[fc][0] - (float)cx) | (q(ext[fc][1] - (float)cx) << 8) | (q(ext[fc][2] - (float)cy) << 16) |
-                 (q(ext[fc][3] - (float)cy) << 24));
+        if (pb_cell_kept(edges, fwf[fc], cx, cy, R))
+          emit((fc * R + cy) * R + cx, nearf[fc],
+               q(ext[fc][0] - (float)cx) | (q(ext[fc][1] - (float)cx) << 8) | (q(ext[fc][2] - (float)cy) << 16) |
+                   (q(ext[fc][3] - (float)cy) << 24));
   }
 }
 
@@ -232,14 +259,16 @@ __global__ void __launch_bounds__(kScanThreads) pb_scan(PbBuild b) {
   }
 }
 
-// One wave per cell: its entries from scatter order into ascending (near, triangle) order, by rank.
+// One wave per cell: its entries from scatter order into ascending (near, triangle) order, by rank, packed to the 8
+// bytes the trace kernel reads: near's high 16 bits (near >= 0: a lower bound that keeps the order) and the sub-cell
+// box in 1 / 16 of a cell (the floor of the scatter's 1 / 256: floor(floor(256 v) / 16) = floor(16 v)).
 __global__ void __launch_bounds__(256) pb_sort(PbBuild b) {
   const int l = blockIdx.y + b.l0, n1 = 6 * b.R * b.R + 1;
   const int cell = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (cell >= n1 || b.info[l * kPointBinsInfo]) return;
   const int2 h = b.hdr[(size_t)l * n1 + cell];
   const uint4* src = b.tmp + h.x;
-  uint4* dst = b.ent + (size_t)l * b.cap + h.x;
+  uint2* dst = b.ent + (size_t)l * b.cap + h.x;
   for (int i = lane; i < h.y; i += 64) {
     const uint4 me = src[i];
     int rank = 0;
@@ -247,21 +276,24 @@ __global__ void __launch_bounds__(256) pb_sort(PbBuild b) {
       const uint4 o = src[j];
       rank += (o.y < me.y || (o.y == me.y && o.x < me.x)) ? 1 : 0;
     }
-    dst[rank] = me;
+    const uint32_t sb = me.z;
+    const uint32_t box16 = ((sb >> 4) & 15u) | (((sb >> 12) & 15u) << 4) | (((sb >> 20) & 15u) << 8) | ((sb >> 28) << 12);
+    dst[rank] = make_uint2(me.x, (me.y >> 16) | (box16 << 16));
   }
 }
 
 }  // namespace
 
-size_t point_bins_bytes(int ntris, int nl, int R) { return pb_layout(ntris, nl, R).total; }
+size_t point_bins_bytes(int ntris, int nl, int R, int tight) { return pb_layout(ntris, nl, R, tight).total; }
 
-int launch_point_bins_build(const SceneDev& sc, int nl, int R, void* base, PointBinsDev* out, hipStream_t s) {
+int launch_point_bins_build(const SceneDev& sc, int nl, int R, int tight, void* base, PointBinsDev* out,
+                            hipStream_t s) {
   if (nl < 1 || nl > kPointBins || R < 1 || R > kPointBinsMaxR || !base || !sc.lights || !sc.tri_leaf)
     return (int)hipErrorInvalidValue;
-  const PbLayout lay = pb_layout(sc.ntris, nl, R);
+  const PbLayout lay = pb_layout(sc.ntris, nl, R, tight);
   char* c = (char*)base;
   PbBuild b{sc, (int*)(c + lay.info), (int*)(c + lay.cnt), (int2*)(c + lay.hdr), (uint4*)(c + lay.tmp),
-            (uint4*)(c + lay.ent), R, nl, lay.cap, 0};
+            (uint2*)(c + lay.ent), R, nl, lay.cap, tight ? 1 : 0, 0};
   hipError_t e = hipMemsetAsync(base, 0, lay.hdr, s);  // info and the cell counts
   if (e != hipSuccess) return (int)e;
   const int gt = (sc.ntris + 255) / 256, n1 = 6 * R * R + 1;

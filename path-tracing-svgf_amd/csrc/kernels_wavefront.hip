@@ -1384,8 +1384,9 @@ __global__ void __launch_bounds__(kTB) PT_TRACE_ATTR wf_trace_closest_refill(PTP
 // direction, an axis-parallel one) goes to the cooperative walk through the straggler list. The lists of a light
 // without usable bins, and of a light index past the bins' lights, stay with the shadow walk (bins_lists).
 // Lists of light l = list l of each frame; one wave takes 64 consecutive items of one list, so the light is
-// wave-uniform. The next entry's triangle is fetched one iteration ahead and the index of the one after that two
-// ahead: the addresses are known up front, so the loads of consecutive entries overlap.
+// wave-uniform. The next entry's triangle is fetched one iteration ahead and the entry after that two ahead: the
+// addresses are known up front, so the loads of consecutive entries overlap. (Fetching the triangle only for an
+// entry whose near and sub-cell box say it will be tested measured slower, 810 against 681 us per launch: DESIGN.md.)
 __global__ void __launch_bounds__(256) wf_shadow_point_bins(PTParams p, ListBatch lb, int cap,
                                                             int* __restrict__ strag_count) {
   const PointBinsDev& pb = p.pbins;
@@ -1404,7 +1405,7 @@ __global__ void __launch_bounds__(256) wf_shadow_point_bins(PTParams p, ListBatc
       const int* f = pb.info + (c < pb.nl ? c : 0) * kPointBinsInfo;
       const v3 L = mk(__int_as_float(f[2]), __int_as_float(f[3]), __int_as_float(f[4]));
       const int2* hdr = pb.hdr + (size_t)(c < pb.nl ? c : 0) * (ncell + 1);
-      const uint4* ent = pb.ent + (size_t)(c < pb.nl ? c : 0) * pb.cap;
+      const uint2* ent = pb.ent + (size_t)(c < pb.nl ? c : 0) * pb.cap;
       for (; vc < nch; vc += nw) {
         int pid = 0;
         const bool valid = seg_get(list, counts, cap, vc * 64 + lane, &pid);
@@ -1432,10 +1433,11 @@ __global__ void __launch_bounds__(256) wf_shadow_point_bins(PTParams p, ListBatc
             const float aw = fabsf(w);
             const float px = (xf / aw + 1.0f) * 0.5f * (float)R, py = (yf / aw + 1.0f) * 0.5f * (float)R;
             const int cx = min(max((int)floorf(px), 0), R - 1), cy = min(max((int)floorf(py), 0), R - 1);
-            // where in its cell, in 1 / 256 of the cell: an entry's sub-cell box holds every direction of the cell
-            // from which a ray can be found to hit its triangle (the build's extent, rounded outward)
-            const uint32_t qx = (uint32_t)min(max((int)floorf((px - (float)cx) * 256.0f), 0), 255);
-            const uint32_t qy = (uint32_t)min(max((int)floorf((py - (float)cy) * 256.0f), 0), 255);
+            // where in its cell, in 1 / 16 of the cell (the floor of the position in 1 / 256, as the build floors its
+            // extent): an entry's sub-cell box holds every direction of the cell from which a ray can be found to hit
+            // its triangle (the build's extent, rounded outward)
+            const uint32_t qx = (uint32_t)min(max((int)floorf((px - (float)cx) * 256.0f), 0), 255) >> 4;
+            const uint32_t qy = (uint32_t)min(max((int)floorf((py - (float)cy) * 256.0f), 0), 255) >> 4;
             const int2 h0 = hdr[ncell], h1 = hdr[((2 * a + (w < 0.0f ? 1 : 0)) * R + cy) * R + cx];
             const int n0 = h0.y, ne = n0 + h1.y;
             const float lim = maxd * 1.0002f + 2.0e-4f;
@@ -1443,20 +1445,26 @@ __global__ void __launch_bounds__(256) wf_shadow_point_bins(PTParams p, ListBatc
               j = min(j, ne - 1);
               return j < n0 ? ent[h0.x + j] : ent[h1.x + (j - n0)];
             };
+            // whether the scan tests entry e's triangle: near (its high 16 bits: no greater than the build's) within
+            // the ray's bound, and the ray's position inside the sub-cell box
+            auto near_ok = [&](uint2 e) { return !(__uint_as_float(e.y << 16) > lim); };
+            auto wanted = [&](uint2 e) {
+              const uint32_t sb = e.y >> 16;
+              return near_ok(e) && !(qx < (sb & 15u) || qx > ((sb >> 4) & 15u) || qy < ((sb >> 8) & 15u) || qy > (sb >> 12));
+            };
             if (ne > 0) {
-              uint4 e1 = entry(0), e2 = entry(1);
+              uint2 e1 = entry(0), e2 = entry(1);
               TriGeom g1 = tri_load(p.scene.tri_geom, (int)e1.x);
               int last_leaf = -1;
               bool last_ok = false;
               for (int i = 0; i < ne; ++i) {
-                const uint4 cur = e1;
+                const uint2 cur = e1;
                 const TriGeom tg = g1;
                 e1 = e2;
                 g1 = tri_load(p.scene.tri_geom, (int)e1.x);
                 e2 = entry(i + 2);
-                if (__uint_as_float(cur.y) > lim) break;  // this one and all after it lie beyond the ray's start
-                const uint32_t sb = cur.z;
-                if (qx < (sb & 255u) || qx > ((sb >> 8) & 255u) || qy < ((sb >> 16) & 255u) || qy > (sb >> 24)) continue;
+                if (!near_ok(cur)) break;  // this one and all after it lie beyond the ray's start
+                if (!wanted(cur)) continue;
                 float t;
                 ++vis;
                 if (!tri_test(tg, S, d, &t)) continue;

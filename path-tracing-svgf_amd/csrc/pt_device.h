@@ -217,10 +217,10 @@ struct Bins {
 // Point-light triangle bins (kernels_pointbins.hip): per light l < nl a cube map of 6 x R x R direction cells around
 // the light. Cell c = (face * R + row) * R + column of light l has the header hdr[l * (ncell + 1) + c] = (first
 // entry, entries) into ent + l * cap; header ncell is the light's catch-all list (triangles the build cannot bound:
-// every ray to the light tests them). An entry is (triangle, float bits of `near`, sub-cell box, 0): `near` a lower
-// bound of the distance from the light to any point of the triangle a shadow ray can be found to hit (a cell's
-// entries ascend by it); the box (x0 | x1 << 8 | y0 << 16 | y1 << 24, in 1 / 256 of the cell) holds every direction
-// of the cell from which such a ray can arrive.
+// every ray to the light tests them). An entry is 8 bytes, (triangle, near16 | box16 << 16): near16 the high 16 bits
+// of the float `near`, a lower bound of the distance from the light to any point of the triangle a shadow ray can be
+// found to hit (a cell's entries ascend by it; truncating a float >= 0 rounds it down); the box (x0 | x1 << 4 |
+// y0 << 8 | y1 << 12, in 1 / 16 of the cell) holds every direction of the cell from which such a ray can arrive.
 // info: kPointBinsInfo ints per light: [0] != 0: the light has no usable bins (a non-finite position, or the entries
 // overflowed `cap`: its rays walk), [1] entries, [2..4] float bits of the light position the bins were built around,
 // [5] float bits of Mtot, the coordinate magnitude of the scene plus the light's, [6] the catch-all list's entries.
@@ -228,7 +228,7 @@ constexpr int kPointBinsInfo = 8;
 constexpr int kPointBinsMaxR = 128;  // (the build packs a cell box into 4 x 8 bits)
 struct PointBinsDev {
   const int2* hdr;
-  const uint4* ent;
+  const uint2* ent;
   const int* info;
   int R, nl, cap;
   __host__ __device__ int ncell() const { return 6 * R * R; }
@@ -446,8 +446,12 @@ int launch_tile_sort(uint32_t* cost, int* perm, int ntiles, hipStream_t s);  // 
 int launch_hdr_merge(const float4* hdr, const float4* cache, float4* out, int n, hipStream_t s);  // (hdr.xyz, cache.z)
 // Point-light triangle bins of `nl` lights (sc.lights, 6 floats each) over sc's triangles with R x R cells per cube
 // face: point_bins_bytes() bytes at `base`; *out describes them. Everything runs on s; nothing is read back.
-size_t point_bins_bytes(int ntris, int nl, int R);
-int launch_point_bins_build(const SceneDev& sc, int nl, int R, void* base, PointBinsDev* out, hipStream_t s);
+size_t point_bins_bytes(int ntris, int nl, int R, int tight);
+// tight != 0: a triangle is listed in the cells its projected polygon reaches (pb_overlap.h), 0: in every cell of
+// the polygon's box (A/B).
+constexpr int kPointBinsEntryBytes = 8;
+int launch_point_bins_build(const SceneDev& sc, int nl, int R, int tight, void* base, PointBinsDev* out,
+                            hipStream_t s);
 }  // namespace ptk
 
 namespace ptk {

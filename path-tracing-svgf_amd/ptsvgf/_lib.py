@@ -145,6 +145,9 @@ _PT_SIGS = [
     ("pt_debug_lbvh_order", C.c_int, [_u32, C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_size_t)]),
     # include/ptsvgf_debug_pose.h
     ("pt_debug_pose_raster", C.c_int, [_u32, C.c_int, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    # include/ptsvgf_debug_pointbins.h
+    ("pt_debug_point_bins_overlap", C.c_int, [_fp, _fp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int)]),
 ]
 
 _PTS_SIGS = [

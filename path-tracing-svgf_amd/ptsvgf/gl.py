@@ -194,16 +194,34 @@ def lbvh_trees(tex: int, source: int = 0) -> dict:
 
 def point_bins_info(tri_tex: int, node_tex: int) -> dict:
     """pt_point_bins_info: the point-light triangle bins the last path-tracing draw of the scene (tri_tex, node_tex)
-    built: cells per face edge R, lights, entry capacity per light, allocated bytes, and per light {"off": no usable
-    bins, "entries", "catch_all", "pos", "magnitude"}."""
+    built: cells per face edge R, lights, entry capacity per light, bytes per entry, allocated bytes, and per light
+    {"off": no usable bins, "entries", "list_bytes" (entries x entry_bytes), "catch_all", "pos", "magnitude"}."""
     info = (C.c_int * 32)()
     dims = (C.c_int * 4)()
     nbytes = C.c_size_t()
     check(pt().pt_point_bins_info(tri_tex, node_tex, info, dims, C.byref(nbytes)))
     raw = np.array(list(info), np.int32).reshape(4, 8)
-    lights = [{"off": int(r[0]), "entries": int(r[1]), "catch_all": int(r[6]), "pos": r[2:5].view(np.float32).tolist(),
-               "magnitude": float(r[5:6].view(np.float32)[0])} for r in raw[:dims[1]]]
-    return {"R": dims[0], "lights": dims[1], "cap": dims[2], "bytes": nbytes.value, "per_light": lights}
+    lights = [{"off": int(r[0]), "entries": int(r[1]), "list_bytes": int(r[1]) * dims[3], "catch_all": int(r[6]),
+               "pos": r[2:5].view(np.float32).tolist(), "magnitude": float(r[5:6].view(np.float32)[0])}
+              for r in raw[:dims[1]]]
+    return {"R": dims[0], "lights": dims[1], "cap": dims[2], "entry_bytes": dims[3], "bytes": nbytes.value,
+            "per_light": lights}
+
+
+def point_bins_overlap(px, py, fw: float, R: int, box) -> tuple:
+    """pt_debug_point_bins_overlap: which cells of box = (cx0, cy0, cx1, cy1) of an R x R face list a triangle whose
+    projected polygon has the cell coordinates (px, py), widened by fw: (kept[cy - cy0, cx - cx0] bool array,
+    degenerate). Runs on the host."""
+    px = np.ascontiguousarray(px, np.float32)
+    py = np.ascontiguousarray(py, np.float32)
+    cx0, cy0, cx1, cy1 = (int(v) for v in box)
+    kept = np.zeros((cy1 - cy0 + 1, cx1 - cx0 + 1), np.uint8)
+    deg = C.c_int()
+    fp = C.POINTER(C.c_float)
+    check(pt().pt_debug_point_bins_overlap(px.ctypes.data_as(fp), py.ctypes.data_as(fp), len(px), float(fw), int(R),
+                                           cx0, cy0, cx1, cy1, kept.ctypes.data_as(C.POINTER(C.c_uint8)), kept.size,
+                                           C.byref(deg)))
+    return kept.astype(bool), bool(deg.value)
 
 
 class PtTileSeg(C.Structure):
