@@ -1,6 +1,7 @@
 // capi.hip — implementation of include/ptsvgf.h: the GL-plumbing-shaped C ABI
 // (Utils/render_pass.h:82-182, Utils/shader.h:21-67, Utils/help_func.h:22-32)
-// over HIP device memory and the gfx950 kernels.
+// over HIP device memory and the gfx950 kernels. The entry points of geometry that moves (builds, refits, raster binds,
+// poses) are in capi_geometry.hip; capi_state.h holds what the two share.
 //
 // GL semantics kept:
 //  * RenderPass uniforms are set by name; an unknown name is silently ignored;
@@ -10,147 +11,74 @@
 //  * draw() is ordered after every previous draw (one in-order HIP stream);
 //  * scene texture buffers are decoded once per (buffer, version) into the
 //    kernels' SoA records (pt_device.h) on first use, like a driver upload.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
 #include <cstdio>
 #include <algorithm>
-#include <array>
 #include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/ptsvgf.h"
-#include "../../include/ptsvgf_debug.h"
 #include "../../include/ptsvgf_debug_pointbins.h"
-#include "../../include/ptsvgf_debug_pose.h"
-#include "../../include/ptsvgf_debug_refit.h"
 #include "../../include/ptsvgf_scene.h"
+#include "capi_state.h"
 #include "glsl_builtins.h"
 #include "host_trees.h"
 #include "pb_overlap.h"
-#include "pt_device.h"
 #include "spp_params.h"
+
+static thread_local std::string g_err;
+
+// the state and helpers capi_state.h declares
+namespace ptapi {
+
+Lib g;
+std::recursive_mutex g_mu;
+ptk::LbvhWork g_lbvh;
+
+int err(int code, const std::string& m) {
+  g_err = m;
+  return code;
+}
+int hip_err(hipError_t e, const char* what) {
+  return err(PT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+Texture* tex_of(uint32_t h) {
+  auto it = g.textures.find(h);
+  return it == g.textures.end() ? nullptr : it->second.get();
+}
+Pass* pass_of(uint32_t h) {
+  auto it = g.passes.find(h);
+  return it == g.passes.end() ? nullptr : it->second.get();
+}
+
+int ensure_init() {
+  if (g.init) return PT_OK;
+  return err(PT_ERR_STATE, "pt_init() has not been called");
+}
+
+// The host mirror of a texbuffer pt_bvh_refit wrote in place is lazy: the refit pays no copy, and whoever reads
+// t->host's contents calls this first (pt_debug_lbvh_trees source 1, get_scene's host decode; pt_texture_readback
+// reads the device copy, and get_scene_lbvh only the sizes, which a refit keeps).
+int refresh_host(Texture* t) {
+  if (!t->host_stale) return PT_OK;
+  HIPCHK(hipDeviceSynchronize());
+  t->host.resize(t->bytes);
+  if (t->bytes) HIPCHK(hipMemcpy(t->host.data(), t->dev, t->bytes, hipMemcpyDeviceToHost));
+  t->host_stale = false;
+  return PT_OK;
+}
+
+}  // namespace ptapi
+
+using namespace ptapi;
 
 namespace {
 
 using namespace ptk;
 
-enum ProgKind {
-  PK_PATHTRACE = 1,
-  PK_REPROJECT,
-  PK_VARIANCE,
-  PK_ATROUS,
-  PK_MODULATE,
-  PK_BLIT,
-  PK_SAVE,
-  PK_OUTPUT,
-  PK_TAA,
-  PK_RASTER
-};
-
-struct Texture {
-  uint32_t target = PT_TEXTURE_2D;
-  int W = 0, H = 0;      // logical (global) size
-  int row0 = 0, rows = 0;  // stored rows (band)
-  int layers = 0;
-  bool owned = true;
-  void* dev = nullptr;
-  size_t bytes = 0;
-  std::vector<uint8_t> host;  // buffers: host copy for decoding
-  uint64_t version = 1;
-  // compact one-float side plane of the stored rows: a depth-fwidth attachment's fwidth.y with the background flag, a
-  // world-position attachment's primary-ray bound for rays from aux_eye (draw_raster)
-  float* aux = nullptr;
-  bool aux_valid = false;
-  float aux_eye[3] = {0.0f, 0.0f, 0.0f};
-  unsigned char* tflags = nullptr;  // a-trous per-tile surface flags derived from aux (atrous_tile_flags)
-  size_t tflags_cap = 0;
-  uint64_t tflags_ver = 0;          // texture version / rows they were derived for
-  int tflags_y0 = 0, tflags_y1 = -1;
-  bool lbvh = false;     // written by pt_bvh_build (the device copy is authoritative: get_scene decodes it there)
-  // a node buffer pt_bvh_build wrote: the walk trees the device derived from it (owned; trees->version == version)
-  ptk::LbvhTrees* trees = nullptr;
-  // a node buffer pt_bvh_build wrote: what pt_bvh_refit needs (owned, held as trees is) and the pair it belongs to,
-  // the triangle buffer's handle and both versions as the build (or the last refit) left them
-  ptk::LbvhRefit* refit = nullptr;
-  uint32_t refit_tri = 0;
-  uint64_t refit_tri_ver = 0, refit_node_ver = 0;
-  // pt_bvh_refit wrote dev in place; host is brought up to date by its readers (refresh_host)
-  bool host_stale = false;
-};
-
-void free_trees(Texture* t) {
-  if (!t->trees) return;
-  ptk::lbvh_trees_free(*t->trees);
-  delete t->trees;
-  t->trees = nullptr;
+std::string basename_of(const char* p) {
+  std::string s(p ? p : "");
+  size_t k = s.find_last_of("/\\");
+  return k == std::string::npos ? s : s.substr(k + 1);
 }
-
-void free_refit(Texture* t) {
-  if (!t->refit) return;
-  ptk::lbvh_refit_free(*t->refit);
-  delete t->refit;
-  t->refit = nullptr;
-}
-
-struct Uniform {
-  int type = 0;  // 1 float 2 int 3 uint 4 bool 5 vec3 6 mat4
-  float f[16] = {0};
-  int i = 0;
-  uint32_t u = 0;
-};
-
-struct RasterScene {
-  float4* geom = nullptr;
-  float4* nrm = nullptr;
-  float4* disp = nullptr;  // pt_raster_pass_set_prev_vertices: displacement records beside nrm, or null
-  float4* bvh = nullptr;
-  int root_ref = 0;
-  int stack_need = 0;
-  int ntris = 0;
-  // pt_raster_pass_bind_device: the encoded nodes of the bind and what refits them (pt_raster_pass_refit_device);
-  // null after a host bind
-  float* enc_nodes = nullptr;
-  ptk::LbvhRefit* refit = nullptr;
-  int bvh_records = 0;  // packed records bvh has room for (that bind's)
-};
-
-void free_raster_refit(RasterScene& r) {
-  if (r.enc_nodes) (void)hipFree(r.enc_nodes);
-  r.enc_nodes = nullptr;
-  if (!r.refit) return;
-  ptk::lbvh_refit_free(*r.refit);
-  delete r.refit;
-  r.refit = nullptr;
-}
-
-// Scratch of the tile-binned G-buffer (launch_gbuffer_raster), per rasterize pass, sized by its triangles and band.
-struct RasterBins {
-  void* base = nullptr;
-  int ntris = 0, ntiles = 0, pair_cap = 0, big_cap = 0;
-  int4* tri_box = nullptr;
-  float* tri_tmin = nullptr;
-  int *tile_count = nullptr, *tile_off = nullptr, *pairs = nullptr, *big = nullptr, *ctr = nullptr;
-};
-
-struct WFBuffers {
-  void* base = nullptr;  // one allocation carved into the WFState arrays
-  size_t n = 0;          // pixels per frame
-  int nb = 1;            // frames (pt_pass_draw_batch): per-pixel arrays for nb * n pixels, lists and counters per frame
-  WFState stb[kMaxBatch]{};  // frame b's state: per-pixel arrays at pid offset b * n; stb[0] == st
-  WFState st{};
-  float4* spp = nullptr;  // the sample planes of an spp draw: nsp planes of n texels (SppResolve::samples)
-  int nsp = 0;
-  int* spill = nullptr;  // deep reference trees: stack entries past the LDS stack (WFState::spill)
-  int spill_levels = 0;
-  size_t spill_cols = 0;
-};
 
 // Spill columns for a tree needing `need` stack entries (> the LDS stack): (need - kSpillKS + 1) entries per
 // pixel of the band, allocated on first use and kept while the depth fits.
@@ -238,274 +166,19 @@ int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1, int nsp = 0) {
   return PT_OK;
 }
 
-// Cost-ordered tile dispatch state of one traversal pass (TileSched, pt_device.h).
-struct TileOrder {
-  uint32_t* cost = nullptr;  // per-tile cost recorded by the current launch
-  int* perm = nullptr;       // dispatch order computed from the previous launch
-  int n = 0;
-  bool ordered = false;      // perm holds a valid order for n tiles
-};
-
-struct Pass {
-  uint32_t program = 0;
-  WFBuffers wf;
-  TileOrder order;
-  int W = 0, H = 0;
-  std::vector<uint32_t> att;
-  bool bound = false, final_pass = false;
-  int slot = 0;
-  std::unordered_map<std::string, uint32_t> tex;
-  std::unordered_map<std::string, Uniform> uni;
-  int y_begin = -1, y_end = -1;
-  RasterScene raster;
-  uint32_t raster_src = 0;  // pt_raster_pass_share: draw this rasterize pass's triangles and tree instead
-  RasterBins bins;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
-  uint32_t* row_cost = nullptr;  // pt_pass_set_row_cost (not owned)
-  uint8_t* sample_counts = nullptr;  // pt_pass_set_sample_counts (not owned)
-  float2* sample_stats = nullptr;    // pt_pass_set_sample_stats (not owned)
-  uint32_t* motion_max = nullptr;  // pt_pass_set_motion_bound (not owned)
-  unsigned long long* stats = nullptr;  // pt_pass_set_trace_stats (not owned)
-  int stats_n = 0;                      // counters that buffer holds (pt_pass_set_trace_stats_n)
-};
-
-// A device buffer built on one draw's stream and read by the draws of every frame in flight on other streams (the
-// merged environment, the point-light bins). A rebuild writes a buffer no draw still reads: the current one is retired
-// with the event of the build that wrote it and its readers' events, and a retired buffer is taken again only once all
-// of those have completed, else a new one is allocated. Every reader's stream waits for the build's event. No host
-// wait anywhere, so a rebuild never blocks on the device (e.g. on RCCL receives in flight for peers); retired buffers
-// are kept, never freed mid-run. Rebuilds are rare.
-struct SharedBuf {
-  void* buf = nullptr;
-  size_t bytes = 0;
-  hipEvent_t built = nullptr;              // recorded after the work that wrote buf, on the stream that ran it
-  std::map<hipStream_t, hipEvent_t> uses;  // per draw stream: recorded after its latest draw that read buf
-  struct Retired {
-    void* buf;
-    size_t bytes;
-    hipEvent_t built;  // the build that wrote it (null: none was recorded)
-    std::vector<hipEvent_t> readers;
-  };
-  std::vector<Retired> spare;
-
-  // a buffer of at least `need` bytes that nothing in flight reads or writes, in place of the current one
-  hipError_t renew(size_t need) {
-    if (buf) {
-      Retired r{buf, bytes, built, {}};
-      for (auto& u : uses) r.readers.push_back(u.second);
-      uses.clear();
-      spare.push_back(std::move(r));
-      buf = nullptr;
-      bytes = 0;
-      built = nullptr;
-    }
-    for (size_t i = 0; i < spare.size(); ++i) {
-      Retired& r = spare[i];
-      bool idle = r.bytes >= need && (!r.built || hipEventQuery(r.built) == hipSuccess);
-      for (size_t j = 0; idle && j < r.readers.size(); ++j) idle = hipEventQuery(r.readers[j]) == hipSuccess;
-      if (!idle) continue;
-      buf = r.buf;
-      bytes = r.bytes;
-      built = r.built;  // completed: recorded again by mark_built
-      for (hipEvent_t e : r.readers) (void)hipEventDestroy(e);
-      spare.erase(spare.begin() + i);
-      return hipSuccess;
-    }
-    const hipError_t e = hipMalloc(&buf, need);
-    if (e != hipSuccess) buf = nullptr;
-    else bytes = need;
-    return e;
-  }
-  // after the work that wrote buf was issued on s
-  hipError_t mark_built(hipStream_t s) {
-    if (!built)
-      if (const hipError_t e = hipEventCreateWithFlags(&built, hipEventDisableTiming)) return e;
-    return hipEventRecord(built, s);
-  }
-  // before work on s reads buf (a no-op wait once the build has run)
-  hipError_t wait_built(hipStream_t s) { return hipStreamWaitEvent(s, built, 0); }
-  // after a draw on s that read buf was issued: a later renew knows when that draw no longer reads it
-  hipError_t note_read(hipStream_t s) {
-    if (!buf) return hipSuccess;
-    hipEvent_t& e = uses[s];
-    if (!e)
-      if (const hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming)) return rc;
-    return hipEventRecord(e, s);
-  }
-  // s is released (pt_stream_release): its last read is waited for, so its event need not outlive the stream
-  void forget(hipStream_t s) {
-    auto u = uses.find(s);
-    if (u == uses.end()) return;
-    (void)hipEventSynchronize(u->second);
-    (void)hipEventDestroy(u->second);
-    uses.erase(u);
-  }
-  bool any() const { return buf || !spare.empty(); }
-  // drops every buffer and event (the caller has synchronised the streams that read them)
-  void free() {
-    if (buf) (void)hipFree(buf);
-    if (built) (void)hipEventDestroy(built);
-    for (auto& u : uses) (void)hipEventDestroy(u.second);
-    for (Retired& r : spare) {
-      (void)hipFree(r.buf);
-      if (r.built) (void)hipEventDestroy(r.built);
-      for (hipEvent_t e : r.readers) (void)hipEventDestroy(e);
-    }
-    *this = SharedBuf{};
-  }
-};
-
-// What the draw being issued reads of the shared buffers (pt_params, point_bins_for), noted on its stream after a
-// successful launch (note_reads). Local to the draw call, which holds g_mu throughout.
-struct DrawReads {
-  SharedBuf* hdr = nullptr;
-  SharedBuf* pbins = nullptr;
-};
-
-// The point-light triangle bins of a scene (ptk::PointBinsDev, kernels_pointbins.hip) for the lights texture a
-// path-tracing draw bound: built on the device by the first such draw, rebuilt when the scene's triangles or tree, the
-// lights texture (handle, device memory, version), pointLightSize, R or the binning (point_bins_tight) change. Read
-// by the path tracers of every frame
-// in flight on other streams: a SharedBuf.
 // cells per cube-face edge (uniform point_bins_r overrides: A/B). 128 since the lists hold 8-byte entries of the
 // polygon's cells only: its lists are smaller than the 64's were before, and it measured faster
 constexpr int kPointBinsR = 128;
-struct PointBinsGPU {
-  SharedBuf sb;
-  ptk::PointBinsDev dev{};
-  uint64_t tri_ver = 0, node_ver = 0, light_ver = 0;
-  uint32_t light_handle = 0;
-  const void* light_dev = nullptr;
-  int nl = 0, R = 0, ntris = 0, tight = 0;
-};
 // drops a scene's point-light bins (the caller has synchronised the streams that read them)
 void free_point_bins(PointBinsGPU& m) {
   m.sb.free();
   m = PointBinsGPU{};
 }
 
-struct SceneGPU {
-  PointBinsGPU pbins;
-  float4* geom = nullptr;
-  float4* shade = nullptr;
-  float4* bvh = nullptr;
-  float4* bvh4 = nullptr;
-  float4* bvh_any = nullptr;  // any-hit tree over the reference leaves (build_anyhit_tree)
-  float4* leaves = nullptr;   // the reference leaves: (box lo, leaf ref bits), (box hi, 0) (wf_primary_raster)
-  int nleaves = 0;
-  int* tri_leaf = nullptr;    // per triangle: its reference leaf's index in `leaves` (wf_primary_tri); always owned
-  int tri_leaf_cap = 0;       // triangles tri_leaf has room for
-  bool tri_shared = false;    // host-built trees: some triangle lies in two leaves (upload_leaves)
-  int root_any = 0, need_any = 0;
-  bool has4 = false;  // bvh4: the 4-wide form of bvh_any (pack_wide)
-  bool nan4 = false;  // a child box of bvh4 has a NaN coordinate (PT_WIDE_SIGNED walks need lo <= hi: not walked)
-  // a scene pt_bvh_build wrote: bvh (== bvh_any), bvh4 and leaves belong to the node texture's LbvhTrees, not to this
-  bool lbvh = false;
-  int root4 = 0, need4 = 0, root4c = 0;  // root4c: the closest-hit walks' root (SceneDev::root4c)
-  // refine_leaves' fine boxes are padded for rays whose origin lies within kFineEyeReach x the scene's largest vertex
-  // coordinate; an eye further out (pt_params) walks the reference tree instead
-  float fine_eye_limit = INFINITY;
-  int stack_need = 0;
-  int root_ref = 0;
-  int ntris = 0;
-  uint64_t tri_ver = 0, node_ver = 0;
-};
-
-// The environment map with its importance cache's pdf channel beside it (PTParams::hdr_pdf): built on the device
-// when a path-tracing draw binds an hdrMap and an hdrCache of one size, rebuilt when either changes (versions), freed
-// with either texture. Read by the path tracers of every frame in flight on other streams: a SharedBuf of float4.
-struct HdrMerged {
-  SharedBuf sb;
-  const void *hdr_dev = nullptr, *cache_dev = nullptr;
-  uint64_t vh = 0, vc = 0;
-  int W = 0, H = 0;
-};
-
 // drops a merged environment: its buffers (the caller has synchronised the streams that read them) and events
 void free_hdr_merged(HdrMerged& m) {
   m.sb.free();
   m = HdrMerged{};
-}
-
-// Posed objects (pt_pose_create): the rest-pose lists on the device and what pt_pose_apply writes from them
-struct Pose {
-  int ntris = 0;               // Triangle_encoded records
-  float* tri_rest = nullptr;   // in the order of the build's tri_in
-  float* tri_posed = nullptr;  // staging: the posed list, pt_bvh_refit's tri_in
-  int rtris = 0;               // raster triangles (0: the pose serves the path tracer only)
-  float* r_rest = nullptr;
-  int* r_obj = nullptr;        // one object per raster triangle
-  float* r_list[2] = {nullptr, nullptr};  // posed raster lists; r_list[cur] is what the pass holds
-  int cur = 0;
-  float* mats_dev = nullptr;   // kPoseMaxObjects x kPoseMatFloats
-  float* mats_host = nullptr;  // pinned staging of the same size
-  float4* disp_spare = nullptr;  // displacement records taken off the pass by a pose without motion, for the next
-};
-constexpr int kPoseMaxObjects = 4096;
-
-void free_pose(Pose& p) {
-  float* dev[] = {p.tri_rest, p.tri_posed, p.r_rest, p.r_list[0], p.r_list[1], p.mats_dev};
-  for (float* d : dev)
-    if (d) (void)hipFree(d);
-  if (p.r_obj) (void)hipFree(p.r_obj);
-  if (p.disp_spare) (void)hipFree(p.disp_spare);
-  if (p.mats_host) (void)hipHostFree(p.mats_host);
-  p = Pose{};
-}
-
-struct Lib {
-  bool init = false;
-  int device = 0;
-  hipStream_t own = nullptr, stream = nullptr;
-  uint32_t next = 1;
-  std::map<uint32_t, int> programs;
-  std::map<uint32_t, std::unique_ptr<Texture>> textures;
-  std::map<uint32_t, std::unique_ptr<Pass>> passes;
-  std::map<uint32_t, std::unique_ptr<Pose>> poses;
-  std::map<std::pair<uint32_t, uint32_t>, SceneGPU> scenes;
-  std::map<std::pair<uint32_t, uint32_t>, HdrMerged> hdr_merged;  // keyed by (hdrMap, hdrCache) handles
-  std::map<hipStream_t, ptk::WfFork> forks;  // per draw stream: the path tracer's side stream (uniform trace_fork)
-  uint32_t unit0 = 0;  // GL texture unit 0 binding (global)
-  int band_w = 0, band_h = 0, band_y0 = 0, band_y1 = 0, band_row0 = 0, band_rows = 0;
-  bool profiling = false;
-};
-
-Lib g;
-thread_local std::string g_err;
-std::recursive_mutex g_mu;
-
-int err(int code, const std::string& m) {
-  g_err = m;
-  return code;
-}
-int hip_err(hipError_t e, const char* what) {
-  return err(PT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(x)                                    \
-  do {                                               \
-    hipError_t e_ = (x);                             \
-    if (e_ != hipSuccess) return hip_err(e_, #x);    \
-  } while (0)
-
-std::string basename_of(const char* p) {
-  std::string s(p ? p : "");
-  size_t k = s.find_last_of("/\\");
-  return k == std::string::npos ? s : s.substr(k + 1);
-}
-
-Texture* tex_of(uint32_t h) {
-  auto it = g.textures.find(h);
-  return it == g.textures.end() ? nullptr : it->second.get();
-}
-Pass* pass_of(uint32_t h) {
-  auto it = g.passes.find(h);
-  return it == g.passes.end() ? nullptr : it->second.get();
-}
-
-int ensure_init() {
-  if (g.init) return PT_OK;
-  return err(PT_ERR_STATE, "pt_init() has not been called");
 }
 
 constexpr int kLbvhWideDefault = 1;  // pass uniform lbvh_wide (pt_params)
@@ -533,6 +206,22 @@ void free_scene(SceneGPU& sg) {
   sg.tri_leaf_cap = 0;
 }
 
+// what a pass holds on the device (pt_pass_destroy, pt_shutdown: nothing in flight reads it)
+void free_pass(Pass* p) {
+  if (p->raster.geom) (void)hipFree(p->raster.geom);
+  if (p->raster.nrm) (void)hipFree(p->raster.nrm);
+  if (p->raster.disp) (void)hipFree(p->raster.disp);
+  if (p->raster.bvh) (void)hipFree(p->raster.bvh);
+  free_raster_refit(p->raster);
+  if (p->bins.base) (void)hipFree(p->bins.base);
+  if (p->wf.base) (void)hipFree(p->wf.base);
+  if (p->wf.spill) (void)hipFree(p->wf.spill);
+  if (p->order.cost) (void)hipFree(p->order.cost);
+  if (p->order.perm) (void)hipFree(p->order.perm);
+  if (p->ev0) (void)hipEventDestroy(p->ev0);
+  if (p->ev1) (void)hipEventDestroy(p->ev1);
+}
+
 // The triangle -> reference leaf map of a scene whose `leaves` were just built or rebuilt (on g.stream, after the
 // work that wrote them).
 static int build_tri_leaf(SceneGPU& sg, int ntris) {
@@ -546,25 +235,6 @@ static int build_tri_leaf(SceneGPU& sg, int ntris) {
   if (ntris <= 0) return PT_OK;
   const int rc = ptk::launch_tri_leaf_map(sg.leaves, sg.nleaves, sg.tri_leaf, ntris, g.stream);
   return rc ? hip_err((hipError_t)rc, "triangle leaf map") : PT_OK;
-}
-
-// the displacement records of a rasterize pass (pt_raster_pass_set_prev_vertices), freed once no draw reads them
-static void drop_disp(Pass* p) {
-  if (!p->raster.disp) return;
-  (void)hipDeviceSynchronize();
-  (void)hipFree(p->raster.disp);
-  p->raster.disp = nullptr;
-}
-
-// (T: the device type, or the host tree builder's Float4 for float4)
-template <class T, class D>
-int upload_vec(const std::vector<T>& v, D** dst) {
-  static_assert(sizeof(T) == sizeof(D), "upload_vec copies records as they are");
-  if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-  if (v.empty()) return PT_OK;
-  HIPCHK(hipMalloc((void**)dst, v.size() * sizeof(T)));
-  HIPCHK(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return PT_OK;
 }
 
 static int upload_leaves(const float* ne, size_t nnodes, SceneGPU& sg) {
@@ -587,18 +257,6 @@ static int upload_leaves(const float* ne, size_t nnodes, SceneGPU& sg) {
     }
   }
   return upload_vec(lv, &sg.leaves);
-}
-
-// The host mirror of a texbuffer pt_bvh_refit wrote in place is lazy: the refit pays no copy, and whoever reads
-// t->host's contents calls this first (pt_debug_lbvh_trees source 1, get_scene's host decode; pt_texture_readback
-// reads the device copy, and get_scene_lbvh only the sizes, which a refit keeps).
-int refresh_host(Texture* t) {
-  if (!t->host_stale) return PT_OK;
-  HIPCHK(hipDeviceSynchronize());
-  t->host.resize(t->bytes);
-  if (t->bytes) HIPCHK(hipMemcpy(t->host.data(), t->dev, t->bytes, hipMemcpyDeviceToHost));
-  t->host_stale = false;
-  return PT_OK;
 }
 
 // A scene pt_bvh_build wrote (dynamic scenes): its triangles are decoded on the device (decode_tris: the host
@@ -785,11 +443,6 @@ int att_plane(Pass* p, int k, Plane* out) {
   t->aux_valid = false;
   return PT_OK;
 }
-#define TRY(x)                    \
-  do {                            \
-    int rc_ = (x);                \
-    if (rc_ != PT_OK) return rc_; \
-  } while (0)
 
 // pt_set_band holds a partition of W x H frames: a band or stored rows that are not the whole frame
 bool band_partition(int W, int H) {
@@ -1574,29 +1227,6 @@ Uniform* set_u(uint32_t pass, const char* name, int type, int* rc) {
 }  // namespace
 
 // ================================================================= C ABI ===
-ptk::LbvhWork g_lbvh;  // GPU BVH builder scratch (grows, reused across rebuilds)
-
-// Replace a texbuffer's contents with `bytes` of device data (device + host copy), as a fresh upload would.
-static int texbuffer_take(Texture* t, const void* dev_src, size_t bytes) {
-  if (t->bytes != bytes || !t->dev) {
-    if (t->owned && t->dev) (void)hipFree(t->dev);
-    t->dev = nullptr;
-    if (bytes) HIPCHK(hipMalloc(&t->dev, bytes));
-    t->owned = true;
-  }
-  t->bytes = bytes;
-  t->W = (int)(bytes / 12);
-  t->host.resize(bytes);
-  if (bytes) {
-    HIPCHK(hipMemcpyAsync(t->dev, dev_src, bytes, hipMemcpyDeviceToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(t->host.data(), dev_src, bytes, hipMemcpyDeviceToHost, g.stream));
-  }
-  t->version++;
-  t->lbvh = true;
-  t->host_stale = false;
-  return PT_OK;
-}
-
 extern "C" {
 
 int pt_tree_check(const float* node_enc, int nnodes, const float* tri_enc, int ntris, int collapse, int treelet,
@@ -1645,21 +1275,7 @@ int pt_shutdown(void) {
     free_trees(t);
     free_refit(t);
   }
-  for (auto& kv : g.passes) {
-    Pass* p = kv.second.get();
-    if (p->raster.geom) (void)hipFree(p->raster.geom);
-    if (p->raster.nrm) (void)hipFree(p->raster.nrm);
-    if (p->raster.disp) (void)hipFree(p->raster.disp);
-    if (p->raster.bvh) (void)hipFree(p->raster.bvh);
-    free_raster_refit(p->raster);
-    if (p->bins.base) (void)hipFree(p->bins.base);
-    if (p->wf.base) (void)hipFree(p->wf.base);
-    if (p->wf.spill) (void)hipFree(p->wf.spill);
-    if (p->order.cost) (void)hipFree(p->order.cost);
-    if (p->order.perm) (void)hipFree(p->order.perm);
-    if (p->ev0) (void)hipEventDestroy(p->ev0);
-    if (p->ev1) (void)hipEventDestroy(p->ev1);
-  }
+  for (auto& kv : g.passes) free_pass(kv.second.get());
   for (auto& kv : g.poses) free_pose(*kv.second);
   for (auto& kv : g.scenes) free_scene(kv.second);
   for (auto& kv : g.hdr_merged) free_hdr_merged(kv.second);
@@ -1915,155 +1531,6 @@ int pt_texbuffer_create(const void* data, size_t bytes, uint32_t fmt, uint32_t* 
   return new_texture(std::move(t), out);
 }
 
-int pt_bvh_build(uint32_t tri_in, int leaf_n, int ploc_radius, uint32_t tri_out, uint32_t node_out, int* out_nodes,
-                 float* out_ms) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  Texture *ti = tex_of(tri_in), *to = tex_of(tri_out), *no = tex_of(node_out);
-  if (!ti || !to || !no || ti->target != PT_TEXTURE_BUFFER || to->target != PT_TEXTURE_BUFFER ||
-      no->target != PT_TEXTURE_BUFFER)
-    return err(PT_ERR_ARG, "pt_bvh_build: tri_in, tri_out and node_out must be texture buffers");
-  if (tri_in == tri_out || tri_in == node_out || tri_out == node_out)
-    return err(PT_ERR_ARG, "pt_bvh_build: tri_in, tri_out and node_out must be three different buffers");
-  if (leaf_n < 1 || leaf_n > 15) return err(PT_ERR_ARG, "pt_bvh_build: leaf_n must be in [1, 15]");
-  if (ploc_radius < 0 || ploc_radius > 256) return err(PT_ERR_ARG, "pt_bvh_build: ploc_radius must be in [0, 256]");
-  if (ti->bytes == 0 || ti->bytes % (45 * sizeof(float)) || !ti->dev)
-    return err(PT_ERR_FORMAT, "pt_bvh_build: tri_in must hold whole Triangle_encoded records (45 floats)");
-  const size_t nt = ti->bytes / (45 * sizeof(float));
-  if (nt > (1u << 24)) return err(PT_ERR_ARG, "pt_bvh_build: more than 2^24 triangles (float-encoded indices)");
-  const int n = (int)nt;
-  float *tbuf = nullptr, *nbuf = nullptr;
-  HIPCHK(hipMalloc(&tbuf, nt * 45 * sizeof(float)));
-  if (hipMalloc(&nbuf, (size_t)2 * n * 12 * sizeof(float)) != hipSuccess) {
-    (void)hipFree(tbuf);
-    return err(PT_ERR_HIP, "pt_bvh_build: out of device memory");
-  }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (out_ms) {
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, g.stream);
-  }
-  int nodes = 0;
-  // what a later pt_bvh_refit needs is kept with the node texture: the leaf order the build writes and the parent
-  // links of its output nodes (the allocation of the previous build is reused while the triangle count holds)
-  if (!no->refit) no->refit = new ptk::LbvhRefit;
-  int rc = ptk::lbvh_refit_alloc(*no->refit, n);
-  if (rc == 0)
-    rc = ptk::lbvh_build(g_lbvh, (const float*)ti->dev, ptk::kTriEncoded, n, leaf_n, ploc_radius, tbuf, nbuf,
-                         no->refit->order, &nodes, g.stream);
-  if (rc == 0) rc = ptk::lbvh_refit_link(*no->refit, nbuf, nodes, g.stream);
-  // the walk trees of the new nodes, derived where they lie; their counters arrive with the final sync below
-  std::unique_ptr<ptk::LbvhTrees> trees(new ptk::LbvhTrees);
-  int trc = rc == 0 ? ptk::lbvh_trees_launch(g_lbvh, nbuf, nodes, *trees, g.stream) : 0;
-  if (out_ms) {
-    (void)hipEventRecord(e1, g.stream);
-    (void)hipEventSynchronize(e1);
-    (void)hipEventElapsedTime(out_ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
-  if (rc == 0) rc = texbuffer_take(to, tbuf, nt * 45 * sizeof(float));
-  else rc = hip_err((hipError_t)rc, "lbvh_build");
-  if (rc == PT_OK) rc = texbuffer_take(no, nbuf, (size_t)nodes * 12 * sizeof(float));
-  {  // also after a failure: the stage's counters are copied into `trees`
-    hipError_t e = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess && rc == PT_OK) rc = hip_err(e, "pt_bvh_build");
-  }
-  if (rc == PT_OK && trc == 0) trc = ptk::lbvh_trees_finish(*trees);
-  if (rc == PT_OK && trc != 0) rc = err(PT_ERR_HIP, "pt_bvh_build: deriving the walk trees failed");
-  if (no->trees && no->trees->version != no->version) free_trees(no);  // the replaced contents' trees
-  if (rc == PT_OK) {
-    trees->version = no->version;
-    no->trees = trees.release();
-    no->refit_tri = tri_out;
-    no->refit_tri_ver = to->version;
-    no->refit_node_ver = no->version;
-  } else {
-    ptk::lbvh_trees_free(*trees);
-    free_refit(no);
-  }
-  (void)hipFree(tbuf);
-  (void)hipFree(nbuf);
-  if (rc == PT_OK && out_nodes) *out_nodes = nodes;
-  return rc;
-}
-
-int pt_bvh_refit(uint32_t tri_in, uint32_t tri_out, uint32_t node_out, float* out_ms) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  Texture *ti = tex_of(tri_in), *to = tex_of(tri_out), *no = tex_of(node_out);
-  if (!ti || !to || !no || ti->target != PT_TEXTURE_BUFFER || to->target != PT_TEXTURE_BUFFER ||
-      no->target != PT_TEXTURE_BUFFER)
-    return err(PT_ERR_ARG, "pt_bvh_refit: tri_in, tri_out and node_out must be texture buffers");
-  if (tri_in == tri_out || tri_in == node_out || tri_out == node_out)
-    return err(PT_ERR_ARG, "pt_bvh_refit: tri_in, tri_out and node_out must be three different buffers");
-  ptk::LbvhRefit* rf = no->refit;
-  if (!to->lbvh || !no->lbvh || !rf || !rf->base || rf->nnodes < 2 || !no->trees || no->refit_tri != tri_out ||
-      no->refit_tri_ver != to->version || no->refit_node_ver != no->version || no->trees->version != no->version ||
-      !to->dev || !no->dev || to->bytes != (size_t)rf->n * 45 * sizeof(float) ||
-      no->bytes != (size_t)rf->nnodes * 12 * sizeof(float))
-    return err(PT_ERR_STATE, "pt_bvh_refit: tri_out and node_out are not the untouched pair of one pt_bvh_build");
-  if (ti->bytes == 0 || ti->bytes % (45 * sizeof(float)) || !ti->dev)
-    return err(PT_ERR_ARG, "pt_bvh_refit: tri_in must hold whole Triangle_encoded records (45 floats)");
-  if (ti->bytes != to->bytes) return err(PT_ERR_ARG, "pt_bvh_refit: tri_in holds another triangle count than the build");
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (out_ms) {
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, g.stream);
-  }
-  // both buffers are written where they lie: no staging, no copy (the host mirrors turn lazy, refresh_host)
-  int rc = ptk::lbvh_refit_reorder(*rf, (const float*)ti->dev, (float*)to->dev, g.stream);
-  if (rc == 0) rc = ptk::lbvh_refit_nodes(*rf, (float*)no->dev, (const float*)ti->dev, ptk::kTriEncoded, g.stream);
-  std::unique_ptr<ptk::LbvhTrees> trees(new ptk::LbvhTrees);
-  int trc = rc == 0 ? ptk::lbvh_trees_launch(g_lbvh, (const float*)no->dev, rf->nnodes, *trees, g.stream, rf->err) : 0;
-  if (out_ms) {
-    (void)hipEventRecord(e1, g.stream);
-    (void)hipEventSynchronize(e1);
-    (void)hipEventElapsedTime(out_ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
-  rc = rc == 0 ? PT_OK : hip_err((hipError_t)rc, "pt_bvh_refit");
-  {  // also after a failure: the stage's counters are copied into `trees`
-    hipError_t e = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess && rc == PT_OK) rc = hip_err(e, "pt_bvh_refit");
-  }
-  if (rc == PT_OK && trc == 0) trc = ptk::lbvh_trees_finish(*trees);
-  if (rc == PT_OK && trc != 0) rc = err(PT_ERR_HIP, "pt_bvh_refit: deriving the walk trees failed");
-  // the contents changed whatever came of it: the old trees go, and every consumer re-reads
-  to->version++;
-  no->version++;
-  to->host_stale = no->host_stale = true;
-  free_trees(no);
-  if (rc == PT_OK) {
-    trees->version = no->version;
-    no->trees = trees.release();
-    no->refit_tri_ver = to->version;
-    no->refit_node_ver = no->version;
-  } else {
-    ptk::lbvh_trees_free(*trees);
-    free_refit(no);
-  }
-  return rc;
-}
-
-int pt_debug_lbvh_order(uint32_t node_tex, int* host_out, size_t cap, size_t* n) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  Texture* t = tex_of(node_tex);
-  if (!t || t->target != PT_TEXTURE_BUFFER) return err(PT_ERR_INVALID_HANDLE, "pt_debug_lbvh_order: not a texture buffer");
-  if (!t->lbvh || !t->refit || !t->refit->base || t->refit_node_ver != t->version)
-    return err(PT_ERR_STATE, "pt_debug_lbvh_order: not a node buffer pt_bvh_build wrote");
-  if (n) *n = (size_t)t->refit->n;
-  if (!host_out) return PT_OK;
-  if (cap < (size_t)t->refit->n) return err(PT_ERR_ARG, "pt_debug_lbvh_order: host_out is too small");
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host_out, t->refit->order, sizeof(int) * (size_t)t->refit->n, hipMemcpyDeviceToHost));
-  return PT_OK;
-}
-
 int pt_texture_readback_aux(uint32_t tex, float* host_out, size_t cap, size_t* bytes) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   TRY(ensure_init());
@@ -2075,51 +1542,6 @@ int pt_texture_readback_aux(uint32_t tex, float* host_out, size_t cap, size_t* b
   if (cap < *bytes) return err(PT_ERR_ARG, "aux buffer too small");
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(host_out, t->aux, *bytes, hipMemcpyDeviceToHost));
-  return PT_OK;
-}
-
-int pt_debug_lbvh_trees(uint32_t node_tex, int source, int which, void* host_out, size_t cap, size_t* bytes,
-                        int* info8) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  Texture* t = tex_of(node_tex);
-  if (!t || t->target != PT_TEXTURE_BUFFER) return err(PT_ERR_INVALID_HANDLE, "pt_debug_lbvh_trees: not a texture buffer");
-  if (!t->lbvh || !t->trees || t->trees->version != t->version)
-    return err(PT_ERR_STATE, "pt_debug_lbvh_trees: not a node buffer pt_bvh_build wrote");
-  if (source < 0 || source > 1 || which < 0 || which > 2) return err(PT_ERR_ARG, "pt_debug_lbvh_trees: source 0-1, which 0-2");
-  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  std::vector<Float4> host;
-  const void* src = nullptr;
-  size_t n = 0;
-  if (source == 0) {
-    const ptk::LbvhTrees& tr = *t->trees;
-    for (int i = 0; i < 7; ++i) info[i] = tr.dev_info[i];
-    info[7] = (int)lrintf(tr.stage_ms * 1000.0f);
-    src = which == 0 ? tr.bin : which == 1 ? tr.leaves : tr.wide;
-    n = which == 0 ? (size_t)tr.nbin() * 4 : which == 1 ? (size_t)tr.nleaves() * 2 : (size_t)tr.nwide() * ptk::kWideStride;
-  } else {
-    // the host functions over the host mirror of the texels: what the device stage has to equal
-    TRY(refresh_host(t));
-    const float* ne = (const float*)t->host.data();
-    const int nnodes = (int)(t->host.size() / (12 * sizeof(float)));
-    std::vector<Float4> bin, leaves, wide;
-    std::string msg;
-    if (const int rc = pack_bvh(ne, nnodes, bin, &info[0], (1 << 24) + 15, &info[1], &msg)) return err(rc, msg);
-    collect_leaves(ne, (size_t)nnodes, leaves);
-    info[2] = (int)(leaves.size() / 2);
-    TRY(pack_wide_encoded(ne, nnodes, wide, &info[3], &info[4]));
-    info[5] = (int)(wide.size() / ptk::kWideStride);
-    info[6] = wide_has_nan(wide);
-    host.swap(which == 0 ? bin : which == 1 ? leaves : wide);
-    n = host.size();
-  }
-  if (bytes) *bytes = n * sizeof(float4);
-  if (info8) memcpy(info8, info, sizeof(info));
-  if (host_out && n) {
-    if (cap < n * sizeof(float4)) return err(PT_ERR_ARG, "pt_debug_lbvh_trees: host_out is too small");
-    if (source == 0) HIPCHK(hipMemcpy(host_out, src, n * sizeof(float4), hipMemcpyDeviceToHost));
-    else memcpy(host_out, host.data(), n * sizeof(float4));
-  }
   return PT_OK;
 }
 
@@ -2283,449 +1705,6 @@ int pt_pass_bind(uint32_t pass, int final_pass) {
   if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
   p->bound = true;
   p->final_pass = final_pass != 0;
-  return PT_OK;
-}
-
-int pt_raster_pass_bind(uint32_t pass, const float* verts, size_t n_floats) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (g.programs[p->program] != PK_RASTER) return err(PT_ERR_ARG, "not a rasterize pass");
-  if (n_floats % 18) return err(PT_ERR_ARG, "vertex list must be whole triangles of pos3+nrm3");
-  int ntris = (int)(n_floats / 18);
-  drop_disp(p);  // the triangle order changes
-  free_raster_refit(p->raster);  // a host-built tree is not refitted
-  p->raster.ntris = ntris;
-  p->raster_src = 0;
-  p->bound = true;
-  if (ntris == 0) return PT_OK;
-  // SAH tree over the raster triangles (build_raster_tree: the walk's answer does not depend on the tree);
-  // geom in leaf order, objIndex = original index (the depth-test tie rule)
-  std::vector<int> order;
-  std::vector<Float4> bvh;
-  int root = 0;
-  std::string msg;
-  if (const int rc = build_raster_tree(verts, ntris, order, bvh, &root, &p->raster.stack_need, &msg))
-    return err(rc, msg);
-  using namespace glsl;
-  std::vector<float4> geom((size_t)ntris * 4), nrm((size_t)ntris * 3);
-  for (int k = 0; k < ntris; ++k) {
-    const int oi = order[k];
-    const float* f = verts + (size_t)oi * 18;
-    v3 p1 = mk(f[0], f[1], f[2]), p2 = mk(f[6], f[7], f[8]), p3 = mk(f[12], f[13], f[14]);
-    v3 e1 = sub(p2, p1), e2 = sub(p3, p1), ng = cross(e1, e2);
-    float oif;
-    memcpy(&oif, &oi, 4);
-    float4* q = &geom[(size_t)k * 4];
-    q[0] = float4{p1.x, p1.y, p1.z, oif};
-    q[1] = float4{e1.x, e1.y, e1.z, 0};
-    q[2] = float4{e2.x, e2.y, e2.z, 0};
-    q[3] = float4{ng.x, ng.y, ng.z, 0};
-    float4* n = &nrm[(size_t)k * 3];
-    n[0] = float4{f[3], f[4], f[5], 0};
-    n[1] = float4{f[9], f[10], f[11], 0};
-    n[2] = float4{f[15], f[16], f[17], 0};
-  }
-  if (bvh.empty()) bvh.push_back(Float4{0, 0, 0, 0});
-  TRY(upload_vec(geom, &p->raster.geom));
-  TRY(upload_vec(nrm, &p->raster.nrm));
-  TRY(upload_vec(bvh, &p->raster.bvh));
-  p->raster.root_ref = root;
-  return PT_OK;
-}
-
-int pt_raster_pass_bind_device(uint32_t pass, const void* dverts, size_t n_floats, int ploc_radius) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (g.programs[p->program] != PK_RASTER) return err(PT_ERR_ARG, "not a rasterize pass");
-  if (n_floats % 18) return err(PT_ERR_ARG, "vertex list must be whole triangles of pos3+nrm3");
-  if (ploc_radius < 0 || ploc_radius > 256) return err(PT_ERR_ARG, "ploc_radius must be in [0, 256]");
-  if (n_floats / 18 > (1u << 24)) return err(PT_ERR_ARG, "more than 2^24 raster triangles");
-  const int ntris = (int)(n_floats / 18);
-  if (ntris > 0 && !dverts) return err(PT_ERR_ARG, "null device vertex list");
-  drop_disp(p);  // the triangle order changes
-  p->raster.ntris = ntris;
-  p->raster_src = 0;
-  p->bound = true;
-  free_raster_refit(p->raster);  // of the bind this one replaces
-  if (ntris == 0) return PT_OK;
-  float* nbuf = nullptr;
-  // the encoded nodes, the leaf order and the parent links stay with the pass after a device bind
-  // (pt_raster_pass_refit_device)
-  std::unique_ptr<ptk::LbvhRefit> rf(new ptk::LbvhRefit);
-  HIPCHK(hipMalloc(&nbuf, (size_t)2 * ntris * 12 * sizeof(float)));
-  if (ptk::lbvh_refit_alloc(*rf, ntris) != 0) {
-    (void)hipFree(nbuf);
-    return err(PT_ERR_HIP, "pt_raster_pass_bind_device: out of device memory");
-  }
-  const int* order = rf->order;
-  bool keep = false;
-  auto release = [&]() {
-    if (keep) return;
-    (void)hipFree(nbuf);
-    ptk::lbvh_refit_free(*rf);
-  };
-  int nodes = 0;
-  int rc = ptk::lbvh_build(g_lbvh, (const float*)dverts, ptk::kRasterVerts, ntris, 8, ploc_radius, nullptr, nbuf,
-                           rf->order, &nodes, g.stream);
-  if (rc == 0) rc = ptk::lbvh_refit_link(*rf, nbuf, nodes, g.stream);
-  if (rc) { release(); return hip_err((hipError_t)rc, "raster lbvh_build"); }
-  // the packed binary tree (pack_bvh's records) and its depth come from the device stage: no node readback
-  ptk::LbvhTrees trees;
-  rc = ptk::lbvh_trees_launch(g_lbvh, nbuf, nodes, trees, g.stream);
-  if (hipStreamSynchronize(g.stream) != hipSuccess && rc == 0) rc = (int)hipErrorUnknown;
-  if (rc == 0) rc = ptk::lbvh_trees_finish(trees);
-  auto release_trees = [&]() { ptk::lbvh_trees_free(trees); };
-  const int root = trees.dev_info[0], need = trees.dev_info[1];
-  if (rc != 0 || need >= kStack) {
-    release_trees();
-    // the G-buffer walk's stack holds kStack entries: a deeper device tree (coincident centroids) takes the host
-    // bind, whose SAH builder caps the depth; the G-buffer does not depend on the tree
-    std::vector<float> hv(n_floats);
-    const bool ok = hipMemcpy(hv.data(), dverts, n_floats * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
-    release();
-    if (!ok) return err(PT_ERR_HIP, "pt_raster_pass_bind_device: vertex readback");
-    return pt_raster_pass_bind(pass, hv.data(), n_floats);
-  }
-  if (p->raster.geom) (void)hipFree(p->raster.geom);
-  if (p->raster.nrm) (void)hipFree(p->raster.nrm);
-  p->raster.geom = p->raster.nrm = nullptr;
-  if (hipMalloc((void**)&p->raster.geom, (size_t)ntris * 4 * sizeof(float4)) != hipSuccess ||
-      hipMalloc((void**)&p->raster.nrm, (size_t)ntris * 3 * sizeof(float4)) != hipSuccess) {
-    release();
-    release_trees();
-    return err(PT_ERR_HIP, "pt_raster_pass_bind_device: out of device memory");
-  }
-  rc = ptk::decode_raster((const float*)dverts, order, ntris, p->raster.geom, p->raster.nrm, g.stream);
-  if (rc) { release(); release_trees(); return hip_err((hipError_t)rc, "decode_raster"); }
-  // the pass owns a copy sized to the tree (an empty tree: one zero record, as the host bind uploads)
-  const size_t bvh_bytes = (size_t)std::max(1, trees.nbin()) * 4 * sizeof(float4);
-  if (p->raster.bvh) { (void)hipFree(p->raster.bvh); p->raster.bvh = nullptr; }
-  if (hipMalloc((void**)&p->raster.bvh, bvh_bytes) != hipSuccess ||
-      hipMemcpyAsync(p->raster.bvh, trees.bin, bvh_bytes, hipMemcpyDeviceToDevice, g.stream) != hipSuccess) {
-    release();
-    release_trees();
-    return err(PT_ERR_HIP, "pt_raster_pass_bind_device: out of device memory");
-  }
-  p->raster.root_ref = root;
-  p->raster.stack_need = need;
-  // draws of other frames may run on other streams: the records are complete when this returns
-  const hipError_t e = hipStreamSynchronize(g.stream);
-  if (e == hipSuccess) {
-    p->raster.enc_nodes = nbuf;
-    p->raster.refit = rf.release();
-    p->raster.bvh_records = std::max(1, trees.nbin());
-    keep = true;
-  }
-  release();
-  release_trees();
-  if (e != hipSuccess) return hip_err(e, "pt_raster_pass_bind_device");
-  return PT_OK;
-}
-
-int pt_raster_pass_refit_device(uint32_t pass, const void* dverts, size_t n_floats) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (g.programs[p->program] != PK_RASTER) return err(PT_ERR_ARG, "not a rasterize pass");
-  if (p->raster_src) return err(PT_ERR_ARG, "pt_raster_pass_refit_device: the pass shares another pass's triangles");
-  RasterScene& rs = p->raster;
-  if (!p->bound || !rs.refit || !rs.refit->base || !rs.enc_nodes || !rs.geom || !rs.nrm || !rs.bvh ||
-      rs.refit->n != rs.ntris)
-    return err(PT_ERR_STATE, "pt_raster_pass_refit_device: the pass was not bound by pt_raster_pass_bind_device "
-                             "(or took its host fallback): bind again");
-  if (n_floats != (size_t)rs.ntris * 18)
-    return err(PT_ERR_ARG, "pt_raster_pass_refit_device: not the bound triangle count");
-  if (!dverts) return err(PT_ERR_ARG, "null device vertex list");
-  drop_disp(p);  // their values are stale
-  ptk::LbvhRefit& rf = *rs.refit;
-  // records in the kept leaf order (the original index in geom[4k].w stays), boxes of the kept nodes, then the
-  // packed tree from the device stage as in the bind; its size is the bind's (same topology): copied in place
-  int rc = ptk::decode_raster((const float*)dverts, rf.order, rs.ntris, rs.geom, rs.nrm, g.stream);
-  if (rc == 0) rc = ptk::lbvh_refit_nodes(rf, rs.enc_nodes, (const float*)dverts, ptk::kRasterVerts, g.stream);
-  ptk::LbvhTrees trees;
-  if (rc == 0) rc = ptk::lbvh_trees_launch(g_lbvh, rs.enc_nodes, rf.nnodes, trees, g.stream, rf.err);
-  if (hipStreamSynchronize(g.stream) != hipSuccess && rc == 0) rc = (int)hipErrorUnknown;
-  if (rc == 0) rc = ptk::lbvh_trees_finish(trees);
-  if (rc == 0 && (trees.dev_info[1] != rs.stack_need || std::max(1, trees.nbin()) != rs.bvh_records))
-    rc = (int)hipErrorInvalidValue;  // the topology is the bind's: the same depth and as many records
-  if (rc == 0) {
-    const size_t bvh_bytes = (size_t)std::max(1, trees.nbin()) * 4 * sizeof(float4);
-    rc = (int)hipMemcpyAsync(rs.bvh, trees.bin, bvh_bytes, hipMemcpyDeviceToDevice, g.stream);
-    rs.root_ref = trees.dev_info[0];
-    // draws of other frames may run on other streams: the records are complete when this returns
-    if (rc == 0) rc = (int)hipStreamSynchronize(g.stream);
-  }
-  ptk::lbvh_trees_free(trees);
-  if (rc != 0) {
-    free_raster_refit(rs);  // the records may be half written: the caller binds again
-    return hip_err((hipError_t)rc, "pt_raster_pass_refit_device");
-  }
-  return PT_OK;
-}
-
-int pt_raster_pass_set_prev_vertices(uint32_t pass, const void* dprev, const void* dcur, size_t n_floats) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (g.programs[p->program] != PK_RASTER) return err(PT_ERR_ARG, "not a rasterize pass");
-  if (p->raster_src) return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: the pass shares another pass's triangles");
-  if (!p->bound) return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: raster pass not bound");
-  if (!dprev) {
-    drop_disp(p);
-    return PT_OK;
-  }
-  if (n_floats != (size_t)p->raster.ntris * 18)
-    return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: not the bound triangle count");
-  if (!dcur) return err(PT_ERR_ARG, "null device vertex list");
-  drop_disp(p);
-  const int ntris = p->raster.ntris;
-  if (ntris == 0) return PT_OK;
-  if (!p->raster.geom) return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: raster pass not bound");
-  float4* disp = nullptr;
-  HIPCHK(hipMalloc((void**)&disp, (size_t)ntris * 3 * sizeof(float4)));
-  const int rc = ptk::raster_disp(p->raster.geom, (const float*)dprev, (const float*)dcur, ntris, disp, g.stream);
-  // draws of other frames may run on other streams: the records are complete when this returns
-  const hipError_t e = rc ? (hipError_t)rc : hipStreamSynchronize(g.stream);
-  if (e != hipSuccess) {
-    (void)hipFree(disp);
-    return hip_err(e, "pt_raster_pass_set_prev_vertices");
-  }
-  p->raster.disp = disp;
-  return PT_OK;
-}
-
-int pt_pose_create(uint32_t tri_rest, const float* raster_rest, size_t n_floats, const int* raster_obj,
-                   uint32_t* out_pose) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  if (!out_pose) return err(PT_ERR_ARG, "pt_pose_create: null out_pose");
-  Texture* t = tex_of(tri_rest);
-  if (!t || t->target != PT_TEXTURE_BUFFER) return err(PT_ERR_ARG, "pt_pose_create: tri_rest must be a texture buffer");
-  if (t->bytes == 0 || t->bytes % (45 * sizeof(float)) || !t->dev)
-    return err(PT_ERR_ARG, "pt_pose_create: tri_rest must hold whole Triangle_encoded records (45 floats)");
-  const size_t nt = t->bytes / (45 * sizeof(float));
-  if (nt > (1u << 24)) return err(PT_ERR_ARG, "pt_pose_create: more than 2^24 triangles");
-  if (n_floats % 18) return err(PT_ERR_ARG, "pt_pose_create: the raster list must be whole triangles of pos3+nrm3");
-  if (n_floats / 18 > (1u << 24)) return err(PT_ERR_ARG, "pt_pose_create: more than 2^24 raster triangles");
-  if (n_floats && (!raster_rest || !raster_obj))
-    return err(PT_ERR_ARG, "pt_pose_create: a raster list needs its vertices and one object per triangle");
-  std::unique_ptr<Pose> ps(new Pose);
-  ps->ntris = (int)nt;
-  ps->rtris = (int)(n_floats / 18);
-  const size_t rbytes = n_floats * sizeof(float), mbytes = (size_t)kPoseMaxObjects * ptk::kPoseMatFloats * sizeof(float);
-  hipError_t e = hipMalloc((void**)&ps->tri_rest, t->bytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&ps->tri_posed, t->bytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&ps->mats_dev, mbytes);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&ps->mats_host, mbytes, hipHostMallocDefault);
-  if (e == hipSuccess && ps->rtris) {
-    e = hipMalloc((void**)&ps->r_rest, rbytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&ps->r_list[0], rbytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&ps->r_list[1], rbytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&ps->r_obj, (size_t)ps->rtris * sizeof(int));
-  }
-  // on the library stream: tri_rest may have been written there
-  if (e == hipSuccess) e = hipMemcpyAsync(ps->tri_rest, t->dev, t->bytes, hipMemcpyDeviceToDevice, g.stream);
-  if (e == hipSuccess && ps->rtris) {
-    e = hipMemcpyAsync(ps->r_rest, raster_rest, rbytes, hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(ps->r_obj, raster_obj, (size_t)ps->rtris * sizeof(int), hipMemcpyHostToDevice, g.stream);
-    for (int k = 0; k < 2 && e == hipSuccess; ++k)
-      e = hipMemcpyAsync(ps->r_list[k], ps->r_rest, rbytes, hipMemcpyDeviceToDevice, g.stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-  if (e != hipSuccess) {
-    free_pose(*ps);
-    return hip_err(e, "pt_pose_create");
-  }
-  const uint32_t h = g.next++;
-  g.poses[h] = std::move(ps);
-  *out_pose = h;
-  return PT_OK;
-}
-
-int pt_pose_destroy(uint32_t pose) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  auto it = g.poses.find(pose);
-  if (it == g.poses.end()) return err(PT_ERR_INVALID_HANDLE, "pt_pose_destroy: unknown pose");
-  (void)hipDeviceSynchronize();  // a pt_pose_apply has completed; nothing else reads the lists
-  free_pose(*it->second);
-  g.poses.erase(it);
-  return PT_OK;
-}
-
-int pt_pose_apply(uint32_t pose, const float* mats16, int n_obj, uint32_t tri_out, uint32_t node_out,
-                  uint32_t raster_pass, int motion, float* out_ms) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  auto pit = g.poses.find(pose);
-  if (pit == g.poses.end()) return err(PT_ERR_INVALID_HANDLE, "pt_pose_apply: unknown pose");
-  Pose& ps = *pit->second;
-  if (!mats16) return err(PT_ERR_ARG, "pt_pose_apply: null mats16");
-  if (n_obj < 1 || n_obj > kPoseMaxObjects) return err(PT_ERR_ARG, "pt_pose_apply: n_obj must be in [1, 4096]");
-  // the pair: pt_bvh_refit's checks, the posed list standing for tri_in
-  Texture *to = tex_of(tri_out), *no = tex_of(node_out);
-  if (!to || !no || to->target != PT_TEXTURE_BUFFER || no->target != PT_TEXTURE_BUFFER)
-    return err(PT_ERR_ARG, "pt_pose_apply: tri_out and node_out must be texture buffers");
-  if (tri_out == node_out) return err(PT_ERR_ARG, "pt_pose_apply: tri_out and node_out must be two different buffers");
-  ptk::LbvhRefit* rf = no->refit;
-  if (!to->lbvh || !no->lbvh || !rf || !rf->base || rf->nnodes < 2 || !no->trees || no->refit_tri != tri_out ||
-      no->refit_tri_ver != to->version || no->refit_node_ver != no->version || no->trees->version != no->version ||
-      !to->dev || !no->dev || to->bytes != (size_t)rf->n * 45 * sizeof(float) ||
-      no->bytes != (size_t)rf->nnodes * 12 * sizeof(float))
-    return err(PT_ERR_STATE, "pt_pose_apply: tri_out and node_out are not the untouched pair of one pt_bvh_build");
-  if (rf->n != ps.ntris) return err(PT_ERR_ARG, "pt_pose_apply: the pose holds another triangle count than the build");
-  // the pass: pt_raster_pass_refit_device's checks
-  Pass* p = nullptr;
-  if (raster_pass) {
-    if (!ps.rtris) return err(PT_ERR_ARG, "pt_pose_apply: the pose was created without a raster list");
-    p = pass_of(raster_pass);
-    if (!p) return err(PT_ERR_INVALID_HANDLE, "pt_pose_apply: invalid pass");
-    if (g.programs[p->program] != PK_RASTER) return err(PT_ERR_ARG, "pt_pose_apply: not a rasterize pass");
-    if (p->raster_src) return err(PT_ERR_ARG, "pt_pose_apply: the pass shares another pass's triangles");
-    const RasterScene& rs = p->raster;
-    if (!p->bound || !rs.refit || !rs.refit->base || !rs.enc_nodes || !rs.geom || !rs.nrm || !rs.bvh ||
-        rs.refit->n != rs.ntris || rs.bvh_records < 1)
-      return err(PT_ERR_STATE, "pt_pose_apply: the pass was not bound by pt_raster_pass_bind_device (or took its "
-                               "host fallback): bind again");
-    if (rs.ntris != ps.rtris) return err(PT_ERR_ARG, "pt_pose_apply: the pose holds another raster triangle count");
-  }
-  // displacement records: the pass's own are rewritten where they lie, else the pair a pose without motion set aside
-  float4* disp = nullptr;
-  if (p && motion) {
-    disp = p->raster.disp ? p->raster.disp : ps.disp_spare;
-    if (!disp && hipMalloc((void**)&disp, (size_t)ps.rtris * 3 * sizeof(float4)) != hipSuccess)
-      return err(PT_ERR_HIP, "pt_pose_apply: out of device memory");
-    if (disp == ps.disp_spare) ps.disp_spare = nullptr;
-  }
-  // the table: each matrix with the cofactor columns of its upper 3x3 (cross products of its columns), once per object
-  for (int k = 0; k < n_obj; ++k) {
-    const float* m = mats16 + (size_t)k * 16;
-    float* o = ps.mats_host + (size_t)k * ptk::kPoseMatFloats;
-    memcpy(o, m, 16 * sizeof(float));
-    const glsl::v3 c0 = glsl::mk(m[0], m[1], m[2]), c1 = glsl::mk(m[4], m[5], m[6]), c2 = glsl::mk(m[8], m[9], m[10]);
-    const glsl::v3 a[3] = {glsl::cross(c1, c2), glsl::cross(c2, c0), glsl::cross(c0, c1)};
-    for (int j = 0; j < 3; ++j) {
-      o[16 + 3 * j] = a[j].x;
-      o[17 + 3 * j] = a[j].y;
-      o[18 + 3 * j] = a[j].z;
-    }
-  }
-  hipStream_t s = g.stream;
-  int rc = (int)hipMemcpyAsync(ps.mats_dev, ps.mats_host, (size_t)n_obj * ptk::kPoseMatFloats * sizeof(float),
-                               hipMemcpyHostToDevice, s);
-  if (rc != 0) {
-    if (disp && disp != p->raster.disp) ps.disp_spare = disp;
-    return hip_err((hipError_t)rc, "pt_pose_apply");
-  }
-  if (p) {
-    if (motion) {
-      p->raster.disp = disp;
-    } else if (p->raster.disp) {  // left without records, as a refit leaves it; no draw reads them (see the header)
-      if (ps.disp_spare) (void)hipFree(ps.disp_spare);
-      ps.disp_spare = p->raster.disp;
-      p->raster.disp = nullptr;
-    }
-  }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (out_ms) {
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, s);
-  }
-  const int nxt = ps.cur ^ 1;
-  rc = ptk::pose_tris_launch(ps.tri_rest, ps.ntris, ps.mats_dev, n_obj, ps.tri_posed, s);
-  if (rc == 0 && ps.rtris)
-    rc = ptk::pose_raster_launch(ps.r_rest, ps.r_obj, ps.rtris, ps.mats_dev, n_obj, ps.r_list[nxt], s);
-  // pt_bvh_refit with the posed list as tri_in
-  if (rc == 0) rc = ptk::lbvh_refit_reorder(*rf, ps.tri_posed, (float*)to->dev, s);
-  if (rc == 0) rc = ptk::lbvh_refit_nodes(*rf, (float*)no->dev, ps.tri_posed, ptk::kTriEncoded, s);
-  std::unique_ptr<ptk::LbvhTrees> trees(new ptk::LbvhTrees);
-  const bool launched = rc == 0;
-  int trc = launched ? ptk::lbvh_trees_launch(g_lbvh, (const float*)no->dev, rf->nnodes, *trees, s, rf->err) : 0;
-  // pt_raster_pass_refit_device with the new list; the packed tree has the bind's size (same topology), so its copy is
-  // issued before the counters are back, and they are checked after the one synchronisation
-  ptk::LbvhTrees rtrees;
-  int rrc = 0;
-  const bool raster_launched = p && launched && trc == 0;
-  if (raster_launched) {
-    RasterScene& rs = p->raster;
-    ptk::LbvhRefit& rrf = *rs.refit;
-    rrc = ptk::decode_raster(ps.r_list[nxt], rrf.order, rs.ntris, rs.geom, rs.nrm, s);
-    if (rrc == 0) rrc = ptk::lbvh_refit_nodes(rrf, rs.enc_nodes, ps.r_list[nxt], ptk::kRasterVerts, s);
-    if (rrc == 0) rrc = ptk::lbvh_trees_launch(g_lbvh, rs.enc_nodes, rrf.nnodes, rtrees, s, rrf.err);
-  }
-  if (out_ms) (void)hipEventRecord(e1, s);
-  if (raster_launched && rrc == 0) {
-    RasterScene& rs = p->raster;
-    rrc = (int)hipMemcpyAsync(rs.bvh, rtrees.bin, (size_t)rs.bvh_records * 4 * sizeof(float4), hipMemcpyDeviceToDevice, s);
-    if (rrc == 0 && motion)
-      rrc = ptk::raster_disp(rs.geom, ps.r_list[ps.cur], ps.r_list[nxt], rs.ntris, rs.disp, s);
-  }
-  rc = rc == 0 ? PT_OK : hip_err((hipError_t)rc, "pt_pose_apply");
-  {  // the one synchronisation; also after a failure: the stages' counters are copied into the trees
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess && rc == PT_OK) rc = hip_err(e, "pt_pose_apply");
-  }
-  if (out_ms) {
-    *out_ms = 0.0f;
-    if (rc == PT_OK) (void)hipEventElapsedTime(out_ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
-  if (rc == PT_OK && trc == 0) trc = ptk::lbvh_trees_finish(*trees);
-  if (rc == PT_OK && trc != 0) rc = err(PT_ERR_HIP, "pt_pose_apply: deriving the walk trees failed");
-  // as pt_bvh_refit: the contents changed whatever came of it, the old trees go, and every consumer re-reads
-  to->version++;
-  no->version++;
-  to->host_stale = no->host_stale = true;
-  free_trees(no);
-  if (rc == PT_OK) {
-    trees->version = no->version;
-    no->trees = trees.release();
-    no->refit_tri_ver = to->version;
-    no->refit_node_ver = no->version;
-  } else {
-    ptk::lbvh_trees_free(*trees);
-    free_refit(no);
-  }
-  if (ps.rtris && launched) ps.cur = nxt;
-  if (p) {
-    RasterScene& rs = p->raster;
-    if (rc == PT_OK && rrc == 0) rrc = ptk::lbvh_trees_finish(rtrees);
-    if (rc == PT_OK && rrc == 0 &&
-        (rtrees.dev_info[1] != rs.stack_need || std::max(1, rtrees.nbin()) != rs.bvh_records))
-      rrc = (int)hipErrorInvalidValue;  // the topology is the bind's: the same depth and as many records
-    if (rc == PT_OK && rrc == 0) rs.root_ref = rtrees.dev_info[0];
-    ptk::lbvh_trees_free(rtrees);
-    if (rc != PT_OK || rrc != 0) {
-      drop_disp(p);
-      free_raster_refit(rs);  // the records may be half written: the caller binds again
-      if (rc == PT_OK) rc = hip_err((hipError_t)rrc, "pt_pose_apply: refitting the rasterize pass");
-    }
-  }
-  return rc;
-}
-
-int pt_debug_pose_raster(uint32_t pose, int which, float* host_out, size_t cap, size_t* n) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  TRY(ensure_init());
-  auto it = g.poses.find(pose);
-  if (it == g.poses.end()) return err(PT_ERR_INVALID_HANDLE, "pt_debug_pose_raster: unknown pose");
-  if (which < 0 || which > 1) return err(PT_ERR_ARG, "pt_debug_pose_raster: which 0 (current) or 1 (previous)");
-  const Pose& ps = *it->second;
-  const size_t floats = (size_t)ps.rtris * 18;
-  if (n) *n = floats;
-  if (!host_out || !floats) return PT_OK;
-  if (cap < floats) return err(PT_ERR_ARG, "pt_debug_pose_raster: host_out is too small");
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host_out, ps.r_list[ps.cur ^ which], floats * sizeof(float), hipMemcpyDeviceToHost));
   return PT_OK;
 }
 
@@ -3049,19 +2028,7 @@ int pt_pass_destroy(uint32_t pass) {
   auto it = g.passes.find(pass);
   if (it == g.passes.end()) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
   (void)hipStreamSynchronize(g.stream);
-  Pass* p = it->second.get();
-  if (p->raster.geom) (void)hipFree(p->raster.geom);
-  if (p->raster.nrm) (void)hipFree(p->raster.nrm);
-  if (p->raster.disp) (void)hipFree(p->raster.disp);
-  if (p->raster.bvh) (void)hipFree(p->raster.bvh);
-  free_raster_refit(p->raster);
-  if (p->bins.base) (void)hipFree(p->bins.base);
-  if (p->wf.base) (void)hipFree(p->wf.base);
-  if (p->wf.spill) (void)hipFree(p->wf.spill);
-  if (p->order.cost) (void)hipFree(p->order.cost);
-  if (p->order.perm) (void)hipFree(p->order.perm);
-  if (p->ev0) (void)hipEventDestroy(p->ev0);
-  if (p->ev1) (void)hipEventDestroy(p->ev1);
+  free_pass(it->second.get());
   g.passes.erase(it);
   return PT_OK;
 }

@@ -1,0 +1,345 @@
+// capi_state.h — the library state behind include/ptsvgf.h, shared by the translation units that implement it:
+// capi.hip (init, textures, passes, draws, the scene cache; it defines the state and the helpers declared here) and
+// capi_geometry.hip (geometry that moves: builds, refits, raster binds, poses). Internal: nothing here is part of the ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/ptsvgf.h"
+#include "pt_device.h"
+
+namespace ptapi {
+
+enum ProgKind { PK_PATHTRACE = 1, PK_REPROJECT, PK_VARIANCE, PK_ATROUS, PK_MODULATE, PK_BLIT, PK_SAVE, PK_OUTPUT, PK_TAA,
+                PK_RASTER };
+
+struct Texture {
+  uint32_t target = PT_TEXTURE_2D;
+  int W = 0, H = 0;      // logical (global) size
+  int row0 = 0, rows = 0;  // stored rows (band)
+  int layers = 0;
+  bool owned = true;
+  void* dev = nullptr;
+  size_t bytes = 0;
+  std::vector<uint8_t> host;  // buffers: host copy for decoding
+  uint64_t version = 1;
+  // compact one-float side plane of the stored rows: a depth-fwidth attachment's fwidth.y with the background flag, a
+  // world-position attachment's primary-ray bound for rays from aux_eye (draw_raster)
+  float* aux = nullptr;
+  bool aux_valid = false;
+  float aux_eye[3] = {0.0f, 0.0f, 0.0f};
+  unsigned char* tflags = nullptr;  // a-trous per-tile surface flags derived from aux (atrous_tile_flags)
+  size_t tflags_cap = 0;
+  uint64_t tflags_ver = 0;          // texture version / rows they were derived for
+  int tflags_y0 = 0, tflags_y1 = -1;
+  bool lbvh = false;     // written by pt_bvh_build (the device copy is authoritative: get_scene decodes it there)
+  // a node buffer pt_bvh_build wrote: the walk trees the device derived from it (owned; trees->version == version)
+  ptk::LbvhTrees* trees = nullptr;
+  // a node buffer pt_bvh_build wrote: what pt_bvh_refit needs (owned, held as trees is) and the pair it belongs to,
+  // the triangle buffer's handle and both versions as the build (or the last refit) left them
+  ptk::LbvhRefit* refit = nullptr;
+  uint32_t refit_tri = 0;
+  uint64_t refit_tri_ver = 0, refit_node_ver = 0;
+  // pt_bvh_refit wrote dev in place; host is brought up to date by its readers (refresh_host)
+  bool host_stale = false;
+};
+
+struct Uniform {
+  int type = 0;  // 1 float 2 int 3 uint 4 bool 5 vec3 6 mat4
+  float f[16] = {0};
+  int i = 0;
+  uint32_t u = 0;
+};
+
+struct RasterScene {
+  float4* geom = nullptr;
+  float4* nrm = nullptr;
+  float4* disp = nullptr;  // pt_raster_pass_set_prev_vertices: displacement records beside nrm, or null
+  float4* bvh = nullptr;
+  int root_ref = 0;
+  int stack_need = 0;
+  int ntris = 0;
+  // pt_raster_pass_bind_device: the encoded nodes of the bind and what refits them (pt_raster_pass_refit_device);
+  // null after a host bind
+  float* enc_nodes = nullptr;
+  ptk::LbvhRefit* refit = nullptr;
+  int bvh_records = 0;  // packed records bvh has room for (that bind's; >= 1 while refit is set)
+};
+
+// Scratch of the tile-binned G-buffer (launch_gbuffer_raster), per rasterize pass, sized by its triangles and band.
+struct RasterBins {
+  void* base = nullptr;
+  int ntris = 0, ntiles = 0, pair_cap = 0, big_cap = 0;
+  int4* tri_box = nullptr;
+  float* tri_tmin = nullptr;
+  int *tile_count = nullptr, *tile_off = nullptr, *pairs = nullptr, *big = nullptr, *ctr = nullptr;
+};
+
+struct WFBuffers {
+  void* base = nullptr;  // one allocation carved into the WFState arrays
+  size_t n = 0;          // pixels per frame
+  int nb = 1;            // frames (pt_pass_draw_batch): per-pixel arrays for nb * n pixels, lists and counters per frame
+  ptk::WFState stb[ptk::kMaxBatch]{};  // frame b's state: per-pixel arrays at pid offset b * n; stb[0] == st
+  ptk::WFState st{};
+  float4* spp = nullptr;  // the sample planes of an spp draw: nsp planes of n texels (SppResolve::samples)
+  int nsp = 0;
+  int* spill = nullptr;  // deep reference trees: stack entries past the LDS stack (WFState::spill)
+  int spill_levels = 0;
+  size_t spill_cols = 0;
+};
+
+// Cost-ordered tile dispatch state of one traversal pass (TileSched, pt_device.h).
+struct TileOrder {
+  uint32_t* cost = nullptr;  // per-tile cost recorded by the current launch
+  int* perm = nullptr;       // dispatch order computed from the previous launch
+  int n = 0;
+  bool ordered = false;      // perm holds a valid order for n tiles
+};
+
+struct Pass {
+  uint32_t program = 0;
+  WFBuffers wf;
+  TileOrder order;
+  int W = 0, H = 0;
+  std::vector<uint32_t> att;
+  bool bound = false, final_pass = false;
+  int slot = 0;
+  std::unordered_map<std::string, uint32_t> tex;
+  std::unordered_map<std::string, Uniform> uni;
+  int y_begin = -1, y_end = -1;
+  RasterScene raster;
+  uint32_t raster_src = 0;  // pt_raster_pass_share: draw this rasterize pass's triangles and tree instead
+  RasterBins bins;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool timed = false;
+  uint32_t* row_cost = nullptr;  // pt_pass_set_row_cost (not owned)
+  uint8_t* sample_counts = nullptr;  // pt_pass_set_sample_counts (not owned)
+  float2* sample_stats = nullptr;    // pt_pass_set_sample_stats (not owned)
+  uint32_t* motion_max = nullptr;  // pt_pass_set_motion_bound (not owned)
+  unsigned long long* stats = nullptr;  // pt_pass_set_trace_stats (not owned)
+  int stats_n = 0;                      // counters that buffer holds (pt_pass_set_trace_stats_n)
+};
+
+// A device buffer built on one draw's stream and read by the draws of every frame in flight on other streams (the
+// merged environment, the point-light bins). A rebuild writes a buffer no draw still reads: the current one is retired
+// with the event of the build that wrote it and its readers' events, and a retired buffer is taken again only once all
+// of those have completed, else a new one is allocated. Every reader's stream waits for the build's event. No host
+// wait anywhere, so a rebuild never blocks on the device (e.g. on RCCL receives in flight for peers); retired buffers
+// are kept, never freed mid-run. Rebuilds are rare.
+struct SharedBuf {
+  void* buf = nullptr;
+  size_t bytes = 0;
+  hipEvent_t built = nullptr;              // recorded after the work that wrote buf, on the stream that ran it
+  std::map<hipStream_t, hipEvent_t> uses;  // per draw stream: recorded after its latest draw that read buf
+  struct Retired {
+    void* buf;
+    size_t bytes;
+    hipEvent_t built;  // the build that wrote it (null: none was recorded)
+    std::vector<hipEvent_t> readers;
+  };
+  std::vector<Retired> spare;
+
+  // a buffer of at least `need` bytes that nothing in flight reads or writes, in place of the current one
+  hipError_t renew(size_t need) {
+    if (buf) {
+      Retired r{buf, bytes, built, {}};
+      for (auto& u : uses) r.readers.push_back(u.second);
+      uses.clear();
+      spare.push_back(std::move(r));
+      buf = nullptr;
+      bytes = 0;
+      built = nullptr;
+    }
+    for (size_t i = 0; i < spare.size(); ++i) {
+      Retired& r = spare[i];
+      bool idle = r.bytes >= need && (!r.built || hipEventQuery(r.built) == hipSuccess);
+      for (size_t j = 0; idle && j < r.readers.size(); ++j) idle = hipEventQuery(r.readers[j]) == hipSuccess;
+      if (!idle) continue;
+      buf = r.buf;
+      bytes = r.bytes;
+      built = r.built;  // completed: recorded again by mark_built
+      for (hipEvent_t e : r.readers) (void)hipEventDestroy(e);
+      spare.erase(spare.begin() + i);
+      return hipSuccess;
+    }
+    const hipError_t e = hipMalloc(&buf, need);
+    if (e != hipSuccess) buf = nullptr;
+    else bytes = need;
+    return e;
+  }
+  // after the work that wrote buf was issued on s
+  hipError_t mark_built(hipStream_t s) {
+    if (!built)
+      if (const hipError_t e = hipEventCreateWithFlags(&built, hipEventDisableTiming)) return e;
+    return hipEventRecord(built, s);
+  }
+  // before work on s reads buf (a no-op wait once the build has run)
+  hipError_t wait_built(hipStream_t s) { return hipStreamWaitEvent(s, built, 0); }
+  // after a draw on s that read buf was issued: a later renew knows when that draw no longer reads it
+  hipError_t note_read(hipStream_t s) {
+    if (!buf) return hipSuccess;
+    hipEvent_t& e = uses[s];
+    if (!e)
+      if (const hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming)) return rc;
+    return hipEventRecord(e, s);
+  }
+  // s is released (pt_stream_release): its last read is waited for, so its event need not outlive the stream
+  void forget(hipStream_t s) {
+    auto u = uses.find(s);
+    if (u == uses.end()) return;
+    (void)hipEventSynchronize(u->second);
+    (void)hipEventDestroy(u->second);
+    uses.erase(u);
+  }
+  bool any() const { return buf || !spare.empty(); }
+  // drops every buffer and event (the caller has synchronised the streams that read them)
+  void free() {
+    if (buf) (void)hipFree(buf);
+    if (built) (void)hipEventDestroy(built);
+    for (auto& u : uses) (void)hipEventDestroy(u.second);
+    for (Retired& r : spare) {
+      (void)hipFree(r.buf);
+      if (r.built) (void)hipEventDestroy(r.built);
+      for (hipEvent_t e : r.readers) (void)hipEventDestroy(e);
+    }
+    *this = SharedBuf{};
+  }
+};
+
+// What the draw being issued reads of the shared buffers (pt_params, point_bins_for), noted on its stream after a
+// successful launch (note_reads). Local to the draw call, which holds g_mu throughout.
+struct DrawReads {
+  SharedBuf* hdr = nullptr;
+  SharedBuf* pbins = nullptr;
+};
+
+// The point-light triangle bins of a scene (ptk::PointBinsDev, kernels_pointbins.hip) for the lights texture a
+// path-tracing draw bound: built on the device by the first such draw, rebuilt when the scene's triangles or tree, the
+// lights texture (handle, device memory, version), pointLightSize, R or the binning (point_bins_tight) change. Read
+// by the path tracers of every frame in flight on other streams: a SharedBuf.
+struct PointBinsGPU {
+  SharedBuf sb;
+  ptk::PointBinsDev dev{};
+  uint64_t tri_ver = 0, node_ver = 0, light_ver = 0;
+  uint32_t light_handle = 0;
+  const void* light_dev = nullptr;
+  int nl = 0, R = 0, ntris = 0, tight = 0;
+};
+
+struct SceneGPU {
+  PointBinsGPU pbins;
+  float4* geom = nullptr;
+  float4* shade = nullptr;
+  float4* bvh = nullptr;
+  float4* bvh4 = nullptr;
+  float4* bvh_any = nullptr;  // any-hit tree over the reference leaves (build_anyhit_tree)
+  float4* leaves = nullptr;   // the reference leaves: (box lo, leaf ref bits), (box hi, 0) (wf_primary_raster)
+  int nleaves = 0;
+  int* tri_leaf = nullptr;    // per triangle: its reference leaf's index in `leaves` (wf_primary_tri); always owned
+  int tri_leaf_cap = 0;       // triangles tri_leaf has room for
+  bool tri_shared = false;    // host-built trees: some triangle lies in two leaves (upload_leaves)
+  int root_any = 0, need_any = 0;
+  bool has4 = false;  // bvh4: the 4-wide form of bvh_any (pack_wide)
+  bool nan4 = false;  // a child box of bvh4 has a NaN coordinate (PT_WIDE_SIGNED walks need lo <= hi: not walked)
+  // a scene pt_bvh_build wrote: bvh (== bvh_any), bvh4 and leaves belong to the node texture's LbvhTrees, not to this
+  bool lbvh = false;
+  int root4 = 0, need4 = 0, root4c = 0;  // root4c: the closest-hit walks' root (SceneDev::root4c)
+  // refine_leaves' fine boxes are padded for rays whose origin lies within kFineEyeReach x the scene's largest vertex
+  // coordinate; an eye further out (pt_params) walks the reference tree instead
+  float fine_eye_limit = INFINITY;
+  int stack_need = 0;
+  int root_ref = 0;
+  int ntris = 0;
+  uint64_t tri_ver = 0, node_ver = 0;
+};
+
+// The environment map with its importance cache's pdf channel beside it (PTParams::hdr_pdf): built on the device
+// when a path-tracing draw binds an hdrMap and an hdrCache of one size, rebuilt when either changes (versions), freed
+// with either texture. Read by the path tracers of every frame in flight on other streams: a SharedBuf of float4.
+struct HdrMerged {
+  SharedBuf sb;
+  const void *hdr_dev = nullptr, *cache_dev = nullptr;
+  uint64_t vh = 0, vc = 0;
+  int W = 0, H = 0;
+};
+
+// Posed objects (pt_pose_create): the rest-pose lists on the device and what pt_pose_apply writes from them
+struct Pose {
+  int ntris = 0;               // Triangle_encoded records
+  float* tri_rest = nullptr;   // in the order of the build's tri_in
+  float* tri_posed = nullptr;  // staging: the posed list, pt_bvh_refit's tri_in
+  int rtris = 0;               // raster triangles (0: the pose serves the path tracer only)
+  float* r_rest = nullptr;
+  int* r_obj = nullptr;        // one object per raster triangle
+  float* r_list[2] = {nullptr, nullptr};  // posed raster lists; r_list[cur] is what the pass holds
+  int cur = 0;
+  float* mats_dev = nullptr;   // kPoseMaxObjects x kPoseMatFloats
+  float* mats_host = nullptr;  // pinned staging of the same size
+  float4* disp_spare = nullptr;  // displacement records taken off the pass by a pose without motion, for the next
+};
+
+struct Lib {
+  bool init = false;
+  int device = 0;
+  hipStream_t own = nullptr, stream = nullptr;
+  uint32_t next = 1;
+  std::map<uint32_t, int> programs;
+  std::map<uint32_t, std::unique_ptr<Texture>> textures;
+  std::map<uint32_t, std::unique_ptr<Pass>> passes;
+  std::map<uint32_t, std::unique_ptr<Pose>> poses;
+  std::map<std::pair<uint32_t, uint32_t>, SceneGPU> scenes;
+  std::map<std::pair<uint32_t, uint32_t>, HdrMerged> hdr_merged;  // keyed by (hdrMap, hdrCache) handles
+  std::map<hipStream_t, ptk::WfFork> forks;  // per draw stream: the path tracer's side stream (uniform trace_fork)
+  uint32_t unit0 = 0;  // GL texture unit 0 binding (global)
+  int band_w = 0, band_h = 0, band_y0 = 0, band_y1 = 0, band_row0 = 0, band_rows = 0;
+  bool profiling = false;
+};
+
+// defined in capi.hip
+extern Lib g;
+extern std::recursive_mutex g_mu;
+extern ptk::LbvhWork g_lbvh;  // GPU BVH builder scratch (grows, reused across rebuilds)
+
+int err(int code, const std::string& m);  // sets the calling thread's pt_last_error text
+int hip_err(hipError_t e, const char* what);
+#define HIPCHK(x)                                    \
+  do {                                               \
+    hipError_t e_ = (x);                             \
+    if (e_ != hipSuccess) return hip_err(e_, #x);    \
+  } while (0)
+#define TRY(x)                    \
+  do {                            \
+    int rc_ = (x);                \
+    if (rc_ != PT_OK) return rc_; \
+  } while (0)
+
+Texture* tex_of(uint32_t h);
+Pass* pass_of(uint32_t h);
+int ensure_init();
+int refresh_host(Texture* t);
+
+// defined in capi_geometry.hip: what pt_shutdown and the destroy calls release of a texture, a pass, a pose
+void free_trees(Texture* t);
+void free_refit(Texture* t);
+void free_raster_refit(RasterScene& r);
+void free_pose(Pose& p);
+
+// (T: the device type, or the host tree builder's Float4 for float4)
+template <class T, class D>
+int upload_vec(const std::vector<T>& v, D** dst) {
+  static_assert(sizeof(T) == sizeof(D), "upload_vec copies records as they are");
+  if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
+  if (v.empty()) return PT_OK;
+  HIPCHK(hipMalloc((void**)dst, v.size() * sizeof(T)));
+  HIPCHK(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return PT_OK;
+}
+
+}  // namespace ptapi

@@ -595,7 +595,7 @@ struct LbvhTrees {
   int dev_info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   float stage_ms = 0.0f;  // device time of the stage
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  uint64_t version = 0;  // the node texture's version these trees were derived from (capi.hip)
+  uint64_t version = 0;  // the node texture's version these trees were derived from (capi_geometry.hip)
   int nbin() const { return dev_info[8]; }
   int nleaves() const { return dev_info[2]; }
   int nwide() const { return dev_info[5]; }

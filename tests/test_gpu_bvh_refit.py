@@ -8,7 +8,8 @@ refit_nodes) for geometry that moves but keeps its triangles and their order.
 * The walk trees derived after a refit equal the host functions on the refitted texels.
 * Rendering over refitted buffers is bit-exact against the oracle path tracer on the same buffers; the refitted
   G-buffer pass draws the planes of a host bind to the moved list, and the motion vectors of a rebuild.
-* Argument and state errors return before any launch and leave buffers and passes as they were."""
+* Argument and state errors return before any launch and leave buffers and passes as they were.
+* A build, a refit and a pose write the same bytes with and without out_ms, and report a time above zero."""
 import dataclasses
 
 import numpy as np
@@ -324,6 +325,49 @@ def test_refit_errors_leave_the_buffers_unchanged(gpu):
         rebuilt = gpu.buffer_readback(b.to).reshape(-1, 45), refitted[1]
         refused(-9, src, b.to, b.no, want=rebuilt)
         gpu.bvh_refit(src, b.to, no2)  # the new pair is one
+
+
+def test_out_ms_is_optional_and_changes_nothing(gpu):
+    """pt_bvh_build, pt_bvh_refit and pt_pose_apply (two objects over the same list), each called without and with
+    out_ms: both calls leave byte-identical triangle and node buffers and the same counters of the derived trees (the
+    first seven info words of pt_debug_lbvh_trees; the eighth is the stage's measured time), and the time reported is
+    finite and above zero. The timed calls read their events after the call's own synchronisation."""
+    import ctypes as C
+
+    from ptsvgf._lib import check, pt
+    from ptsvgf.scene import transform
+
+    t = _random_tris(100, seed=2)
+    t[:, 42] = np.arange(100) % 2
+    mats = np.ascontiguousarray(np.stack([transform(), transform(rot=(10, 40, -20), trans=(0.3, -0.1, 0.2))]),
+                                np.float32).reshape(-1, 16)
+    src, moved = gpu.texture_buffer(t), gpu.texture_buffer(_displaced(t, seed=3))
+    to, no = gpu.texture_buffer(np.zeros(3, np.float32)), gpu.texture_buffer(np.zeros(3, np.float32))
+    poses = []
+
+    def state():
+        return (gpu.buffer_readback(to).tobytes(), gpu.buffer_readback(no).tobytes(), gpu.lbvh_trees(no, 0)["info"][:7])
+
+    def without_and_with(call):
+        check(call(None))
+        plain = state()
+        ms = C.c_float(-1.0)
+        check(call(C.byref(ms)))
+        assert state() == plain
+        assert np.isfinite(ms.value) and ms.value > 0.0, ms.value
+
+    try:
+        without_and_with(lambda ms: pt().pt_bvh_build(src, 4, 16, to, no, None, ms))
+        assert len(gpu.buffer_readback(to)) == t.size
+        without_and_with(lambda ms: pt().pt_bvh_refit(moved, to, no, ms))
+        poses.append(gpu.pose_create(src))
+        mp = mats.ctypes.data_as(C.POINTER(C.c_float))
+        without_and_with(lambda ms: pt().pt_pose_apply(poses[0], mp, 2, to, no, 0, 1, ms))
+    finally:
+        for p in poses:
+            gpu.pose_destroy(p)
+        for h in (src, moved, to, no):
+            gpu.destroy_texture(h)
 
 
 def test_raster_refit_errors_leave_the_pass_drawing(gpu, scene_small):
