@@ -313,6 +313,37 @@ int pt_pass_set_sample_stats(uint32_t pass, void* device_f32x2);
  * pt_set_band partition. Nothing is launched on an error. */
 int pt_sample_counts_derive(const void* stats, uint32_t motion_tex, uint32_t nd_tex, float lag, float tolerance,
                             int nmax, void* out_u8);
+/* The next draw's sample counts from statistics pooled over a slot's draws, on
+ * the library's current stream (DESIGN.md "Pooled sample statistics"). A pool
+ * plane holds width * height float4 (m, v, w, z): mean and unbiased variance
+ * of the pooled luminances, the pooled sample weight (0: empty) and nd_tex.z
+ * of the pixel when the texel was written. For every pixel p of the frame a
+ * texel T(p) is formed: (0, 0, 0, z) on the background (nd_tex.w == 1) or
+ * where the position (pixel centre) - lag * motion_tex.xy * (width, height)
+ * is non-finite or outside the frame; else, with q the texel holding that
+ * position, the history a = pool_in[q] is rejected (T empty) unless
+ * |a.z - z| <= zeta * max(|z|, 1e-4), and is valid when a.w >= 1 and a.m, a.v
+ * are finite; the new samples are n_s = min(max(counts_prev[q], 1), nmax_prev)
+ * (nmax_prev without a plane) with (m_s, v_s) = stats[q], valid when m_s is
+ * finite and n_s < 2 or v_s is finite and >= 0 (v_s counts as 0 at n_s < 2).
+ * T is the valid one of the two, or their pairwise combination (Chan) with
+ * the weight a.w + n_s held to wmax, or empty. T asks for nmax samples where
+ * w < 2, else for ceil(v / d^2) held to 1 .. nmax with d = tolerance *
+ * max(m, 1e-4) (rule 0, relative) or d = tolerance (rule 1, absolute).
+ * pool_out[p] = T(p); out_u8[p] = 1 on the background, else the largest ask
+ * over the surface texels of the 3 x 3 block around p inside the frame.
+ * stats (width * height float pairs, pt_pass_set_sample_stats), counts_prev
+ * (width * height bytes: the plane the statistics' draw read, nmax_prev its
+ * spp) and pool_in (the plane the previous call wrote) are in that draw's
+ * pixel coordinates; each may be NULL. lag: frames since that draw.
+ * PT_ERR_ARG for a null pool_out or out_u8, pool_out == pool_in, out_u8 ==
+ * counts_prev, a tolerance or zeta that is not > 0, wmax that is not >= 2, a
+ * rule other than 0 or 1, nmax or nmax_prev outside 2 .. 8, or textures of
+ * different sizes; PT_ERR_STATE for textures created under an active
+ * pt_set_band partition. Nothing is launched on an error. */
+int pt_sample_counts_pool(const void* stats, const void* counts_prev, int nmax_prev, const void* pool_in,
+                          uint32_t motion_tex, uint32_t nd_tex, float lag, float wmax, float zeta, int rule,
+                          float tolerance, int nmax, void* pool_out, void* out_u8);
 /* Motion bound (G-buffer pass): while set, every draw first zeroes *device_u32 and
  * then stores there the largest |motion.y| (UV units, the bits of a non-negative
  * float; +inf for a non-finite motion) over the surface pixels it computes. The

@@ -1937,6 +1937,48 @@ int pt_sample_counts_derive(const void* stats, uint32_t motion_tex, uint32_t nd_
   return rc ? hip_err((hipError_t)rc, "sample counts launch") : PT_OK;
 }
 
+int pt_sample_counts_pool(const void* stats, const void* counts_prev, int nmax_prev, const void* pool_in,
+                          uint32_t motion_tex, uint32_t nd_tex, float lag, float wmax, float zeta, int rule,
+                          float tolerance, int nmax, void* pool_out, void* out_u8) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  if (!pool_out || !out_u8) return err(PT_ERR_ARG, "pt_sample_counts_pool: null output plane");
+  if (pool_out == pool_in) return err(PT_ERR_ARG, "pt_sample_counts_pool: pool_out must not be pool_in");
+  if (out_u8 == counts_prev) return err(PT_ERR_ARG, "pt_sample_counts_pool: out_u8 must not be counts_prev");
+  if (!(tolerance > 0.0f)) return err(PT_ERR_ARG, "pt_sample_counts_pool: the tolerance must be > 0");
+  if (!(zeta > 0.0f)) return err(PT_ERR_ARG, "pt_sample_counts_pool: zeta must be > 0");
+  if (!(wmax >= 2.0f)) return err(PT_ERR_ARG, "pt_sample_counts_pool: wmax must be >= 2");
+  if (rule != 0 && rule != 1) return err(PT_ERR_ARG, "pt_sample_counts_pool: rule must be 0 (relative) or 1 (absolute)");
+  if (nmax < 2 || nmax > kMaxBatch || nmax_prev < 2 || nmax_prev > kMaxBatch)
+    return err(PT_ERR_ARG, "pt_sample_counts_pool: nmax and nmax_prev must lie in 2 .. 8");
+  Texture* mt = tex_of(motion_tex);
+  Texture* nt = tex_of(nd_tex);
+  if (!mt || !nt || mt->target != PT_TEXTURE_2D || nt->target != PT_TEXTURE_2D || !mt->dev || !nt->dev)
+    return err(PT_ERR_MISSING_TEXTURE, "pt_sample_counts_pool needs the 2-D textures gMotion and gNormalAndLinearZ");
+  if (mt->W != nt->W || mt->H != nt->H) return err(PT_ERR_ARG, "pt_sample_counts_pool: textures of different sizes");
+  if (band_partition(mt->W, mt->H) || mt->row0 != 0 || nt->row0 != 0 || mt->rows != mt->H || nt->rows != nt->H)
+    return err(PT_ERR_STATE, "pt_sample_counts_pool: not under a pt_set_band partition");
+  ptk::SppPoolParams c{};
+  c.stats = (const float2*)stats;
+  c.counts_prev = (const uint8_t*)counts_prev;
+  c.pool_in = (const float4*)pool_in;
+  c.motion = (const float4*)mt->dev;
+  c.nd = (const float4*)nt->dev;
+  c.pool_out = (float4*)pool_out;
+  c.out = (uint8_t*)out_u8;
+  c.W = mt->W;
+  c.H = mt->H;
+  c.nmax = nmax;
+  c.nmax_prev = nmax_prev;
+  c.rule = rule;
+  c.lag = lag;
+  c.tol = tolerance;
+  c.wmax = wmax;
+  c.zeta = zeta;
+  const int rc = launch_spp_pool(c, g.stream);
+  return rc ? hip_err((hipError_t)rc, "sample counts pool launch") : PT_OK;
+}
+
 int pt_pass_set_trace_stats_n(uint32_t pass, void* device_u64, int count) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   Pass* p = pass_of(pass);

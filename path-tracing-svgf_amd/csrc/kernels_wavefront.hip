@@ -2020,6 +2020,108 @@ int launch_spp_counts(const SppCountsParams& c, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+// One texel of pt_sample_counts_pool (tests/adaptive_pool_ref.py T(p) and r(T)) for the frame pixel (x, y), which the
+// caller has tested to lie in the frame: the pooled statistics (m, v, w, z) and the samples they ask for (0 on the
+// background). The history and the new samples are read at q, tested to lie in the frame, and only where the rule
+// still needs them: nothing past a background pixel, an off-frame q or a failed depth test.
+__device__ __forceinline__ int spp_pool_texel(const SppPoolParams& c, int x, int y, float4* T) {
+  const size_t i = (size_t)y * c.W + x;
+  const float4 nd = c.nd[i];
+  *T = make_float4(0.0f, 0.0f, 0.0f, nd.z);
+  if (nd.w == 1.0f) return 0;
+  const float4 mv = c.motion[i];
+  const float fx = ((float)x + 0.5f) - (c.lag * mv.x) * (float)c.W;
+  const float fy = ((float)y + 0.5f) - (c.lag * mv.y) * (float)c.H;
+  // (NaN fails every comparison; the bounds hold in float before the conversion, so no int overflows)
+  if (!(fx >= 0.0f && fx < (float)c.W && fy >= 0.0f && fy < (float)c.H)) return c.nmax;
+  const size_t q = (size_t)(int)floorf(fy) * c.W + (int)floorf(fx);
+  float am = 0.0f, av = 0.0f, aw = 0.0f;  // the history (m, v, w); its z is the float4's fourth component
+  bool a_ok = false;
+  if (c.pool_in) {
+    const float4 a = c.pool_in[q];
+    am = a.x, av = a.y, aw = a.z;
+    const float az = fabsf(nd.z);  // (a NaN stays a NaN through the floor below and fails the test)
+    if (!(fabsf(a.w - nd.z) <= c.zeta * (az < 1e-4f ? 1e-4f : az))) return c.nmax;
+    a_ok = aw >= 1.0f && __builtin_isfinite(am) && __builtin_isfinite(av);
+  }
+  int n = c.nmax_prev;
+  if (c.counts_prev) n = min(max((int)c.counts_prev[q], 1), c.nmax_prev);
+  const float ns = (float)n;
+  float ms = 0.0f, vs = 0.0f;
+  bool s_ok = false;
+  if (c.stats) {
+    const float2 st = c.stats[q];
+    ms = st.x;
+    s_ok = __builtin_isfinite(ms) && (n < 2 || (__builtin_isfinite(st.y) && st.y >= 0.0f));
+    vs = n >= 2 ? st.y : 0.0f;
+  }
+  float m, v, w;
+  if (a_ok && s_ok) {  // Chan's pairwise update, one rounding per operation (-ffp-contract=off)
+    w = aw + ns;
+    const float d = ms - am;
+    m = am + d * (ns / w);
+    const float m2 = (av * (aw - 1.0f) + vs * (ns - 1.0f)) + (d * d) * ((aw * ns) / w);
+    v = m2 / (w - 1.0f);
+    w = fminf(w, c.wmax);  // (w >= 2 here, never a NaN)
+  } else if (s_ok) {
+    m = ms, v = vs, w = ns;
+  } else if (a_ok) {
+    m = am, v = av, w = aw;
+  } else {
+    return c.nmax;
+  }
+  *T = make_float4(m, v, w, nd.z);
+  if (!(w >= 2.0f)) return c.nmax;
+  const float d = c.rule ? c.tol : c.tol * (m < 1e-4f ? 1e-4f : m);  // (a NaN m stays: k is a NaN, r = N)
+  const float k = ceilf(v / (d * d));
+  if (!(k < (float)c.nmax)) return c.nmax;
+  return k >= 1.0f ? (int)k : 1;
+}
+
+// pt_sample_counts_pool: one fused launch, a block of 256 threads per 16 x 16 pixel tile. Every thread evaluates the
+// texel of its own pixel and keeps it in registers; the first 68 threads also evaluate one texel of the apron ring
+// (18 + 18 + 16 + 16). Each texel's need r goes to LDS as one byte (324 per block, 0 for a texel off the frame or on
+// the background: neither raises a maximum); after one barrier each thread takes the 9-tap maximum around its pixel
+// and stores one byte and one float4. No atomics; every global access is of a texel tested to lie in the frame.
+__global__ void __launch_bounds__(256) spp_pool_kernel(SppPoolParams c) {
+  __shared__ uint8_t need[18 * 18];
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+  const int x0 = blockIdx.x * 16, y0 = blockIdx.y * 16;
+  const int x = x0 + tx, y = y0 + ty;
+  const bool own = x < c.W && y < c.H;
+  float4 T = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  need[(ty + 1) * 18 + tx + 1] = own ? (uint8_t)spp_pool_texel(c, x, y, &T) : (uint8_t)0;
+  if (t < 68) {  // the ring: the rows above and below (18 texels each), then the columns left and right (16 each)
+    int ax, ay;
+    if (t < 36) {
+      ax = t % 18, ay = t < 18 ? 0 : 17;
+    } else {
+      ax = t < 52 ? 0 : 17, ay = 1 + (t - 36) % 16;
+    }
+    const int px = x0 + ax - 1, py = y0 + ay - 1;
+    float4 unused;
+    need[ay * 18 + ax] =
+        px >= 0 && px < c.W && py >= 0 && py < c.H ? (uint8_t)spp_pool_texel(c, px, py, &unused) : (uint8_t)0;
+  }
+  __syncthreads();
+  if (!own) return;
+  const size_t i = (size_t)y * c.W + x;
+  int count = 0;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) count = max(count, (int)need[(ty + dy) * 18 + tx + dx]);
+  if (need[(ty + 1) * 18 + tx + 1] == 0) count = 1;  // the background: a surface texel's own need is >= 1
+  c.pool_out[i] = T;
+  c.out[i] = (uint8_t)count;
+}
+
+int launch_spp_pool(const SppPoolParams& c, hipStream_t s) {
+  if (c.W <= 0 || c.H <= 0) return 0;
+  hipLaunchKernelGGL(spp_pool_kernel, dim3((c.W + 15) / 16, (c.H + 15) / 16), dim3(256), 0, s, c);
+  return (int)hipGetLastError();
+}
+
 // A producer block appends at most 256 items to the segment blockIdx % kSeg; the most blocks
 // an appending launch has is the larger of the per-pixel grid and the bounce-0 tile grid.
 int wf_list_capacity(int W, int rows) {

@@ -194,6 +194,23 @@ struct SppCountsParams {
 };
 int launch_spp_counts(const SppCountsParams& c, hipStream_t s);
 
+// pt_sample_counts_pool: the next draw's count plane from luminance statistics pooled over the slot's draws
+// (spp_pool_kernel; tests/adaptive_pool_ref.py). stats / counts_prev / pool_in: the previous draw's statistics, the
+// count plane it read (its spp nmax_prev) and the pool plane of its step, all in that draw's pixel coordinates and
+// each optional; pool_out: float4 (m, v, w, z) per frame pixel; rule 0 relative, 1 absolute.
+struct SppPoolParams {
+  const float2* stats;
+  const uint8_t* counts_prev;
+  const float4* pool_in;
+  const float4* motion;
+  const float4* nd;
+  float4* pool_out;
+  uint8_t* out;
+  int W, H, nmax, nmax_prev, rule;
+  float lag, tol, wmax, zeta;
+};
+int launch_spp_pool(const SppPoolParams& c, hipStream_t s);
+
 // Screen-tile binning of items (the G-buffer's triangles, the path tracer's BVH leaves) for the tile rasterisers:
 // an item-specific setup kernel writes each item's pixel box and counts it into the 16 x 16 tiles of the band it
 // covers (bins_count_item); launch_bins then bins the large items, scans and scatters (kernels_pt.hip).

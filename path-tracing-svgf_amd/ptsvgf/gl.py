@@ -275,6 +275,20 @@ def sample_counts_derive(stats_ptr: int, motion_tex: int, nd_tex: int, lag: floa
                                        float(np.float32(tolerance)), int(nmax), C.c_void_p(out_ptr or None)))
 
 
+def sample_counts_pool(stats_ptr: int, counts_prev_ptr: int, nmax_prev: int, pool_in_ptr: int, motion_tex: int,
+                       nd_tex: int, lag: float, wmax: float, zeta: float, rule: int, tolerance: float, nmax: int,
+                       pool_out_ptr: int, out_ptr: int) -> None:
+    """pt_sample_counts_pool: the next draw's per-pixel sample counts (W * H uint8 at out_ptr) and the pool plane
+    (W * H float4 (m, v, w, z) at pool_out_ptr) from the previous draw's statistics, the counts it read and the pool
+    plane of its step (each pointer may be 0), followed along this frame's motion vectors, on the library's current
+    stream. rule: 0 relative, 1 absolute."""
+    f = lambda v: float(np.float32(v))  # noqa: E731
+    check(pt().pt_sample_counts_pool(C.c_void_p(stats_ptr or None), C.c_void_p(counts_prev_ptr or None),
+                                     int(nmax_prev), C.c_void_p(pool_in_ptr or None), motion_tex, nd_tex, f(lag),
+                                     f(wmax), f(zeta), int(rule), f(tolerance), int(nmax),
+                                     C.c_void_p(pool_out_ptr or None), C.c_void_p(out_ptr or None)))
+
+
 def readback(tex: int) -> np.ndarray:
     """Stored rows of an RGBA32F texture as (rows, W, 4) float32."""
     w, rows, _ = texture_info(tex)

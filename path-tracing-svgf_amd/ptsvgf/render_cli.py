@@ -55,6 +55,10 @@ def main(argv=None) -> int:
     ap.add_argument("--spp", type=int, default=1, help="path-tracing samples per pixel per frame (1 .. 8)")
     ap.add_argument("--adaptive", type=float, default=None, metavar="TAU",
                     help="adaptive sample counts: relative tolerance of a pixel's mean luminance (needs --spp >= 2)")
+    ap.add_argument("--adaptive-pool", type=float, default=None, metavar="W",
+                    help="pool the sample statistics over frames, the pooled weight held to W >= 2 (needs --adaptive)")
+    ap.add_argument("--adaptive-rule", default="relative", choices=("relative", "absolute"),
+                    help="TAU bounds the error relative to the mean luminance, or absolutely (needs --adaptive-pool)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
 
@@ -66,7 +70,7 @@ def main(argv=None) -> int:
     gl.init(a.device)
     try:
         r = Renderer(scene, a.width, a.height, parameter_config(), mode=a.mode, run_taa=True, run_output=True,
-                     spp=a.spp, adaptive=a.adaptive)
+                     spp=a.spp, adaptive=a.adaptive, adaptive_pool=a.adaptive_pool, adaptive_rule=a.adaptive_rule)
         r.set_view(a.view)
         for _ in range(a.frames):
             if a.orbit:

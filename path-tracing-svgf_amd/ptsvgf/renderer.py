@@ -151,7 +151,8 @@ class Renderer:
                  halo=None, gbuffer_rows=None, frames_in_flight: int = 1, after_gbuffer=None, back_lag: int = 0,
                  trace_batch: int = 1, front_streams: int | None = None, pt_source=None, pt_flush=None,
                  stage_rows=None, early_history=None, draw_gbuffer: bool = True, fuse_modulate: bool = True,
-                 host_pace: bool = False, spp: int = 1, adaptive=None):
+                 host_pace: bool = False, spp: int = 1, adaptive=None, adaptive_pool=None,
+                 adaptive_rule: str = "relative", adaptive_zeta: float = 0.1):
         """band = (y0, y1, row0, rows) for screen-band sharding; tex_factory(w, h) -> handle allocates the
         frame-sized planes (ptsvgf.dist wraps torch tensors); halo(stage, {plane name: handle}) is called before
         the SVGF passes that read rows beyond the band (dist.HALO_SCHEDULE names the planes); after_gbuffer(set,
@@ -201,9 +202,17 @@ class Renderer:
         writes and a count plane its draws read. Before a slot's draw, on the front end's stream right after the
         G-buffer, the count plane is derived on the device from the statistics of the slot's own previous draw, looked
         up along this frame's motion vectors scaled by the frames since that draw; a slot that has not drawn takes N
-        samples everywhere. sample_counts() / sample_stats() read the planes back."""
+        samples everywhere. sample_counts() / sample_stats() read the planes back.
+
+        adaptive_pool = W (a pooled weight cap >= 2; default None, which leaves the path above as it is; needs
+        adaptive), adaptive_rule = "relative" | "absolute" ("absolute" needs adaptive_pool), adaptive_zeta (relative
+        depth tolerance of the history, > 0): the counts come from luminance statistics pooled over the slot's draws
+        (DESIGN.md "Pooled sample statistics", pt_sample_counts_pool). Every slot owns two pool planes and two count
+        planes, swapped every draw; the step runs at every frame of the slot, the first included (which writes the
+        depths and gives N on surfaces, 1 on the background). sample_pool() reads the current pool plane back."""
         if mode not in ("fast", "reference"):
             raise ValueError(mode)
+        self._pool = self._check_adaptive_pool(adaptive, adaptive_pool, adaptive_rule, adaptive_zeta)
         self.mode = mode
         self.W, self.H = int(width), int(height)
         self.cfg = config or parameter_config()
@@ -477,6 +486,10 @@ class Renderer:
 
                 ad = dict(stats=torch.zeros((H, W, 2), dtype=torch.float32, device="cuda"),
                           counts=torch.full((H, W), 255, dtype=torch.uint8, device="cuda"), last=None)
+                if self._pool is not None:  # the planes of the previous step beside those of this one
+                    ad.update(counts_prev=torch.full((H, W), 255, dtype=torch.uint8, device="cuda"),
+                              pool=torch.zeros((H, W, 4), dtype=torch.float32, device="cuda"),
+                              pool_prev=torch.zeros((H, W, 4), dtype=torch.float32, device="cuda"), n_prev=None)
                 torch.cuda.current_stream().synchronize()  # the slot's draws run on the renderer's own streams
                 p.set_sample_stats(ad["stats"].data_ptr())
                 p.set_sample_counts(ad["counts"].data_ptr())
@@ -583,20 +596,45 @@ class Renderer:
         That draw's resolve is ordered before this launch by what already orders the slot's reuse (_slot_free; one
         stream when K = 1)."""
         ad = self._ad[self._slot]
+        if self._pool is not None:
+            return self._pool_counts(ad, g)
         if ad["last"] is not None:
             gl.sample_counts_derive(ad["stats"].data_ptr(), g["velocity"], g["normal_depth"],
                                     float(self.frame_index - ad["last"]), self.adaptive, self._spp,
                                     ad["counts"].data_ptr())
         ad["last"] = self.frame_index
 
+    def _pool_counts(self, ad: dict, g: dict) -> None:
+        """_derive_counts with adaptive_pool: swap the slot's planes, then one pt_sample_counts_pool from the previous
+        step's planes into this one's; the pass reads the new count plane. At the slot's first frame nothing is
+        bound: the step writes the depths and N on surfaces."""
+        first = ad["last"] is None
+        ad["counts"], ad["counts_prev"] = ad["counts_prev"], ad["counts"]
+        ad["pool"], ad["pool_prev"] = ad["pool_prev"], ad["pool"]
+        po = self._pool
+        gl.sample_counts_pool(0 if first else ad["stats"].data_ptr(), 0 if first else ad["counts_prev"].data_ptr(),
+                              self._spp if first else ad["n_prev"], 0 if first else ad["pool_prev"].data_ptr(),
+                              g["velocity"], g["normal_depth"], 1.0 if first else float(self.frame_index - ad["last"]),
+                              po["wmax"], po["zeta"], po["rule"], self.adaptive, self._spp, ad["pool"].data_ptr(),
+                              ad["counts"].data_ptr())
+        self.pt_slots[self._slot][0].set_sample_counts(ad["counts"].data_ptr())
+        ad["last"], ad["n_prev"] = self.frame_index, self._spp
+
     def sample_counts(self) -> np.ndarray:
         """The count plane the last frame's path-tracing draw read, (H, W) uint8: 255 (= N) before the slot's first
-        draw, else pt_sample_counts_derive's values 1 .. N. adaptive only."""
+        draw, else pt_sample_counts_derive's values 1 .. N (with adaptive_pool: pt_sample_counts_pool's 1 .. N at every
+        frame). adaptive only."""
         return self._ad_read("counts")
 
     def sample_stats(self) -> np.ndarray:
         """The (mean, variance) plane the last frame's path-tracing draw wrote, (H, W, 2) float32. adaptive only."""
         return self._ad_read("stats")
+
+    def sample_pool(self) -> np.ndarray:
+        """The pool plane (m, v, w, z) the last frame's step wrote, (H, W, 4) float32. adaptive_pool only."""
+        if self._pool is None:
+            raise ValueError("the renderer was built without adaptive_pool")
+        return self._ad_read("pool")
 
     def _ad_read(self, key: str) -> np.ndarray:
         if self.adaptive is None:
@@ -618,6 +656,23 @@ class Renderer:
         if spp < 2:
             raise ValueError("adaptive needs spp >= 2: one sample gives no variance estimate")
         return float(tau)
+
+    @staticmethod
+    def _check_adaptive_pool(adaptive, wmax, rule, zeta):
+        """None without adaptive_pool, else the step's settings; ValueError for what the arguments refuse."""
+        if rule not in ("relative", "absolute"):
+            raise ValueError(f"adaptive_rule must be 'relative' or 'absolute', got {rule!r}")
+        if wmax is None:
+            if rule == "absolute":
+                raise ValueError("adaptive_rule='absolute' needs adaptive_pool")
+            return None
+        if adaptive is None:
+            raise ValueError("adaptive_pool needs adaptive (the tolerance)")
+        if not float(wmax) >= 2.0:
+            raise ValueError(f"adaptive_pool must be a weight cap >= 2 (or None), got {wmax!r}")
+        if not float(zeta) > 0.0:
+            raise ValueError(f"adaptive_zeta must be > 0, got {zeta!r}")
+        return dict(wmax=float(wmax), rule=int(rule == "absolute"), zeta=float(zeta))
 
     def _batching(self) -> bool:
         return self.B > 1 and self.mode == "fast" and not self.cfg.accumulate_color and self._spp == 1
