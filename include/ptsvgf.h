@@ -241,6 +241,28 @@ int pt_pose_create(uint32_t tri_rest, const float* raster_rest, size_t n_floats,
  * that differs from the pose's. PT_ERR_STATE: whatever pt_bvh_refit or pt_raster_pass_refit_device report so. */
 int pt_pose_apply(uint32_t pose, const float* mats16, int n_obj, uint32_t tri_out, uint32_t node_out,
                   uint32_t raster_pass, int motion, float* out_ms);
+/* Skinned objects: linear blend skinning of the pose's rest lists on the device (tests/skin_ref.py restates it).
+ * Every corner (a vertex of a Triangle_encoded record, or of a raster triangle) has four bone indices and four
+ * weights; the 12 affine floats of a bone (floats 3, 7, 11, 15 of its mat4 are not read) are blended as
+ * M[j] = ((w0 B0[j] + w1 B1[j]) + w2 B2[j]) + w3 B3[j], positions go through M as in a pose and normals through the
+ * normalised cofactor matrix of M. Weights are not normalised; unused slots carry weight 0 and any valid index. A
+ * corner whose four weights all compare == 0 keeps the bits of its position and normal (a NaN weight is not == 0: that
+ * corner is skinned, to NaN). All four terms are always evaluated: a non-finite float in a bone named with weight 0
+ * yields NaN. A singular blend gives NaN normals and finite positions.
+ * pt_pose_set_skin copies the influences to the device: tri_bones / tri_weights hold 12 entries per record of the
+ * pose (3 corners x 4, in the order of its tri_rest), raster_bones / raster_weights 12 per raster triangle; the raster
+ * arrays are required exactly when the pose has a raster list (PT_ERR_ARG otherwise, and for null tri arrays). A
+ * second call replaces the skin; pt_pose_destroy releases it.
+ * pt_pose_apply_skin is pt_pose_apply with bones16 (n_bones in [1, 4096] glm column-major mat4s, absolute: every call
+ * skins the rest lists) in place of the object matrices: the same refits, displacement records from whichever list
+ * is current, one synchronisation, out_ms from the first skin kernel to the end of the tree derivations. The two
+ * calls may alternate on one pose. All checks run before the first launch: on an error the pose, the buffers, their
+ * trees and the pass are unchanged. PT_ERR_STATE: the pose has no skin. PT_ERR_ARG: null bones16, n_bones out of range
+ * or <= the largest index of the skin. Otherwise whatever pt_pose_apply reports, for the same causes. */
+int pt_pose_set_skin(uint32_t pose, const uint16_t* tri_bones, const float* tri_weights,
+                     const uint16_t* raster_bones, const float* raster_weights);
+int pt_pose_apply_skin(uint32_t pose, const float* bones16, int n_bones, uint32_t tri_out, uint32_t node_out,
+                       uint32_t raster_pass, int motion, float* out_ms);
 int pt_pose_destroy(uint32_t pose);
 /* A rasterize pass drawing another (bound) rasterize pass's triangles and tree: the reference has one G-buffer pass;
  * a driver with several G-buffer targets (frames in flight) binds one and shares it. Rebinding `pass` ends the share;

@@ -39,6 +39,17 @@ struct DevFree {
   void operator()(void* p) const { (void)hipFree(p); }
 };
 
+// the skin's device copies (pt_pose_set_skin)
+void free_skin(Pose& p) {
+  void* dev[] = {p.sk_tri_bones, p.sk_tri_weights, p.sk_r_bones, p.sk_r_weights};
+  for (void* d : dev)
+    if (d) (void)hipFree(d);
+  p.sk_tri_bones = p.sk_r_bones = nullptr;
+  p.sk_tri_weights = p.sk_r_weights = nullptr;
+  p.skinned = false;
+  p.skin_max = 0;
+}
+
 }  // namespace
 
 namespace ptapi {
@@ -67,6 +78,7 @@ void free_pose(Pose& p) {
   if (p.r_obj) (void)hipFree(p.r_obj);
   if (p.disp_spare) (void)hipFree(p.disp_spare);
   if (p.mats_host) (void)hipHostFree(p.mats_host);
+  free_skin(p);
   p = Pose{};
 }
 
@@ -228,6 +240,82 @@ int raster_refit_finish(RasterScene& rs, LbvhTrees& trees, int rc) {
     rc = (int)hipErrorInvalidValue;  // the topology is the bind's: the same depth and as many records
   if (rc == 0) rs.root_ref = trees.dev_info[0];
   else free_raster_refit(rs);
+  return rc;
+}
+
+// What pt_pose_apply and pt_pose_apply_skin do once their own arguments are checked: the checks they share, then a
+// pt_bvh_refit with the placed list standing for tri_in and a pt_raster_pass_refit_device with the placed raster list.
+// fill() writes the call's table into ps.mats_host and returns its floats; place(r_out, s) issues the kernels that
+// write ps.tri_posed and (with a raster list) r_out from the rest lists and ps.mats_dev. Texts carry `who`.
+template <class Fill, class Place>
+int pose_apply_with(const char* who, Pose& ps, uint32_t tri_out, uint32_t node_out, uint32_t raster_pass, int motion,
+                    float* out_ms, Fill fill, Place place) {
+  const std::string w = std::string(who) + ": ";
+  Texture *to = nullptr, *no = nullptr;
+  TRY(refit_pair(who, tri_out, node_out, &to, &no));
+  LbvhRefit* rf = no->refit;
+  if (rf->n != ps.ntris) return err(PT_ERR_ARG, w + "the pose holds another triangle count than the build");
+  Pass* p = nullptr;
+  if (raster_pass) {
+    if (!ps.rtris) return err(PT_ERR_ARG, w + "the pose was created without a raster list");
+    TRY(raster_pass_of(raster_pass, &p, w.c_str()));
+    TRY(refit_pass(who, p));
+    if (p->raster.ntris != ps.rtris) return err(PT_ERR_ARG, w + "the pose holds another raster triangle count");
+  }
+  // displacement records: the pass's own are rewritten where they lie, else the pair a pose without motion set aside
+  float4* disp = nullptr;
+  if (p && motion) {
+    disp = p->raster.disp ? p->raster.disp : ps.disp_spare;
+    if (!disp && hipMalloc((void**)&disp, (size_t)ps.rtris * 3 * sizeof(float4)) != hipSuccess)
+      return err(PT_ERR_HIP, w + "out of device memory");
+    if (disp == ps.disp_spare) ps.disp_spare = nullptr;
+  }
+  const size_t table_floats = fill();
+  hipStream_t s = g.stream;
+  int rc = (int)hipMemcpyAsync(ps.mats_dev, ps.mats_host, table_floats * sizeof(float), hipMemcpyHostToDevice, s);
+  if (rc != 0) {
+    if (disp && disp != p->raster.disp) ps.disp_spare = disp;
+    return hip_err((hipError_t)rc, who);
+  }
+  if (p) {
+    if (motion) {
+      p->raster.disp = disp;
+    } else if (p->raster.disp) {  // left without records, as a refit leaves it; no draw reads them (see the header)
+      if (ps.disp_spare) (void)hipFree(ps.disp_spare);
+      ps.disp_spare = p->raster.disp;
+      p->raster.disp = nullptr;
+    }
+  }
+  EventTimer timer(out_ms);
+  timer.start(s);
+  const int nxt = ps.cur ^ 1;
+  rc = place(ps.r_list[nxt], s);
+  if (rc == 0) rc = lbvh_refit_reorder(*rf, ps.tri_posed, (float*)to->dev, s);
+  if (rc == 0) rc = lbvh_refit_nodes(*rf, (float*)no->dev, ps.tri_posed, kTriEncoded, s);
+  TreesPtr trees(new LbvhTrees, delete_trees);
+  const bool launched = rc == 0;
+  const int trc = launched ? lbvh_trees_launch(g_lbvh, (const float*)no->dev, rf->nnodes, *trees, s, rf->err) : 0;
+  // the pass's refit with the new list; out_ms ends with its derivation, before the copies that follow it
+  TreesGuard rtrees;
+  const bool raster_launched = p && launched && trc == 0;
+  int rrc = raster_launched ? raster_refit_issue(p->raster, ps.r_list[nxt], rtrees.t, s) : 0;
+  timer.stop(s);
+  if (raster_launched && rrc == 0) {
+    rrc = raster_refit_copy(p->raster, rtrees.t, s);
+    if (rrc == 0 && motion)
+      rrc = raster_disp(p->raster.geom, ps.r_list[ps.cur], ps.r_list[nxt], ps.rtris, p->raster.disp, s);
+  }
+  rc = sync_after(who, rc == 0 ? PT_OK : hip_err((hipError_t)rc, who), s);  // the one wait
+  timer.read();
+  rc = refit_pair_commit(who, to, no, trees, trc, rc);
+  if (ps.rtris && launched) ps.cur = nxt;
+  if (p) {
+    rrc = raster_refit_finish(p->raster, rtrees.t, rc == PT_OK ? rrc : (int)hipErrorUnknown);
+    if (rrc != 0) {
+      drop_disp(p);
+      if (rc == PT_OK) rc = hip_err((hipError_t)rrc, (w + "refitting the rasterize pass").c_str());
+    }
+  }
   return rc;
 }
 
@@ -611,87 +699,104 @@ int pt_pose_apply(uint32_t pose, const float* mats16, int n_obj, uint32_t tri_ou
   Pose& ps = *pit->second;
   if (!mats16) return err(PT_ERR_ARG, "pt_pose_apply: null mats16");
   if (n_obj < 1 || n_obj > kPoseMaxObjects) return err(PT_ERR_ARG, "pt_pose_apply: n_obj must be in [1, 4096]");
-  // a pt_bvh_refit with the posed list standing for tri_in, and a pt_raster_pass_refit_device with the posed raster list
-  Texture *to = nullptr, *no = nullptr;
-  TRY(refit_pair("pt_pose_apply", tri_out, node_out, &to, &no));
-  LbvhRefit* rf = no->refit;
-  if (rf->n != ps.ntris) return err(PT_ERR_ARG, "pt_pose_apply: the pose holds another triangle count than the build");
-  Pass* p = nullptr;
-  if (raster_pass) {
-    if (!ps.rtris) return err(PT_ERR_ARG, "pt_pose_apply: the pose was created without a raster list");
-    TRY(raster_pass_of(raster_pass, &p, "pt_pose_apply: "));
-    TRY(refit_pass("pt_pose_apply", p));
-    if (p->raster.ntris != ps.rtris) return err(PT_ERR_ARG, "pt_pose_apply: the pose holds another raster triangle count");
-  }
-  // displacement records: the pass's own are rewritten where they lie, else the pair a pose without motion set aside
-  float4* disp = nullptr;
-  if (p && motion) {
-    disp = p->raster.disp ? p->raster.disp : ps.disp_spare;
-    if (!disp && hipMalloc((void**)&disp, (size_t)ps.rtris * 3 * sizeof(float4)) != hipSuccess)
-      return err(PT_ERR_HIP, "pt_pose_apply: out of device memory");
-    if (disp == ps.disp_spare) ps.disp_spare = nullptr;
-  }
   // the table: each matrix with the cofactor columns of its upper 3x3 (cross products of its columns), once per object
-  for (int k = 0; k < n_obj; ++k) {
-    const float* m = mats16 + (size_t)k * 16;
-    float* o = ps.mats_host + (size_t)k * kPoseMatFloats;
-    memcpy(o, m, 16 * sizeof(float));
-    const glsl::v3 c0 = glsl::mk(m[0], m[1], m[2]), c1 = glsl::mk(m[4], m[5], m[6]), c2 = glsl::mk(m[8], m[9], m[10]);
-    const glsl::v3 a[3] = {glsl::cross(c1, c2), glsl::cross(c2, c0), glsl::cross(c0, c1)};
-    for (int j = 0; j < 3; ++j) {
-      o[16 + 3 * j] = a[j].x;
-      o[17 + 3 * j] = a[j].y;
-      o[18 + 3 * j] = a[j].z;
+  auto fill = [&] {
+    for (int k = 0; k < n_obj; ++k) {
+      const float* m = mats16 + (size_t)k * 16;
+      float* o = ps.mats_host + (size_t)k * kPoseMatFloats;
+      memcpy(o, m, 16 * sizeof(float));
+      const glsl::v3 c0 = glsl::mk(m[0], m[1], m[2]), c1 = glsl::mk(m[4], m[5], m[6]), c2 = glsl::mk(m[8], m[9], m[10]);
+      const glsl::v3 a[3] = {glsl::cross(c1, c2), glsl::cross(c2, c0), glsl::cross(c0, c1)};
+      for (int j = 0; j < 3; ++j) {
+        o[16 + 3 * j] = a[j].x;
+        o[17 + 3 * j] = a[j].y;
+        o[18 + 3 * j] = a[j].z;
+      }
     }
-  }
-  hipStream_t s = g.stream;
-  int rc = (int)hipMemcpyAsync(ps.mats_dev, ps.mats_host, (size_t)n_obj * kPoseMatFloats * sizeof(float),
-                               hipMemcpyHostToDevice, s);
-  if (rc != 0) {
-    if (disp && disp != p->raster.disp) ps.disp_spare = disp;
-    return hip_err((hipError_t)rc, "pt_pose_apply");
-  }
-  if (p) {
-    if (motion) {
-      p->raster.disp = disp;
-    } else if (p->raster.disp) {  // left without records, as a refit leaves it; no draw reads them (see the header)
-      if (ps.disp_spare) (void)hipFree(ps.disp_spare);
-      ps.disp_spare = p->raster.disp;
-      p->raster.disp = nullptr;
+    return (size_t)n_obj * kPoseMatFloats;
+  };
+  auto place = [&](float* r_out, hipStream_t s) {
+    int rc = pose_tris_launch(ps.tri_rest, ps.ntris, ps.mats_dev, n_obj, ps.tri_posed, s);
+    if (rc == 0 && ps.rtris) rc = pose_raster_launch(ps.r_rest, ps.r_obj, ps.rtris, ps.mats_dev, n_obj, r_out, s);
+    return rc;
+  };
+  return pose_apply_with("pt_pose_apply", ps, tri_out, node_out, raster_pass, motion, out_ms, fill, place);
+}
+
+int pt_pose_set_skin(uint32_t pose, const uint16_t* tri_bones, const float* tri_weights, const uint16_t* raster_bones,
+                     const float* raster_weights) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  auto pit = g.poses.find(pose);
+  if (pit == g.poses.end()) return err(PT_ERR_INVALID_HANDLE, "pt_pose_set_skin: unknown pose");
+  Pose& ps = *pit->second;
+  if (!tri_bones || !tri_weights) return err(PT_ERR_ARG, "pt_pose_set_skin: null tri_bones or tri_weights");
+  if (ps.rtris ? !raster_bones || !raster_weights : raster_bones || raster_weights)
+    return err(PT_ERR_ARG, ps.rtris ? "pt_pose_set_skin: the pose has a raster list and needs its influences"
+                                    : "pt_pose_set_skin: raster influences for a pose without a raster list");
+  // the new skin whole, then the old one released: a failed call leaves the pose as it was
+  const size_t nt = (size_t)ps.ntris * 12, nr = (size_t)ps.rtris * 12;
+  std::unique_ptr<void, DevFree> tb, tw, rb, rw;
+  auto up = [](std::unique_ptr<void, DevFree>& d, const void* src, size_t bytes) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
+    d.reset(p);
+    if (e == hipSuccess) e = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, g.stream);
+    return e;
+  };
+  hipError_t e = up(tb, tri_bones, nt * sizeof(uint16_t));
+  if (e == hipSuccess) e = up(tw, tri_weights, nt * sizeof(float));
+  if (e == hipSuccess && nr) e = up(rb, raster_bones, nr * sizeof(uint16_t));
+  if (e == hipSuccess && nr) e = up(rw, raster_weights, nr * sizeof(float));
+  const hipError_t es = hipStreamSynchronize(g.stream);  // the caller's arrays are free again, also after a failure
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_err(e, "pt_pose_set_skin");
+  int mx = 0;
+  for (size_t i = 0; i < nt; ++i) mx = std::max(mx, (int)tri_bones[i]);
+  for (size_t i = 0; i < nr; ++i) mx = std::max(mx, (int)raster_bones[i]);
+  free_skin(ps);  // an apply has completed: nothing reads the old influences
+  ps.sk_tri_bones = (uint16_t*)tb.release();
+  ps.sk_tri_weights = (float*)tw.release();
+  ps.sk_r_bones = (uint16_t*)rb.release();
+  ps.sk_r_weights = (float*)rw.release();
+  ps.skin_max = mx;
+  ps.skinned = true;
+  return PT_OK;
+}
+
+int pt_pose_apply_skin(uint32_t pose, const float* bones16, int n_bones, uint32_t tri_out, uint32_t node_out,
+                       uint32_t raster_pass, int motion, float* out_ms) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  TRY(ensure_init());
+  auto pit = g.poses.find(pose);
+  if (pit == g.poses.end()) return err(PT_ERR_INVALID_HANDLE, "pt_pose_apply_skin: unknown pose");
+  Pose& ps = *pit->second;
+  if (!ps.skinned) return err(PT_ERR_STATE, "pt_pose_apply_skin: the pose has no skin (pt_pose_set_skin)");
+  if (!bones16) return err(PT_ERR_ARG, "pt_pose_apply_skin: null bones16");
+  if (n_bones < 1 || n_bones > kPoseMaxObjects)
+    return err(PT_ERR_ARG, "pt_pose_apply_skin: n_bones must be in [1, 4096]");
+  if (n_bones <= ps.skin_max)
+    return err(PT_ERR_ARG, "pt_pose_apply_skin: the skin names bone " + std::to_string(ps.skin_max) + ", n_bones is " +
+                               std::to_string(n_bones));
+  // the table: the 12 affine floats of each bone as three rows of four, permuted only (the bits are the caller's)
+  static_assert(kSkinBoneFloats <= kPoseMatFloats, "the bone table lies in the pose's matrix table");
+  auto fill = [&] {
+    for (int k = 0; k < n_bones; ++k) {
+      const float* m = bones16 + (size_t)k * 16;
+      float* o = ps.mats_host + (size_t)k * kSkinBoneFloats;
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) o[4 * r + c] = m[4 * c + r];
     }
-  }
-  EventTimer timer(out_ms);
-  timer.start(s);
-  const int nxt = ps.cur ^ 1;
-  rc = pose_tris_launch(ps.tri_rest, ps.ntris, ps.mats_dev, n_obj, ps.tri_posed, s);
-  if (rc == 0 && ps.rtris) rc = pose_raster_launch(ps.r_rest, ps.r_obj, ps.rtris, ps.mats_dev, n_obj, ps.r_list[nxt], s);
-  if (rc == 0) rc = lbvh_refit_reorder(*rf, ps.tri_posed, (float*)to->dev, s);
-  if (rc == 0) rc = lbvh_refit_nodes(*rf, (float*)no->dev, ps.tri_posed, kTriEncoded, s);
-  TreesPtr trees(new LbvhTrees, delete_trees);
-  const bool launched = rc == 0;
-  const int trc = launched ? lbvh_trees_launch(g_lbvh, (const float*)no->dev, rf->nnodes, *trees, s, rf->err) : 0;
-  // the pass's refit with the new list; out_ms ends with its derivation, before the copies that follow it
-  TreesGuard rtrees;
-  const bool raster_launched = p && launched && trc == 0;
-  int rrc = raster_launched ? raster_refit_issue(p->raster, ps.r_list[nxt], rtrees.t, s) : 0;
-  timer.stop(s);
-  if (raster_launched && rrc == 0) {
-    rrc = raster_refit_copy(p->raster, rtrees.t, s);
-    if (rrc == 0 && motion)
-      rrc = raster_disp(p->raster.geom, ps.r_list[ps.cur], ps.r_list[nxt], ps.rtris, p->raster.disp, s);
-  }
-  rc = sync_after("pt_pose_apply", rc == 0 ? PT_OK : hip_err((hipError_t)rc, "pt_pose_apply"), s);  // the one wait
-  timer.read();
-  rc = refit_pair_commit("pt_pose_apply", to, no, trees, trc, rc);
-  if (ps.rtris && launched) ps.cur = nxt;
-  if (p) {
-    rrc = raster_refit_finish(p->raster, rtrees.t, rc == PT_OK ? rrc : (int)hipErrorUnknown);
-    if (rrc != 0) {
-      drop_disp(p);
-      if (rc == PT_OK) rc = hip_err((hipError_t)rrc, "pt_pose_apply: refitting the rasterize pass");
-    }
-  }
-  return rc;
+    return (size_t)n_bones * kSkinBoneFloats;
+  };
+  auto place = [&](float* r_out, hipStream_t s) {
+    int rc = skin_tris_launch(ps.tri_rest, ps.ntris, ps.sk_tri_bones, ps.sk_tri_weights, ps.mats_dev, n_bones,
+                              ps.tri_posed, s);
+    if (rc == 0 && ps.rtris)
+      rc = skin_raster_launch(ps.r_rest, ps.rtris, ps.sk_r_bones, ps.sk_r_weights, ps.mats_dev, n_bones, r_out, s);
+    return rc;
+  };
+  return pose_apply_with("pt_pose_apply_skin", ps, tri_out, node_out, raster_pass, motion, out_ms, fill, place);
 }
 
 int pt_debug_pose_raster(uint32_t pose, int which, float* host_out, size_t cap, size_t* n) {

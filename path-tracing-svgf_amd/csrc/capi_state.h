@@ -283,6 +283,11 @@ struct Pose {
   float* mats_dev = nullptr;   // kPoseMaxObjects x kPoseMatFloats
   float* mats_host = nullptr;  // pinned staging of the same size
   float4* disp_spare = nullptr;  // displacement records taken off the pass by a pose without motion, for the next
+  // the skin (pt_pose_set_skin): four bones and four weights per corner, three corners per record / raster triangle
+  bool skinned = false;
+  int skin_max = 0;  // the largest bone index the skin names
+  uint16_t *sk_tri_bones = nullptr, *sk_r_bones = nullptr;
+  float *sk_tri_weights = nullptr, *sk_r_weights = nullptr;
 };
 
 struct Lib {

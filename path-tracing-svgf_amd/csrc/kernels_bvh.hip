@@ -953,7 +953,134 @@ __global__ void __launch_bounds__(256) pose_raster(const float* __restrict__ res
   o[3] = nv.x; o[4] = nv.y; o[5] = nv.z;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Skinned objects (skin_tris, skin_raster): rest-pose corners placed by a blend of up to four bone matrices, defined
+// by tests/skin_ref.py. A corner carries four bone indices (uint16, 8 bytes) and four weights (float, 16 bytes). The
+// table holds kSkinBoneFloats per bone: three float4 rows (m[k], m[4+k], m[8+k], m[12+k]), k = 0..2, of the glm
+// column-major mat4, so an influence is three 16-byte loads through the cache. Every float32 operation is spelled as
+// the definition evaluates it; a corner whose four weights all compare == 0, or that names a bone >= n_bones (checked
+// before the table is read), is copied bit for bit.
+
+struct SkinBlend {
+  float4 r[3];  // row k: M[k], M[4+k], M[8+k], M[12+k]
+};
+
+// the corner's influences; false: the corner is kept
+__device__ __forceinline__ bool skin_influences(const uint16_t* __restrict__ bones, const float* __restrict__ weights,
+                                                size_t corner, int n_bones, int b[4], float w[4]) {
+  const float4 wv = *reinterpret_cast<const float4*>(weights + 4 * corner);
+  w[0] = wv.x; w[1] = wv.y; w[2] = wv.z; w[3] = wv.w;
+  if (w[0] == 0.0f && w[1] == 0.0f && w[2] == 0.0f && w[3] == 0.0f) return false;
+  const uint2 bv = *reinterpret_cast<const uint2*>(bones + 4 * corner);
+  b[0] = (int)(bv.x & 0xffffu); b[1] = (int)(bv.x >> 16);
+  b[2] = (int)(bv.y & 0xffffu); b[3] = (int)(bv.y >> 16);
+  return b[0] < n_bones && b[1] < n_bones && b[2] < n_bones && b[3] < n_bones;
+}
+
+// M[j] = ((w0 B0[j] + w1 B1[j]) + w2 B2[j]) + w3 B3[j]: all four terms, whatever the weights
+__device__ __forceinline__ float skin_mix(const float w[4], float b0, float b1, float b2, float b3) {
+  const float mul0 = w[0] * b0, mul1 = w[1] * b1, mul2 = w[2] * b2, mul3 = w[3] * b3;
+  const float add0 = mul0 + mul1, add1 = add0 + mul2;
+  return add1 + mul3;
+}
+
+__device__ __forceinline__ SkinBlend skin_blend(const float4* __restrict__ table, const int b[4], const float w[4]) {
+  SkinBlend m;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float4 b0 = table[3 * b[0] + k], b1 = table[3 * b[1] + k], b2 = table[3 * b[2] + k],
+                 b3 = table[3 * b[3] + k];
+    m.r[k] = make_float4(skin_mix(w, b0.x, b1.x, b2.x, b3.x), skin_mix(w, b0.y, b1.y, b2.y, b3.y),
+                         skin_mix(w, b0.z, b1.z, b2.z, b3.z), skin_mix(w, b0.w, b1.w, b2.w, b3.w));
+  }
+  return m;
+}
+
+// pose_point's expression with the blended matrix
+__device__ __forceinline__ glsl::v3 skin_point(const SkinBlend& m, glsl::v3 p) {
+  float r[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float mul0 = m.r[k].x * p.x, mul1 = m.r[k].y * p.y, mul2 = m.r[k].z * p.z, mul3 = m.r[k].w * 1.0f;
+    const float add0 = mul0 + mul1, add1 = mul2 + mul3;
+    r[k] = add0 + add1;
+  }
+  return glsl::mk(r[0], r[1], r[2]);
+}
+
+// pose_normal with the cofactor columns of the blended matrix, computed per corner
+__device__ __forceinline__ glsl::v3 skin_normal(const SkinBlend& m, glsl::v3 n) {
+  const glsl::v3 c0 = glsl::mk(m.r[0].x, m.r[1].x, m.r[2].x), c1 = glsl::mk(m.r[0].y, m.r[1].y, m.r[2].y),
+                 c2 = glsl::mk(m.r[0].z, m.r[1].z, m.r[2].z);
+  const glsl::v3 a0 = glsl::cross(c1, c2), a1 = glsl::cross(c2, c0), a2 = glsl::cross(c0, c1);
+  const float a[9] = {a0.x, a0.y, a0.z, a1.x, a1.y, a1.z, a2.x, a2.y, a2.z};
+  return pose_normal(a, n);
+}
+
+// pose_tris's mapping: one thread per 12-byte texel, 15 per record; texels 0-2 are p1-p3, 3-5 n1-n3, the rest is
+// copied. A position or normal texel reads the influences of its corner (3 rec + tex % 3) and blends.
+__global__ void __launch_bounds__(256) skin_tris(const float* __restrict__ rest, int n,
+                                                  const uint16_t* __restrict__ bones,
+                                                  const float* __restrict__ weights,
+                                                  const float4* __restrict__ table, int n_bones,
+                                                  float* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)n * 15) return;
+  const size_t rec = t / 15;
+  const int tex = (int)(t - rec * 15);
+  glsl::v3 v = glsl::mk(rest[3 * t], rest[3 * t + 1], rest[3 * t + 2]);
+  if (tex < 6) {
+    int b[4];
+    float w[4];
+    if (skin_influences(bones, weights, rec * 3 + (size_t)(tex < 3 ? tex : tex - 3), n_bones, b, w)) {
+      const SkinBlend m = skin_blend(table, b, w);
+      v = tex < 3 ? skin_point(m, v) : skin_normal(m, v);
+    }
+  }
+  out[3 * t] = v.x;
+  out[3 * t + 1] = v.y;
+  out[3 * t + 2] = v.z;
+}
+
+// pose_raster's mapping: one thread per vertex of the raster list (pos3 + nrm3), one blend for both.
+__global__ void __launch_bounds__(256) skin_raster(const float* __restrict__ rest, int ntris,
+                                                    const uint16_t* __restrict__ bones,
+                                                    const float* __restrict__ weights,
+                                                    const float4* __restrict__ table, int n_bones,
+                                                    float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)ntris * 3) return;
+  const float* f = rest + 6 * i;
+  glsl::v3 p = glsl::mk(f[0], f[1], f[2]), nv = glsl::mk(f[3], f[4], f[5]);
+  int b[4];
+  float w[4];
+  if (skin_influences(bones, weights, i, n_bones, b, w)) {
+    const SkinBlend m = skin_blend(table, b, w);
+    p = skin_point(m, p);
+    nv = skin_normal(m, nv);
+  }
+  float* o = out + 6 * i;
+  o[0] = p.x; o[1] = p.y; o[2] = p.z;
+  o[3] = nv.x; o[4] = nv.y; o[5] = nv.z;
+}
+
 }  // namespace
+
+int skin_tris_launch(const float* rest, int n, const uint16_t* bones, const float* weights, const float* table,
+                     int n_bones, float* out, hipStream_t s) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(skin_tris, dim3((unsigned)(((size_t)n * 15 + 255) / 256)), dim3(256), 0, s, rest, n, bones,
+                     weights, reinterpret_cast<const float4*>(table), n_bones, out);
+  return (int)hipGetLastError();
+}
+
+int skin_raster_launch(const float* rest, int ntris, const uint16_t* bones, const float* weights, const float* table,
+                       int n_bones, float* out, hipStream_t s) {
+  if (ntris <= 0) return 0;
+  hipLaunchKernelGGL(skin_raster, dim3((unsigned)(((size_t)ntris * 3 + 255) / 256)), dim3(256), 0, s, rest, ntris,
+                     bones, weights, reinterpret_cast<const float4*>(table), n_bones, out);
+  return (int)hipGetLastError();
+}
 
 int pose_tris_launch(const float* rest, int n, const float* mats, int n_obj, float* out, hipStream_t s) {
   if (n <= 0) return 0;

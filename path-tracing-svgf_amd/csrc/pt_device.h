@@ -657,5 +657,16 @@ int pose_tris_launch(const float* rest, int n, const float* mats, int n_obj, flo
 int pose_raster_launch(const float* rest, const int* obj, int ntris, const float* mats, int n_obj, float* out,
                        hipStream_t s);
 
+// Skinned objects (DESIGN.md "Skinned objects", tests/skin_ref.py): out = the rest-pose records with every corner
+// placed by the blend of its four bones. bones / weights hold four entries per corner (3 corners per record or raster
+// triangle); table holds kSkinBoneFloats per bone, 16-byte aligned: the rows (m[k], m[4+k], m[8+k], m[12+k]), k = 0..2,
+// of the glm column-major mat4. Corners whose weights all compare == 0, or that name a bone >= n_bones, are copied
+// bit for bit.
+constexpr int kSkinBoneFloats = 12;
+int skin_tris_launch(const float* rest, int n, const uint16_t* bones, const float* weights, const float* table,
+                     int n_bones, float* out, hipStream_t s);
+int skin_raster_launch(const float* rest, int ntris, const uint16_t* bones, const float* weights, const float* table,
+                       int n_bones, float* out, hipStream_t s);
+
 }  // namespace ptk
 #endif

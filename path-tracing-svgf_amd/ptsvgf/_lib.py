@@ -110,6 +110,8 @@ _PT_SIGS = [
     ("pt_raster_pass_set_prev_vertices", C.c_int, [_u32, _vp, _vp, C.c_size_t]),
     ("pt_pose_create", C.c_int, [_u32, _fp, C.c_size_t, C.POINTER(C.c_int), _u32p]),
     ("pt_pose_apply", C.c_int, [_u32, _fp, C.c_int, _u32, _u32, _u32, C.c_int, _fp]),
+    ("pt_pose_set_skin", C.c_int, [_u32, C.POINTER(C.c_uint16), _fp, C.POINTER(C.c_uint16), _fp]),
+    ("pt_pose_apply_skin", C.c_int, [_u32, _fp, C.c_int, _u32, _u32, _u32, C.c_int, _fp]),
     ("pt_pose_destroy", C.c_int, [_u32]),
     ("pt_raster_pass_share", C.c_int, [_u32, _u32]),
     ("pt_raster_pass_adopt", C.c_int, [_u32, C.c_int, C.c_int]),

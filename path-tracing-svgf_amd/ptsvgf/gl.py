@@ -154,6 +154,43 @@ def pose_apply(pose: int, mats, tri_out: int, node_out: int, raster_pass: int = 
     return ms.value
 
 
+def pose_set_skin(pose: int, tri_bones, tri_weights, raster_bones=None, raster_weights=None) -> None:
+    """pt_pose_set_skin: four bone indices (uint16) and four weights (float32) per corner, 12 entries per record of
+    the pose's triangle list and, for a pose with a raster list, 12 per raster triangle. A second call replaces the
+    skin."""
+    def pair(bones, weights, what):
+        if bones is None and weights is None:
+            return None, None, None, None
+        if bones is None or weights is None:
+            raise ValueError(f"pose_set_skin: {what} bones and weights go together")
+        b = np.asarray(bones)
+        if b.size and (b.min() < 0 or b.max() > 0xFFFF):
+            raise ValueError(f"pose_set_skin: {what} bone index outside uint16")
+        b = np.ascontiguousarray(b, np.uint16).reshape(-1)
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        if b.size != w.size or b.size % 12:
+            raise ValueError(f"pose_set_skin: {b.size} {what} bones for {w.size} weights (12 per triangle each)")
+        return b, w, b.ctypes.data_as(C.POINTER(C.c_uint16)), fptr(w)
+
+    tb, tw, tbp, twp = pair(tri_bones, tri_weights, "triangle")
+    rb, rw, rbp, rwp = pair(raster_bones, raster_weights, "raster")
+    n = C.c_size_t()
+    check(pt().pt_debug_pose_raster(pose, 0, None, 0, C.byref(n)))  # also: the pose exists
+    if rb is not None and rb.size * 18 != n.value * 12:
+        raise ValueError(f"pose_set_skin: {rb.size // 12} raster triangles of influences for {n.value // 18}")
+    check(pt().pt_pose_set_skin(pose, tbp, twp, rbp, rwp))
+
+
+def pose_apply_skin(pose: int, bones, tri_out: int, node_out: int, raster_pass: int = 0, motion: bool = True) -> float:
+    """pt_pose_apply_skin: pose_apply with the pose's skin blended from bones ((n_bones, 16), glm column-major,
+    absolute) in place of one matrix per object. Returns device ms."""
+    m = np.ascontiguousarray(bones, np.float32).reshape(-1, 16)
+    ms = C.c_float()
+    check(pt().pt_pose_apply_skin(pose, fptr(m), m.shape[0], tri_out, node_out, raster_pass, 1 if motion else 0,
+                                  C.byref(ms)))
+    return ms.value
+
+
 def pose_destroy(pose: int) -> None:
     check(pt().pt_pose_destroy(pose))
 

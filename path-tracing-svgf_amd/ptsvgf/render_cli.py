@@ -3,6 +3,8 @@ debug-view switch of its GUI (main.cpp:398-415, gui_config.h:7-45) as a flag, th
 written as PNG and, optionally, the selected plane's raw floats as PFM.
 
     python -m ptsvgf.render_cli --width 800 --height 800 --frames 8 --view final_pic --png out.png
+
+--sway DEG bends the bench scene's plant on the device each frame (Renderer.set_skin / skin_objects).
 """
 from __future__ import annotations
 
@@ -35,6 +37,30 @@ def write_pfm(path: str, rgb: np.ndarray) -> None:
         f.write(np.ascontiguousarray(rgb[..., :3], "<f4").tobytes())
 
 
+SWAY_BONES = 8
+SWAY_PERIOD = 48  # frames per swing
+
+
+def _sway_setup(r, scene, obj: int = 2):
+    """--sway: the scene rebuilt on the device with its raster list, the corners of object `obj` (the bench scene's
+    plant) skinned to a chain of SWAY_BONES bones up its vertical extent. Returns bend_deg -> the chain's matrices."""
+    from . import skin
+
+    tp, rp = skin.corner_positions(scene.tri_enc), skin.corner_positions_raster(scene.raster)
+    tmask = np.repeat(scene.tri_enc[:, 42] == float(obj), 3)
+    rmask = np.repeat(np.asarray(scene.raster_obj) == obj, 3)
+    if not tmask.any():
+        raise SystemExit(f"--sway: the scene has no object {obj}")
+    lo, hi = tp[tmask].min(axis=0), tp[tmask].max(axis=0)
+    base = np.array([(lo[0] + hi[0]) / 2, lo[1], (lo[2] + hi[2]) / 2])
+    tip = np.array([base[0], hi[1], base[2]])
+    r.rebuild_bvh(raster=scene.raster)
+    tb, tw = skin.chain_weights(tp, base, tip, SWAY_BONES, tmask)
+    rb, rw = skin.chain_weights(rp, base, tip, SWAY_BONES, rmask)
+    r.set_skin(tb, tw, rb, rw)
+    return lambda deg: skin.chain_bones(base, tip, SWAY_BONES, deg, (0.0, 0.0, 1.0))
+
+
 def main(argv=None) -> int:
     from . import gl
     from .camera import parameter_config
@@ -59,6 +85,8 @@ def main(argv=None) -> int:
                     help="pool the sample statistics over frames, the pooled weight held to W >= 2 (needs --adaptive)")
     ap.add_argument("--adaptive-rule", default="relative", choices=("relative", "absolute"),
                     help="TAU bounds the error relative to the mean luminance, or absolutely (needs --adaptive-pool)")
+    ap.add_argument("--sway", type=float, default=None, metavar="DEG",
+                    help="bend the plant (object 2) by an 8-bone chain, the angle a sine over the frames of this amplitude")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
 
@@ -72,9 +100,12 @@ def main(argv=None) -> int:
         r = Renderer(scene, a.width, a.height, parameter_config(), mode=a.mode, run_taa=True, run_output=True,
                      spp=a.spp, adaptive=a.adaptive, adaptive_pool=a.adaptive_pool, adaptive_rule=a.adaptive_rule)
         r.set_view(a.view)
-        for _ in range(a.frames):
+        sway = _sway_setup(r, scene) if a.sway is not None else None
+        for f in range(a.frames):
             if a.orbit:
                 r.camera.orbit(a.orbit, 0.0)
+            if sway is not None:
+                r.skin_objects(sway(a.sway * float(np.sin(2.0 * np.pi * (f + 1) / SWAY_PERIOD))))
             r.frame()
         gl.sync()
         write_png(a.png, gl.readback(r.planes()["output"]))

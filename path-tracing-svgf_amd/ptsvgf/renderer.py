@@ -311,6 +311,8 @@ class Renderer:
         self.object_motion = True
         self._pose = None       # pose_objects: the pt_pose handle, and the rest pose the last rebuild_bvh received
         self._pose_rest = None
+        self._skin = None       # set_skin: the influences of skin_objects, kept with the rest pose
+        self._skin_set = False  # whether the pose holds them
         self._motion_records = self._motion_pending = False
         self._last_raster =np.ascontiguousarray(scene.raster, np.float32).reshape(-1)
         raster_prog = _prog("rasterize_frag.frag", "rasterize_vert.vert")
@@ -1235,6 +1237,21 @@ class Renderer:
             gl.pose_destroy(self._pose)
         self._pose = None
         self._pose_rest = None
+        self._skin = None
+        self._skin_set = False
+
+    def _ensure_pose(self) -> None:
+        """The pose over the rest lists of the last rebuild_bvh, created at the first call that needs it."""
+        if self._pose is None:
+            rest, raster, raster_obj = self._pose_rest
+            if raster is not None and raster_obj is None:
+                # only pose_objects reads the objects, and it refuses a raster list without them: none is named
+                raster_obj = np.full(raster.size // 18, -1, np.int32)
+            src = gl.texture_buffer(rest)
+            try:
+                self._pose = gl.pose_create(src, raster, raster_obj)
+            finally:
+                gl.destroy_texture(src)
 
     def pose_objects(self, mats, motion: bool = True) -> float:
         """Dynamic scenes, rigid (or any affine) motion of whole objects: place every object by one matrix, on the
@@ -1276,16 +1293,87 @@ class Renderer:
             torch.cuda.synchronize()
         if raster is not None and raster_obj is None:
             raise ValueError("pose_objects: no raster_obj (Scene.raster_obj or rebuild_bvh(raster_obj=...))")
-        if self._pose is None:
-            src = gl.texture_buffer(rest)
-            try:
-                self._pose = gl.pose_create(src, raster, raster_obj)
-            finally:
-                gl.destroy_texture(src)
+        self._ensure_pose()
         raster_pass = 0 if raster is None else self.init_pass[0]._handle()
         arm = bool(motion) and raster is not None
         try:
             ms = gl.pose_apply(self._pose, table, self.trianglesTextureBuffer, self.nodesTextureBuffer, raster_pass, arm)
+        except PtError as e:
+            if e.code == -9:  # PT_ERR_STATE
+                raise PtError(e.code, "refit_bvh: " + self._NOT_REBUILT) from e
+            raise
+        if raster is not None:
+            self._motion_records = self._motion_pending = arm
+        return ms
+
+    def set_skin(self, tri_bones, tri_weights, raster_bones=None, raster_weights=None) -> None:
+        """The skin of skin_objects: four bone indices (uint16) and four weights (float32) per corner, as arrays of
+        12 entries per row of the rest `tri_enc` the last rebuild_bvh received (3 corners x 4) and, if that call got a
+        `raster`, 12 per raster triangle (required then, refused otherwise). Weights are not normalised; unused slots
+        carry weight 0 and any valid index; a corner whose weights are all 0 stays where the rest pose has it
+        (ptsvgf.skin.chain_weights makes such arrays for a bending chain). Valid after a rebuild_bvh; kept with the
+        rest pose and dropped wherever it is dropped (rebuild_bvh, refit_bvh, close); a second call replaces it.
+        Raises PtError (PT_ERR_STATE) when rebuild_bvh has not run."""
+        from ._lib import PtError
+
+        if getattr(self, "_pose_rest", None) is None:
+            raise PtError(-9, "refit_bvh: " + self._NOT_REBUILT)
+        rest, raster, _ = self._pose_rest
+
+        def pair(bones, weights, ntris, what):
+            b = np.asarray(bones)
+            if b.size and (b.min() < 0 or b.max() > 0xFFFF):
+                raise ValueError(f"set_skin: {what} bone index outside uint16")
+            b = np.ascontiguousarray(b, np.uint16).reshape(-1)
+            w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+            if b.size != ntris * 12 or w.size != ntris * 12:
+                raise ValueError(f"set_skin: {b.size} bones and {w.size} weights for {ntris} {what} triangles "
+                                 "(12 each per triangle)")
+            return b, w
+
+        if (raster is None) != (raster_bones is None) or (raster is None) != (raster_weights is None):
+            raise ValueError("set_skin: raster_bones and raster_weights are required exactly when rebuild_bvh got a "
+                             "raster list")
+        skin = pair(tri_bones, tri_weights, rest.size // 45, "scene")
+        if raster is not None:
+            skin += pair(raster_bones, raster_weights, raster.size // 18, "raster")
+        self._skin = skin
+        self._skin_set = False
+
+    def skin_objects(self, bones, motion: bool = True) -> float:
+        """Dynamic scenes, geometry that deforms but keeps its topology: linear blend skinning on the device
+        (pt_pose_apply_skin). `bones` is an (n_bones, 16) array (or n_bones 4x4s) of glm column-major matrices as
+        scene.transform returns them, n_bones above every index set_skin received. Every corner is placed by the
+        blend of its four bones, M = ((w0 B0 + w1 B1) + w2 B2) + w3 B3 over the 12 affine floats; positions go through
+        M, normals through its normalised cofactor matrix (tests/skin_ref.py; DESIGN.md "Skinned objects"). Matrices
+        are absolute: each call skins the rest pose of the last rebuild_bvh. Everything after the vertices is
+        pose_objects': the refits, the G-buffer pass, the object motion vectors of the next frame (`motion`), one
+        synchronisation, no vertex data over the bus; the two calls may alternate. The first call after a
+        rebuild_bvh creates the pose and uploads the skin once. Frames already issued finish first. Returns the
+        device ms: both skin kernels, both refits and the walk trees' derivation. Raises PtError (PT_ERR_STATE) when
+        rebuild_bvh or set_skin has not run."""
+        from ._lib import PtError
+
+        if getattr(self, "_pose_rest", None) is None:
+            raise PtError(-9, "refit_bvh: " + self._NOT_REBUILT)
+        if self._skin is None:
+            raise PtError(-9, "skin_objects: no skin (call set_skin after rebuild_bvh)")
+        raster = self._pose_rest[1]
+        table = np.ascontiguousarray(bones, np.float32).reshape(-1, 16)
+        if self._streams is not None:
+            import torch
+
+            self.flush()
+            torch.cuda.synchronize()
+        self._ensure_pose()
+        if not self._skin_set:
+            gl.pose_set_skin(self._pose, *self._skin)
+            self._skin_set = True
+        raster_pass = 0 if raster is None else self.init_pass[0]._handle()
+        arm = bool(motion) and raster is not None
+        try:
+            ms = gl.pose_apply_skin(self._pose, table, self.trianglesTextureBuffer, self.nodesTextureBuffer,
+                                    raster_pass, arm)
         except PtError as e:
             if e.code == -9:  # PT_ERR_STATE
                 raise PtError(e.code, "refit_bvh: " + self._NOT_REBUILT) from e
