@@ -413,6 +413,22 @@ int pt_trace_stats_total(void);
  * per entry (a light's lists hold [1] * that many bytes).
  * *bytes: the allocation. Any output may be NULL. */
 int pt_point_bins_info(uint32_t tri_tex, uint32_t node_tex, int* info8x4, int* dims4, size_t* bytes);
+/* A draw may reuse the work of the pass's last draw when nothing it depends on
+ * has changed (a view that stands still; DESIGN.md "Static view"). Results are
+ * bit for bit those of doing the work again.
+ *  - path-tracing pass, int uniform primary_cache (default 1): the primary stage is
+ *    skipped while eye, cameraRotate, the rows, the tile subset, the geometry and
+ *    the stage's settings are those of the stage the pass last ran. Its state is
+ *    the pass's own; 0 runs the stage in every draw. Bypassed while trace
+ *    statistics or row costs are bound, by pt_kernel = 1 and by pt_pass_draw_batch.
+ *  - rasterize pass, int uniform reuse_static (default 0): the caller's statement
+ *    that nothing outside the library writes this pass's attachments between its
+ *    draws (no write through pt_texture_device_ptr or into wrapped memory). Then a
+ *    draw whose uniforms, triangles and attachments are as the pass's last draw
+ *    left them launches nothing and returns PT_OK. The library tracks its own
+ *    writes (draws of any pass, uploads, pt_tiles_copy, adopt) and every call that
+ *    changes the triangles; a pass with a motion bound always draws.
+ *    PTSVGF_STATIC_REUSE=0 in the environment forces 0. */
 int pt_pass_draw(uint32_t pass);
 /* Draw `count` (1..8) path-tracing passes — the frames of a batch, each with its
  * own uniforms, samplers and attachments, one scene, size and band — as one

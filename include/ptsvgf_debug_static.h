@@ -1,0 +1,39 @@
+/* ptsvgf_debug_static.h — diagnostics of the static-view reuse (DESIGN.md "Static view"): the primary-hit cache of a
+ * path-tracing pass (pass uniform primary_cache) and the G-buffer draw elision of a rasterize pass (pass uniform
+ * reuse_static). Beside ptsvgf_debug.h and with its conventions: entry points tests and tools use to look inside the
+ * library, no part of the drop-in boundary. */
+#ifndef PTSVGF_DEBUG_STATIC_H
+#define PTSVGF_DEBUG_STATIC_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* How many draws of `pass` did the work and how many reused an earlier draw's, since the pass was created.
+ *   a path-tracing pass: *runs counts the draws that ran the primary stage (a pt_pass_draw_batch counts one for each of
+ *     its passes), *reuses those that read the cached primary hit instead; megakernel draws (pt_kernel = 1) count in
+ *     neither;
+ *   a rasterize pass: *runs counts the G-buffer draws that launched, *reuses those that were elided.
+ * PT_ERR_ARG for a pass of any other program. Either pointer may be NULL. */
+int pt_debug_stage_counts(uint32_t pass, uint64_t* runs, uint64_t* reuses);
+
+/* The keys behind both (csrc/static_key.h), for tests of the compare; needs no device. kind 0: the primary stage's
+ * key, 1: the G-buffer draw's. A key is pt_debug_static_key_words(kind) 64-bit words, one per field. */
+int pt_debug_static_key_words(int kind);
+/* *field receives the index of the first word in which keys a and b differ, -1 when they are equal. */
+int pt_debug_static_key_diff(int kind, const uint64_t* a, const uint64_t* b, int words, int* field);
+/* The decision itself: *hit receives 1 when a draw with key `now` may reuse the work of the draw that left `last`
+ * (last_valid: that key describes a completed draw). enabled: for kind 0, no trace statistics or row costs are bound
+ * and primary_cache is not 0; for kind 1, reuse_static is on and no motion bound is bound. Kind 1 also needs the
+ * compact planes the draw writes present and valid in `now`: the fwidth attachment's, and with bound_eye set the world
+ * attachment's. */
+int pt_debug_static_key_hit(int kind, const uint64_t* last, int last_valid, const uint64_t* now, int words, int enabled,
+                            int* hit);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "../../include/ptsvgf_debug_pointbins.h"
+#include "../../include/ptsvgf_debug_static.h"
 #include "../../include/ptsvgf_scene.h"
 #include "capi_state.h"
 #include "glsl_builtins.h"
@@ -118,15 +119,18 @@ int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1, int nsp = 0) {
   const size_t nl = (size_t)wf_list_capacity(W, rows) * 8;  // 8 list segments
   auto up = [&](size_t v) { return (v + al - 1) / al * al; };
   const size_t lists = up(nl * 4 * kLiveBins) * 2 + up(nl * 4 * (1 + kPointBins));
-  size_t total = up(f4) * 10 + up(m * 8) + up(m * 4) + up(m) * 2 + lists * nb + up(m * 8) + up(m * 4) +
+  // (the second up(m * 8) of int2: the primary hit plane hit0, 8 bytes per pixel)
+  size_t total = up(f4) * 10 + up(m * 8) * 2 + up(m * 4) + up(m) * 2 + lists * nb + up(m * 8) + up(m * 4) +
                  up((size_t)nb * kWfCounters * 4) + (nsp ? up((size_t)nsp * n * 16) : 0);
   if (hipMalloc(&b.base, total) != hipSuccess) { b.base = nullptr; return PT_ERR_HIP; }
+  b.gen++;
   char* c = (char*)b.base;
   WFState s0{};
   float4** f4p[10] = {&s0.ray_o, &s0.ray_d, &s0.light, &s0.red, &s0.pend0,
                       &s0.pend1, &s0.pend2, &s0.pend3, &s0.sh_h, &s0.sh_p};
   for (auto q : f4p) { *q = (float4*)c; c += up(f4); }
   s0.hit = (int2*)c; c += up(m * 8);
+  s0.hit0 = (int2*)c; c += up(m * 8);
   s0.seed = (uint32_t*)c; c += up(m * 4);
   s0.occ_h = (uint8_t*)c; c += up(m);
   s0.occ_p = (uint8_t*)c; c += up(m);
@@ -147,6 +151,7 @@ int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1, int nsp = 0) {
     st.sh_h = s0.sh_h + o;
     st.sh_p = s0.sh_p + o;
     st.hit = s0.hit + o;
+    st.hit0 = s0.hit0 + o;
     st.seed = s0.seed + o;
     st.occ_h = s0.occ_h + o;
     st.occ_p = s0.occ_p + o;
@@ -439,8 +444,7 @@ int att_plane(Pass* p, int k, Plane* out) {
   Texture* t = tex_of(p->att[k]);
   int rc = plane_of(t, p, out, "color attachment");
   if (rc != PT_OK) return rc;
-  t->version++;
-  t->aux_valid = false;
+  tex_written(t);  // (a draw into it by any pass)
   return PT_OK;
 }
 
@@ -476,8 +480,7 @@ int copy_plane(Texture* dst, Texture* src, Pass* p, int y0, int y1) {
                           (char*)src->dev + (size_t)(a - src->row0) * rowb, (size_t)(b - a) * rowb,
                           hipMemcpyDeviceToDevice, g.stream));
   }
-  dst->version++;
-  dst->aux_valid = false;
+  tex_written(dst);
   if (src->aux_valid && src->aux) {  // keep the compact side plane in step with its texture
     if (!dst->aux) HIPCHK(hipMalloc((void**)&dst->aux, (size_t)dst->W * dst->rows * 4));
     if (b > a) {
@@ -762,9 +765,62 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
   return PT_OK;
 }
 
+// The key of what the primary stage of the draw `k` of pass p reads (static_key.h; k complete but for leaf_bins,
+// which is scratch): the view, the rows and tiles, the walk settings as the draw uses them, the scene and the trees
+// bound from it, the plane the stage writes and the tile order it sorts. Not in it: frameCounter (the stage does not
+// read it) and the G-buffer hint planes (the bound only prunes the walk; DESIGN.md "The primary's bound as one float").
+ptk::PrimaryKey primary_key(const Pass* p, const PTParams& k, const SceneGPU* sg, int pair_cap) {
+  using namespace ptk;
+  PrimaryKey q{};
+  for (int i = 0; i < 3; ++i) q.w[kPkEye0 + i] = key_bits(k.eye[i]);
+  for (int i = 0; i < 16; ++i) q.w[kPkCamRot0 + i] = key_bits(k.camRot[i]);
+  q.w[kPkW] = key_bits(k.W);
+  q.w[kPkH] = key_bits(k.H);
+  q.w[kPkY0] = key_bits(k.y0);
+  q.w[kPkY1] = key_bits(k.y1);
+  q.w[kPkBandW] = key_bits(g.band_w);
+  q.w[kPkBandH] = key_bits(g.band_h);
+  q.w[kPkBandY0] = key_bits(g.band_y0);
+  q.w[kPkBandY1] = key_bits(g.band_y1);
+  q.w[kPkBandRow0] = key_bits(g.band_row0);
+  q.w[kPkBandRows] = key_bits(g.band_rows);
+  q.w[kPkTileStride] = key_bits(k.tile_stride);
+  q.w[kPkTileOffset] = key_bits(k.tile_offset);
+  q.w[kPkAspectCorrected] = key_bits(k.aspect_corrected);
+  q.w[kPkPrune] = key_bits(k.prune);
+  q.w[kPkClosestTree] = key_bits(k.closest_tree);
+  q.w[kPkPrimaryRaster] = key_bits(k.primary_raster);
+  q.w[kPkScene] = key_bits((const void*)sg);
+  q.w[kPkTriVer] = sg->tri_ver;
+  q.w[kPkNodeVer] = sg->node_ver;
+  q.w[kPkNtris] = key_bits(sg->ntris);
+  q.w[kPkTriGeom] = key_bits((const void*)k.scene.tri_geom);
+  q.w[kPkBvh] = key_bits((const void*)k.scene.bvh);
+  q.w[kPkRootRef] = key_bits(k.scene.root_ref);
+  q.w[kPkBvhAny] = key_bits((const void*)k.scene.bvh_any);
+  q.w[kPkRootAny] = key_bits(k.scene.root_any);
+  q.w[kPkBvh4] = key_bits((const void*)k.scene.bvh4);
+  q.w[kPkRoot4] = key_bits(k.scene.root4);
+  q.w[kPkRoot4c] = key_bits(k.scene.root4c);
+  q.w[kPkLeaves] = key_bits((const void*)k.scene.leaves);
+  q.w[kPkNleaves] = key_bits(k.scene.nleaves);
+  q.w[kPkTriLeaf] = key_bits((const void*)k.scene.tri_leaf);
+  q.w[kPkStackNeed] = key_bits(k.stack_need);
+  q.w[kPkSpill] = key_bits((const void*)k.wf.spill);
+  q.w[kPkPairCap] = key_bits(pair_cap);
+  q.w[kPkPlane] = key_bits((const void*)k.wf.hit0);
+  q.w[kPkPlaneGen] = p->wf.gen;
+  q.w[kPkTileCost] = key_bits((const void*)k.tiles.cost);
+  q.w[kPkTilePerm] = key_bits((const void*)k.tiles.perm_next);
+  return q;
+}
+
 // The wavefront-side fields of a path-tracing pass's PTParams: its wavefront state `st` (its own, or its frame's
 // share of a batch's), counters, budgets, refill, cost-ordered tiles and the primary rasteriser's bins.
-int pt_wf_setup(Pass* p, PTParams& k, SceneGPU* sg, const WFState& st) {
+// key / reuse (a draw of one pass: both, or neither): the primary-hit cache's key of this draw, and whether it may skip
+// the stage.
+int pt_wf_setup(Pass* p, PTParams& k, SceneGPU* sg, const WFState& st, ptk::PrimaryKey* key = nullptr,
+                bool* reuse = nullptr) {
     k.wf = st;
     if (k.wf.spill) k.point_bins = 0;  // deep trees keep the walk (launch_wavefront<.., DEEP>)
     k.wf.row_cost = p->row_cost;
@@ -788,13 +844,33 @@ int pt_wf_setup(Pass* p, PTParams& k, SceneGPU* sg, const WFState& st) {
     // primary rays by tile-binned rasterisation: 1 = of the reference leaves, 2 = of the triangles; 0 = the per-pixel
     // walk. The items are binned to every tile of the band, a tile subset rasterises its own tiles
     const int pr = ui(p, "primary_raster", kPrimaryRasterDefault);
-    if (pr) {
-      // (the triangle rasteriser packs pixel coordinates into 16 bits)
-      const bool tri = pr == 2 && !sg->tri_shared && k.W <= 65536 && k.H <= 65536;
-      TRY(bins_for(p->bins, tri ? sg->ntris : sg->nleaves, k.W, k.y0, k.y1, ui(p, "raster_pair_cap", 0), &k.leaf_bins));
-      k.primary_raster = tri ? 2 : 1;
+    // (the triangle rasteriser packs pixel coordinates into 16 bits)
+    const bool tri = pr == 2 && !sg->tri_shared && k.W <= 65536 && k.H <= 65536;
+    k.primary_raster = pr ? (tri ? 2 : 1) : 0;
+    const int pair_cap = ui(p, "raster_pair_cap", 0);
+    if (reuse) {
+      // the primary-hit cache: a draw whose key equals that of the pass's last stage skips the stage, and with it the
+      // bins' scratch (DESIGN.md "Static view"). The stage runs whenever its counters are asked for.
+      *key = primary_key(p, k, sg, pair_cap);
+      const bool bypass = p->stats || p->row_cost || ui(p, "primary_cache", 1) == 0;
+      *reuse = ptk::primary_cache_hit(p->pcache, *key, bypass);
+      if (*reuse) return PT_OK;
     }
+    if (pr) TRY(bins_for(p->bins, tri ? sg->ntris : sg->nleaves, k.W, k.y0, k.y1, pair_cap, &k.leaf_bins));
     return PT_OK;
+}
+
+// after the launch of a draw that pt_wf_setup gave a key: the cache's state and counts
+void primary_cache_note(Pass* p, const ptk::PrimaryKey& key, bool reused, bool ok) {
+  if (reused) {
+    if (ok) p->pcache.reuses++;
+    return;  // (a failed launch wrote nothing into hit0)
+  }
+  p->pcache.valid = ok;
+  if (ok) {
+    p->pcache.key = key;
+    p->pcache.runs++;
+  }
 }
 
 // The side stream and events of path-tracing draws issued on `s` (uniform trace_fork = 1), created on first use: one
@@ -854,7 +930,9 @@ int draw_pathtrace_spp(Pass* p, PTParams& k, SceneGPU* sg, int n) {
   const int nb = std::max(n, std::min(kMaxBatch, ui(p, "trace_batch", 1)));
   TRY(wf_alloc(p->wf, k.W, rows, nb, n));
   if (wf_spill(p->wf, k.stack_need) != PT_OK) return err(PT_ERR_HIP, "spill stack allocation failed");
-  TRY(pt_wf_setup(p, k, sg, p->wf.stb[0]));
+  ptk::PrimaryKey key;
+  bool reuse = false;  // sample 0's stage is the draw's: the cache serves it as it serves a one-sample draw
+  TRY(pt_wf_setup(p, k, sg, p->wf.stb[0], &key, &reuse));
   PTParams ks[kMaxBatch];
   for (int s = 0; s < n; ++s) spp_sample_params(k, n, s, p->wf.stb[s], p->wf.spp, &ks[s]);
   ptk::SppResolve rs{};
@@ -874,7 +952,8 @@ int draw_pathtrace_spp(Pass* p, PTParams& k, SceneGPU* sg, int n) {
   int rc;
   const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
   if (rc) return rc;
-  rc = launch_pathtrace_wavefront_spp(ks, rs, g.stream, fk, &ad);
+  rc = launch_pathtrace_wavefront_spp(ks, rs, g.stream, fk, &ad, reuse);
+  primary_cache_note(p, key, reuse, rc == 0);
   if (!rc && k.tiles.cost) p->order.ordered = true;
   return rc ? hip_err((hipError_t)rc, "pathtrace spp launch") : PT_OK;
 }
@@ -901,14 +980,18 @@ int draw_pathtrace(Pass* p) {
     if (k.stack_need >= kStack)
       return err(PT_ERR_ARG, "the megakernel (pt_kernel=1) walks a 32-entry LDS stack; this BVH is deeper: use the "
                              "wavefront path tracer (pt_kernel=0, the default)");
+    p->pcache.valid = false;  // (it sorts the pass's tile order by its own costs)
     rc = launch_pathtrace(k, g.stream);
   } else {                            // 0: wavefront (kernels_wavefront.hip), production
     TRY(wf_alloc(p->wf, k.W, std::max(0, k.y1 - k.y0)));
     if (wf_spill(p->wf, k.stack_need) != PT_OK) return err(PT_ERR_HIP, "spill stack allocation failed");
-    TRY(pt_wf_setup(p, k, sg, p->wf.st));
+    ptk::PrimaryKey key;
+    bool reuse = false;
+    TRY(pt_wf_setup(p, k, sg, p->wf.st, &key, &reuse));
     const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
     if (rc) return rc;
-    rc = launch_pathtrace_wavefront(k, g.stream, fk);
+    rc = launch_pathtrace_wavefront(k, g.stream, fk, reuse);
+    primary_cache_note(p, key, reuse, rc == 0);
     if (!rc && k.tiles.cost) p->order.ordered = true;
   }
   if (rc) return hip_err((hipError_t)rc, "pathtrace launch");
@@ -952,6 +1035,9 @@ int draw_pathtrace_batch(Pass** ps, int n) {
   const int cap = std::max(n, std::min(kMaxBatch, ui(h, "trace_batch", n)));
   TRY(wf_alloc(h->wf, k[0].W, std::max(0, k[0].y1 - k[0].y0), cap));
   if (wf_spill(h->wf, k[0].stack_need) != PT_OK) return err(PT_ERR_HIP, "spill stack allocation failed");
+  // A batch always runs the stage, into the head pass's planes, and sorts every pass's tile order: no pass keeps a key
+  // that claims a plane or an order this draw changed. Each counts as a draw that ran the stage.
+  for (int b = 0; b < n; ++b) ps[b]->pcache.valid = false;
   for (int b = 0; b < n; ++b) TRY(pt_wf_setup(ps[b], k[b], sg, h->wf.stb[b]));
   // the batched shadow launches read frame 0's point-light bins for every frame: frames that do not share them (other
   // lights, another pointLightSize) all walk
@@ -964,8 +1050,10 @@ int draw_pathtrace_batch(Pass** ps, int n) {
   const ptk::WfFork* fk = wf_fork(h, g.stream, &rc);
   if (rc) return rc;
   rc = launch_pathtrace_wavefront_batch(k, n, g.stream, fk);
-  for (int b = 0; b < n && !rc; ++b)
+  for (int b = 0; b < n && !rc; ++b) {
     if (k[b].tiles.cost) ps[b]->order.ordered = true;
+    ps[b]->pcache.runs++;
+  }
   if (rc) return hip_err((hipError_t)rc, "pathtrace batch launch");
   for (int b = 0; b < n; ++b) TRY(note_reads(reads[b]));
   return PT_OK;
@@ -1000,6 +1088,79 @@ static int gbuf_flags(Pass* p, Texture* fwt, GBufParams& k) {
   return PT_OK;
 }
 
+// The key of a draw of the rasterize pass p over the triangles of src (static_key.h), read from the state as it is
+// now: before a draw it is compared with the key taken after the pass's last completed draw. Returns false when an
+// attachment is missing (the draw then reports it).
+bool gbuf_key(Pass* p, const Pass* src, ptk::GbufKey* out) {
+  using namespace ptk;
+  GbufKey q{};
+  if (p->att.size() < 4) return false;
+  int y0, y1;
+  rows_of(p, &y0, &y1);
+  q.w[kGkW] = key_bits(p->W);
+  q.w[kGkH] = key_bits(p->H);
+  q.w[kGkY0] = key_bits(y0);
+  q.w[kGkY1] = key_bits(y1);
+  q.w[kGkBandW] = key_bits(g.band_w);
+  q.w[kGkBandH] = key_bits(g.band_h);
+  q.w[kGkBandY0] = key_bits(g.band_y0);
+  q.w[kGkBandY1] = key_bits(g.band_y1);
+  q.w[kGkBandRow0] = key_bits(g.band_row0);
+  q.w[kGkBandRows] = key_bits(g.band_rows);
+  for (int i = 0; i < 4; ++i) {
+    const Texture* t = tex_of(p->att[i]);
+    if (!t) return false;
+    q.w[kGkAtt0 + 4 * i] = p->att[i];
+    q.w[kGkAtt0 + 4 * i + 1] = key_bits((const void*)t->dev);
+    q.w[kGkAtt0 + 4 * i + 2] = t->version;
+    q.w[kGkAtt0 + 4 * i + 3] = t->raster_stamp;
+  }
+  const Texture *wt = tex_of(p->att[0]), *fwt = tex_of(p->att[3]);
+  q.w[kGkFwAux] = key_bits((const void*)fwt->aux);
+  q.w[kGkFwAuxValid] = fwt->aux_valid;
+  q.w[kGkBoundAux] = key_bits((const void*)wt->aux);
+  q.w[kGkBoundAuxValid] = wt->aux_valid;
+  for (int i = 0; i < 3; ++i) q.w[kGkAuxEye0 + i] = key_bits(wt->aux_eye[i]);
+  if (const Uniform* be = U(p, "bound_eye", 5)) {
+    q.w[kGkBoundEyeSet] = 1;
+    for (int i = 0; i < 3; ++i) q.w[kGkBoundEye0 + i] = key_bits(be->f[i]);
+  }
+  const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // (draw_raster's defaults)
+  const Uniform *uv = U(p, "view", 6), *up = U(p, "projection", 6), *upv = U(p, "pre_viewproj", 6);
+  for (int i = 0; i < 16; ++i) {
+    q.w[kGkView0 + i] = key_bits(uv ? uv->f[i] : I[i]);
+    q.w[kGkProj0 + i] = key_bits(up ? up->f[i] : I[i]);
+    q.w[kGkPreViewProj0 + i] = key_bits(upv ? upv->f[i] : I[i]);
+  }
+  const RasterScene& rs = src->raster;
+  const bool motion = rs.disp && rs.ntris > 0 && ui(p, "object_motion", 1) != 0;
+  q.w[kGkDisp] = key_bits((const void*)(motion ? rs.disp : nullptr));
+  q.w[kGkMode] = key_bits(ui(p, "gbuffer_mode", 1));
+  q.w[kGkPairCap] = key_bits(ui(p, "raster_pair_cap", 0));
+  q.w[kGkTileFlags] = key_bits(ui(p, "atrous_tile_flags", 1));
+  q.w[kGkTfRows0] = key_bits(ui(p, "atrous_rows_begin", -1));
+  q.w[kGkTfRows1] = key_bits(ui(p, "atrous_rows_end", -1));
+  q.w[kGkTflags] = key_bits((const void*)fwt->tflags);
+  q.w[kGkTflagsCap] = fwt->tflags_cap;
+  q.w[kGkTflagsVer] = fwt->tflags_ver;
+  q.w[kGkTflagsY0] = key_bits(fwt->tflags_y0);
+  q.w[kGkTflagsY1] = key_bits(fwt->tflags_y1);
+  q.w[kGkSource] = p->raster_src;
+  q.w[kGkSceneVer] = rs.version;
+  *out = q;
+  return true;
+}
+
+// reuse_static (int uniform of a rasterize pass, default 0): the caller states that nothing outside the library writes
+// this pass's attachments between its draws. PTSVGF_STATIC_REUSE=0 in the environment forces it off (A/B).
+bool reuse_static_on(Pass* p) {
+  static const bool env_off = [] {
+    const char* e = getenv("PTSVGF_STATIC_REUSE");
+    return e && atoi(e) == 0;
+  }();
+  return !env_off && ui(p, "reuse_static", 0) != 0;
+}
+
 int draw_raster(Pass* p) {
   Pass* src = p->raster_src ? pass_of(p->raster_src) : p;
   if (!src) return err(PT_ERR_STATE, "raster pass shares the triangles of a destroyed pass");
@@ -1007,6 +1168,17 @@ int draw_raster(Pass* p) {
     return err(PT_ERR_STATE, "raster pass shares the triangles of a pass that now shares another pass's");
   const RasterScene& rs = src->raster;
   if (!rs.geom && rs.ntris > 0) return err(PT_ERR_STATE, "raster pass not bound");
+  // Static view: the G-buffer is a function of what the key holds. When this draw's key equals the one
+  // taken after the pass's last completed draw, the four attachments, both compact planes and the tile flags already
+  // hold what it would write: nothing is launched and no version moves. A motion bound is cleared and reduced per
+  // draw, so a pass with one always draws. The planes were written by an earlier draw of this pass, perhaps on
+  // another stream: what lets a draw overwrite a set (its earlier readers are done) lets this one leave it as it is.
+  ptk::GbufKey now;
+  if (reuse_static_on(p) && !p->motion_max && gbuf_key(p, src, &now) && ptk::gbuf_cache_hit(p->gcache, now, true)) {
+    p->gcache.reuses++;
+    return PT_OK;
+  }
+  p->gcache.valid = false;
   GBufParams k;
   memset(&k, 0, sizeof(k));
   k.W = p->W;
@@ -1079,6 +1251,11 @@ int draw_raster(Pass* p) {
     wt->aux_valid = true;
     memcpy(wt->aux_eye, k.bound_eye, sizeof(wt->aux_eye));
   }
+  // the draw is complete: its serial on what it wrote, and the key of the state it leaves
+  const uint64_t serial = ++g.raster_serial;
+  for (int i = 0; i < 4; ++i) tex_of(p->att[i])->raster_stamp = serial;
+  p->gcache.valid = gbuf_key(p, src, &p->gcache.key);
+  p->gcache.runs++;
   return PT_OK;
 }
 
@@ -1494,8 +1671,7 @@ int pt_texture2d_upload(uint32_t tex, int w, int h, uint32_t fmt, const float* d
   }
   HIPCHK(hipMemcpyAsync(t->dev, buf.data(), t->bytes, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
-  t->version++;
-  t->aux_valid = false;
+  tex_written(t);
   return PT_OK;
 }
 
@@ -1507,8 +1683,7 @@ int pt_texture_upload_rgba(uint32_t tex, const float* data, size_t bytes) {
   if (!data || bytes != t->bytes) return err(PT_ERR_ARG, "upload size must equal the stored rows");
   HIPCHK(hipMemcpyAsync(t->dev, data, bytes, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
-  t->version++;
-  t->aux_valid = false;
+  tex_written(t);
   return PT_OK;
 }
 
@@ -1580,6 +1755,69 @@ int pt_debug_point_bins_overlap(const float* px, const float* py, int n, float f
   if (bw * bh <= 2) e.n = 0;  // (as pb_bin: a box of at most two cells keeps both)
   for (int cy = cy0; cy <= cy1; ++cy)
     for (int cx = cx0; cx <= cx1; ++cx) kept[(cy - cy0) * bw + (cx - cx0)] = ptk::pb_cell_kept(e, fw, cx, cy, R) ? 1 : 0;
+  return PT_OK;
+}
+
+int pt_debug_stage_counts(uint32_t pass, uint64_t* runs, uint64_t* reuses) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  const int kind = g.programs[p->program];
+  if (kind != PK_PATHTRACE && kind != PK_RASTER)
+    return err(PT_ERR_ARG, "pt_debug_stage_counts: a path-tracing or a rasterize pass");
+  if (runs) *runs = kind == PK_PATHTRACE ? p->pcache.runs : p->gcache.runs;
+  if (reuses) *reuses = kind == PK_PATHTRACE ? p->pcache.reuses : p->gcache.reuses;
+  return PT_OK;
+}
+
+int pt_debug_static_key_words(int kind) {
+  if (kind != 0 && kind != 1) return err(PT_ERR_ARG, "pt_debug_static_key_words: kind 0 (primary) or 1 (G-buffer)");
+  return kind == 0 ? (int)ptk::kPkWords : (int)ptk::kGkWords;
+}
+
+static int static_key_args(const char* who, int kind, const uint64_t* a, const uint64_t* b, int words,
+                           const void* out) {
+  if (kind != 0 && kind != 1) return err(PT_ERR_ARG, std::string(who) + ": kind 0 (primary) or 1 (G-buffer)");
+  if (!a || !b || !out) return err(PT_ERR_ARG, std::string(who) + ": null argument");
+  if (words != (kind == 0 ? (int)ptk::kPkWords : (int)ptk::kGkWords))
+    return err(PT_ERR_ARG, std::string(who) + ": not this kind's word count");
+  return PT_OK;
+}
+
+int pt_debug_static_key_diff(int kind, const uint64_t* a, const uint64_t* b, int words, int* field) {
+  TRY(static_key_args("pt_debug_static_key_diff", kind, a, b, words, field));
+  if (kind == 0) {
+    ptk::PrimaryKey ka, kb;
+    memcpy(ka.w, a, sizeof(ka.w));
+    memcpy(kb.w, b, sizeof(kb.w));
+    *field = ptk::primary_key_diff(ka, kb);
+  } else {
+    ptk::GbufKey ka, kb;
+    memcpy(ka.w, a, sizeof(ka.w));
+    memcpy(kb.w, b, sizeof(kb.w));
+    *field = ptk::gbuf_key_diff(ka, kb);
+  }
+  return PT_OK;
+}
+
+int pt_debug_static_key_hit(int kind, const uint64_t* last, int last_valid, const uint64_t* now, int words, int enabled,
+                            int* hit) {
+  TRY(static_key_args("pt_debug_static_key_hit", kind, last, now, words, hit));
+  if (kind == 0) {
+    ptk::PrimaryCache c;
+    ptk::PrimaryKey k;
+    memcpy(c.key.w, last, sizeof(c.key.w));
+    memcpy(k.w, now, sizeof(k.w));
+    c.valid = last_valid != 0;
+    *hit = ptk::primary_cache_hit(c, k, !enabled) ? 1 : 0;
+  } else {
+    ptk::GbufCache c;
+    ptk::GbufKey k;
+    memcpy(c.key.w, last, sizeof(c.key.w));
+    memcpy(k.w, now, sizeof(k.w));
+    c.valid = last_valid != 0;
+    *hit = ptk::gbuf_cache_hit(c, k, enabled != 0) ? 1 : 0;
+  }
   return PT_OK;
 }
 
@@ -1718,6 +1956,8 @@ int pt_raster_pass_share(uint32_t pass, uint32_t src_pass) {
   if (pass == src_pass || s->raster_src) return err(PT_ERR_ARG, "pt_raster_pass_share: share from an own-bound pass");
   p->raster_src = src_pass;
   p->bound = true;
+  raster_touch(p);
+  p->gcache.valid = false;  // another pass's triangles: the next draw draws
   return PT_OK;
 }
 
@@ -1733,6 +1973,8 @@ int pt_raster_pass_adopt(uint32_t pass, int y_begin, int y_end) {
   k.W = p->W;
   k.H = p->H;
   if (y_begin < 0 || y_end > p->H || y_begin > y_end) return err(PT_ERR_ARG, "pt_raster_pass_adopt: bad rows");
+  raster_touch(p);  // the attachments hold texels no draw of this pass wrote (att_plane below clears their stamps)
+  p->gcache.valid = false;
   k.y0 = y_begin;
   k.y1 = y_end;
   for (int i = 0; i < 4; ++i) {  // the attachments now hold new texels (their versions move on, as after a draw)
@@ -1802,7 +2044,10 @@ int pt_tiles_copy(const uint32_t* tex, int ntex, int tile_y0, int stride, const 
     if (rc) return hip_err((hipError_t)rc, "pt_tiles_copy");
   }
   if (unpack)
-    for (int j = 0; j < ntex; ++j) ts[j]->version++;  // new texels, as after a draw
+    for (int j = 0; j < ntex; ++j) {  // new texels, as after a draw
+      ts[j]->version++;
+      ts[j]->raster_stamp = 0;
+    }
   return PT_OK;
 }
 

@@ -117,6 +117,7 @@ int sync_after(const char* who, int rc, hipStream_t s) {
 // the displacement records of a rasterize pass (pt_raster_pass_set_prev_vertices), freed once no draw reads them
 void drop_disp(Pass* p) {
   if (!p->raster.disp) return;
+  raster_touch(p);
   (void)hipDeviceSynchronize();
   (void)hipFree(p->raster.disp);
   p->raster.disp = nullptr;
@@ -278,6 +279,7 @@ int pose_apply_with(const char* who, Pose& ps, uint32_t tri_out, uint32_t node_o
     return hip_err((hipError_t)rc, who);
   }
   if (p) {
+    raster_touch(p);  // the records, the tree and the displacement records are rewritten below
     if (motion) {
       p->raster.disp = disp;
     } else if (p->raster.disp) {  // left without records, as a refit leaves it; no draw reads them (see the header)
@@ -466,6 +468,7 @@ int pt_raster_pass_bind(uint32_t pass, const float* verts, size_t n_floats) {
   TRY(raster_pass_of(pass, &p));
   if (n_floats % 18) return err(PT_ERR_ARG, "vertex list must be whole triangles of pos3+nrm3");
   int ntris = (int)(n_floats / 18);
+  raster_touch(p);  // new triangles and tree: the next G-buffer draw of this pass and of its sharers draws
   drop_disp(p);  // the triangle order changes
   free_raster_refit(p->raster);  // a host-built tree is not refitted
   p->raster.ntris = ntris;
@@ -517,6 +520,7 @@ int pt_raster_pass_bind_device(uint32_t pass, const void* dverts, size_t n_float
   if (n_floats / 18 > (1u << 24)) return err(PT_ERR_ARG, "more than 2^24 raster triangles");
   const int ntris = (int)(n_floats / 18);
   if (ntris > 0 && !dverts) return err(PT_ERR_ARG, "null device vertex list");
+  raster_touch(p);
   drop_disp(p);  // the triangle order changes
   RasterScene& rs = p->raster;
   rs.ntris = ntris;
@@ -589,6 +593,7 @@ int pt_raster_pass_refit_device(uint32_t pass, const void* dverts, size_t n_floa
   if (n_floats != (size_t)rs.ntris * 18)
     return err(PT_ERR_ARG, "pt_raster_pass_refit_device: not the bound triangle count");
   if (!dverts) return err(PT_ERR_ARG, "null device vertex list");
+  raster_touch(p);
   drop_disp(p);  // their values are stale
   TreesGuard trees;
   int rc = raster_refit_issue(rs, (const float*)dverts, trees.t, g.stream);
@@ -606,6 +611,7 @@ int pt_raster_pass_set_prev_vertices(uint32_t pass, const void* dprev, const voi
   TRY(raster_pass_of(pass, &p));
   if (p->raster_src) return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: the pass shares another pass's triangles");
   if (!p->bound) return err(PT_ERR_ARG, "pt_raster_pass_set_prev_vertices: raster pass not bound");
+  raster_touch(p);  // the records come, go or change
   if (!dprev) {
     drop_disp(p);
     return PT_OK;

@@ -14,6 +14,7 @@
 
 #include "../../include/ptsvgf.h"
 #include "pt_device.h"
+#include "static_key.h"
 
 namespace ptapi {
 
@@ -30,6 +31,9 @@ struct Texture {
   size_t bytes = 0;
   std::vector<uint8_t> host;  // buffers: host copy for decoding
   uint64_t version = 1;
+  // the serial of the draw_raster that wrote this attachment last (Lib::raster_serial); 0 once anything else in the
+  // library wrote the texture (tex_written): part of the G-buffer draw's key (static_key.h)
+  uint64_t raster_stamp = 0;
   // compact one-float side plane of the stored rows: a depth-fwidth attachment's fwidth.y with the background flag, a
   // world-position attachment's primary-ray bound for rays from aux_eye (draw_raster)
   float* aux = nullptr;
@@ -71,6 +75,9 @@ struct RasterScene {
   float* enc_nodes = nullptr;
   ptk::LbvhRefit* refit = nullptr;
   int bvh_records = 0;  // packed records bvh has room for (that bind's; >= 1 while refit is set)
+  // moved on (raster_touch, from Lib::raster_ver: no two states of any pass share a value) by every entry point that
+  // changes geom, nrm, disp, bvh or ntris: part of the G-buffer draw's key (static_key.h)
+  uint64_t version = 0;
 };
 
 // Scratch of the tile-binned G-buffer (launch_gbuffer_raster), per rasterize pass, sized by its triangles and band.
@@ -90,6 +97,7 @@ struct WFBuffers {
   ptk::WFState st{};
   float4* spp = nullptr;  // the sample planes of an spp draw: nsp planes of n texels (SppResolve::samples)
   int nsp = 0;
+  uint64_t gen = 0;      // counts the allocations of base: part of the primary-hit cache's key (static_key.h)
   int* spill = nullptr;  // deep reference trees: stack entries past the LDS stack (WFState::spill)
   int spill_levels = 0;
   size_t spill_cols = 0;
@@ -107,6 +115,8 @@ struct Pass {
   uint32_t program = 0;
   WFBuffers wf;
   TileOrder order;
+  ptk::PrimaryCache pcache;  // path-tracing pass: the primary-hit cache (static_key.h, DESIGN.md "Static view")
+  ptk::GbufCache gcache;     // rasterize pass: its last completed draw's key (reuse_static)
   int W = 0, H = 0;
   std::vector<uint32_t> att;
   bool bound = false, final_pass = false;
@@ -305,10 +315,14 @@ struct Lib {
   uint32_t unit0 = 0;  // GL texture unit 0 binding (global)
   int band_w = 0, band_h = 0, band_y0 = 0, band_y1 = 0, band_row0 = 0, band_rows = 0;
   bool profiling = false;
+  uint64_t raster_serial = 0;  // draw_raster calls that launched (Texture::raster_stamp)
+  uint64_t raster_ver = 0;     // RasterScene::version values handed out
 };
 
 // defined in capi.hip
 extern Lib g;
+// an entry point changes (or may have half changed) the pass's raster triangles, tree or displacement records
+inline void raster_touch(Pass* p) { p->raster.version = ++g.raster_ver; }
 extern std::recursive_mutex g_mu;
 extern ptk::LbvhWork g_lbvh;  // GPU BVH builder scratch (grows, reused across rebuilds)
 
@@ -327,6 +341,13 @@ int hip_err(hipError_t e, const char* what);
 
 Texture* tex_of(uint32_t h);
 Pass* pass_of(uint32_t h);
+// the library wrote (or is about to write) new texels into t: its version moves on, its compact plane and its
+// G-buffer stamp no longer describe it
+inline void tex_written(Texture* t) {
+  t->version++;
+  t->aux_valid = false;
+  t->raster_stamp = 0;
+}
 int ensure_init();
 int refresh_host(Texture* t);
 

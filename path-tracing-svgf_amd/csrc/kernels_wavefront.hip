@@ -2165,7 +2165,7 @@ static int list_blocks(int n_items_max, int grid = 0) {
 }
 template <int KS, bool DEEP>
 int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk, const SppResolve* rs = nullptr,
-                     const SppAdaptive* ad = nullptr) {
+                     const SppAdaptive* ad = nullptr, bool reuse_primary = false) {
   const PTParams& p = ps[0];
   const int rows = p.y1 - p.y0;
   if (rows <= 0) return 0;
@@ -2175,8 +2175,17 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
   if (e != hipSuccess) return (int)e;
   const int ntiles = wf_subset_tiles(p.W, rows, p.tile_stride, p.tile_offset);
   if (ntiles <= 0) return 0;
-  for (int b = 0; b < (rs ? 1 : nb); ++b) {  // (the primary ray does not depend on the sample: :1060-1062)
-    const PTParams& f = ps[b];
+  // The primary hit lives in wf.hit0, not wf.hit: the stage's launches and the bounce-0 shades below get a copy of the
+  // frame's parameters whose `hit` is that plane (kernel bodies unchanged), and the bounce-1 trace overwrites wf.hit
+  // alone. Nothing the stage computes depends on frameCounter (the jitter of :1060-1062 is never applied), so with
+  // reuse_primary (the caller compared the key of everything the stage reads, static_key.h) the stage is skipped: hit0
+  // and the tile order of the last stage that ran (tile_sort_kernel cleared `cost` then, and nothing outside the stage
+  // adds to it) are what this stage would write. hit0 is written and read only by draws of its own pass, like every
+  // other array of the pass's wavefront state: whatever orders two draws of a pass over ray_o or the lists (one
+  // stream, or the caller's events before a slot is reused) orders the stage's writes before every later draw's reads.
+  for (int b = 0; b < (rs ? 1 : nb) && !reuse_primary; ++b) {  // (the primary ray does not depend on the sample)
+    PTParams f = ps[b];
+    f.wf.hit = f.wf.hit0;
     if (f.primary_raster) {  // triangles (2) or leaves binned to every tile of the band; the subset's tiles rasterised
       const bool tris = f.primary_raster == 2;
       const int nitems = f.leaf_bins.n;
@@ -2258,19 +2267,17 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
     }
     for (int b = 0; b < nb; ++b) {
       PTParams shared;
-      if (rs && i == 0 && b > 0) {
-        // Sample b's bounce-0 shade reads sample 0's primary hit (and, the samples being copies of one pass, its
-        // tiles.perm_next). ps[0].wf.hit is next written by closest(1), sample 0's own bounce-1 trace, which is issued
-        // on `s` after this loop has issued all nb bounce-0 shades on `s`: stream order puts every read before that
-        // write. The side stream of a trace_fork runs only the bounce-0 shadow walks and finish, which do not touch
-        // `hit`. The first-hit planes are sample 0's alone: the folded shade skips the stores of null planes; the
-        // unfolded one (shade_fold = 0, A/B) has no such branch and stores into the sample's own colour plane, every
-        // texel of which its wf_finalize writes afterwards on `s`.
+      if (i == 0) {
+        // The bounce-0 shade reads the primary hit plane (above); sample b of an spp draw reads sample 0's (and, the
+        // samples being copies of one pass, its tiles.perm_next). No launch of this draw after the stage writes hit0:
+        // the bounce-1 trace writes wf.hit. The first-hit planes are sample 0's alone: the folded shade skips the
+        // stores of null planes; the unfolded one (shade_fold = 0, A/B) has no such branch and stores into the
+        // sample's own colour plane, every texel of which its wf_finalize writes afterwards on `s`.
         shared = ps[b];
-        shared.wf.hit = ps[0].wf.hit;
-        shared.emission = shared.albedo = fold ? Plane{} : ps[b].color;
+        shared.wf.hit = ps[rs ? 0 : b].wf.hit0;
+        if (rs && b > 0) shared.emission = shared.albedo = fold ? Plane{} : ps[b].color;
       }
-      const PTParams& f = rs && i == 0 && b > 0 ? shared : ps[b];
+      const PTParams& f = i == 0 ? shared : ps[b];
       const int* live_in = f.wf.counters + kWfCtr * (i > 0 ? i - 1 : 0);
 #define PT_SHADE_LAUNCH(FOLD, FIRST, LAST)                                                                          \
   hipLaunchKernelGGL((wf_shade<FOLD, FIRST, LAST>), dim3(i == 0 ? gS0 : gL), dim3(256), 0, s, f, i,                  \
@@ -2374,11 +2381,12 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
   return (int)hipGetLastError();
 }
 
-int launch_pathtrace_wavefront(const PTParams& p, hipStream_t s, const WfFork* fk) {
+int launch_pathtrace_wavefront(const PTParams& p, hipStream_t s, const WfFork* fk, bool reuse_primary) {
   // the LDS stack bounds resident waves: a tree that fits the small stack gets more of them
-  if (p.wf.spill) return launch_wavefront<kSpillKS, true>(&p, 1, s, fk);  // deep tree
-  return p.stack_need <= kStackSmall ? launch_wavefront<kStackSmall, false>(&p, 1, s, fk)
-                                     : launch_wavefront<kStack, false>(&p, 1, s, fk);
+  const bool re = reuse_primary;
+  if (p.wf.spill) return launch_wavefront<kSpillKS, true>(&p, 1, s, fk, nullptr, nullptr, re);  // deep tree
+  return p.stack_need <= kStackSmall ? launch_wavefront<kStackSmall, false>(&p, 1, s, fk, nullptr, nullptr, re)
+                                     : launch_wavefront<kStack, false>(&p, 1, s, fk, nullptr, nullptr, re);
 }
 
 int launch_pathtrace_wavefront_batch(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk) {
@@ -2389,12 +2397,13 @@ int launch_pathtrace_wavefront_batch(const PTParams* ps, int nb, hipStream_t s, 
 }
 
 int launch_pathtrace_wavefront_spp(const PTParams* ps, const SppResolve& rs, hipStream_t s, const WfFork* fk,
-                                   const SppAdaptive* ad) {
+                                   const SppAdaptive* ad, bool reuse_primary) {
   if (rs.n < 2 || rs.n > kMaxBatch) return (int)hipErrorInvalidValue;
   if (ad && !ad->counts && !ad->stats) ad = nullptr;
-  if (ps[0].wf.spill) return launch_wavefront<kSpillKS, true>(ps, rs.n, s, fk, &rs, ad);
-  return ps[0].stack_need <= kStackSmall ? launch_wavefront<kStackSmall, false>(ps, rs.n, s, fk, &rs, ad)
-                                         : launch_wavefront<kStack, false>(ps, rs.n, s, fk, &rs, ad);
+  const bool re = reuse_primary;
+  if (ps[0].wf.spill) return launch_wavefront<kSpillKS, true>(ps, rs.n, s, fk, &rs, ad, re);
+  return ps[0].stack_need <= kStackSmall ? launch_wavefront<kStackSmall, false>(ps, rs.n, s, fk, &rs, ad, re)
+                                         : launch_wavefront<kStack, false>(ps, rs.n, s, fk, &rs, ad, re);
 }
 
 }  // namespace ptk

@@ -134,6 +134,11 @@ struct WFState {
   int stats_n;                  // counters the caller's buffer holds: counter k is written only when k < stats_n
   int* spill;                   // deep trees only: stack entries past the LDS stack, entry kStack + j of pixel pid at
   size_t spill_stride;          // spill[j * spill_stride + pid] (spill_stride = band pixels); null otherwise
+  // The primary hit (triangle, t bits), a plane of its own: the primary stage writes it and every bounce-0 shade
+  // reads it, `hit` being overwritten by the bounce-1 trace. It survives the draw, so a later draw of the same pass
+  // from the same view skips the stage (DESIGN.md "Static view"). Host side only: launch_wavefront passes it to the
+  // primary and bounce-0 launches as their `hit`; no kernel names this field.
+  int2* hit0;
 };
 // Traversal counters of one path-tracing draw (pt_pass_set_trace_stats): rays traced and node + triangle visits
 // per traversal kind, tie re-walks on the reference tree, primary rays retried unbounded after the G-buffer bound, rays
@@ -429,7 +434,10 @@ struct WfFork {
   hipStream_t side;
   hipEvent_t fork, join;
 };
-int launch_pathtrace_wavefront(const PTParams& p, hipStream_t s, const WfFork* fk = nullptr);
+// reuse_primary: p.wf.hit0 (and the tile order in p.tiles.perm_next) still hold what the primary stage would write for
+// this draw (the caller's key compare, static_key.h): the stage is not launched
+int launch_pathtrace_wavefront(const PTParams& p, hipStream_t s, const WfFork* fk = nullptr,
+                               bool reuse_primary = false);
 // 1 when the walk kernels' translation unit keeps f32 subnormals (max(0, least subnormal) > 0, evaluated on the device
 // with the walk code's compile flags), as PT_WIDE_SIGNED's one-compare child test needs; 0 if it flushes; < 0 a HIP error
 int subnormal_probe(hipStream_t s);
@@ -447,7 +455,7 @@ int launch_pathtrace_wavefront_batch(const PTParams* ps, int nb, hipStream_t s, 
 // sample 0 alone, every sample's bounce-0 shade reads its hit, and wf_spp_resolve writes rs.color after the last finish
 // ad (optional): the draw's count and statistics planes; without it, or with both null, the launches are the plain ones
 int launch_pathtrace_wavefront_spp(const PTParams* ps, const SppResolve& rs, hipStream_t s, const WfFork* fk = nullptr,
-                                   const SppAdaptive* ad = nullptr);
+                                   const SppAdaptive* ad = nullptr, bool reuse_primary = false);
 int launch_reproject(const ReprojParams& p, hipStream_t s);
 int launch_variance(const VarianceParams& p, hipStream_t s);
 int launch_atrous_exact(const AtrousParams& p, hipStream_t s);

@@ -152,6 +152,13 @@ _PT_SIGS = [
     # include/ptsvgf_debug_pointbins.h
     ("pt_debug_point_bins_overlap", C.c_int, [_fp, _fp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int)]),
+    # include/ptsvgf_debug_static.h
+    ("pt_debug_stage_counts", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("pt_debug_static_key_words", C.c_int, [C.c_int]),
+    ("pt_debug_static_key_diff", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int,
+                                           C.POINTER(C.c_int)]),
+    ("pt_debug_static_key_hit", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64), C.c_int,
+                                          C.c_int, C.POINTER(C.c_int)]),
 ]
 
 _PTS_SIGS = [

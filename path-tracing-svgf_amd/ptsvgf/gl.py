@@ -261,6 +261,36 @@ def point_bins_overlap(px, py, fw: float, R: int, box) -> tuple:
     return kept.astype(bool), bool(deg.value)
 
 
+def static_key_words(kind: int) -> int:
+    """pt_debug_static_key_words: 64-bit words of a static-view key (kind 0: the primary stage's, 1: the G-buffer
+    draw's; csrc/static_key.h)."""
+    return check(pt().pt_debug_static_key_words(int(kind)))
+
+
+def _key_ptr(a):
+    a = np.ascontiguousarray(a, np.uint64)
+    return a, a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def static_key_diff(kind: int, a, b) -> int:
+    """pt_debug_static_key_diff: the first word in which two keys differ, -1 when they are equal. Runs on the host."""
+    a, pa = _key_ptr(a)
+    b, pb = _key_ptr(b)
+    field = C.c_int()
+    check(pt().pt_debug_static_key_diff(int(kind), pa, pb, int(min(a.size, b.size)), C.byref(field)))
+    return field.value
+
+
+def static_key_hit(kind: int, last, last_valid: bool, now, enabled: bool) -> bool:
+    """pt_debug_static_key_hit: may a draw with key `now` reuse the work of the draw that left `last`?"""
+    last, pl = _key_ptr(last)
+    now, pn = _key_ptr(now)
+    hit = C.c_int()
+    check(pt().pt_debug_static_key_hit(int(kind), pl, 1 if last_valid else 0, pn, int(min(last.size, now.size)),
+                                       1 if enabled else 0, C.byref(hit)))
+    return bool(hit.value)
+
+
 class PtTileSeg(C.Structure):
     _fields_ = [("y_begin", C.c_int), ("y_end", C.c_int), ("offset", C.c_int), ("packed", C.c_void_p)]
 
@@ -450,6 +480,14 @@ class RenderPass:
     def set_motion_bound(self, device_ptr: int) -> None:
         """G-buffer pass: store the largest |motion.y| of every draw into a device uint32 (float bits; 0 disables)."""
         check(pt().pt_pass_set_motion_bound(self._handle(), C.c_void_p(device_ptr or None)))
+
+    def stage_counts(self):
+        """pt_debug_stage_counts (DESIGN.md "Static view"): (runs, reuses) of this pass's draws. A path-tracing pass:
+        the draws that ran the primary stage / that read the cached primary hit; a rasterize pass: the G-buffer draws
+        that launched / that were elided (int uniform reuse_static)."""
+        runs, reuses = C.c_uint64(), C.c_uint64()
+        check(pt().pt_debug_stage_counts(self._handle(), C.byref(runs), C.byref(reuses)))
+        return runs.value, reuses.value
 
     def destroy(self) -> None:
         if self._h is not None:

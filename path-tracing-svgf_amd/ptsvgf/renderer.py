@@ -325,6 +325,12 @@ class Renderer:
             p.set_uniform_int("screen_height", H)
             if gbuffer_rows is not None:
                 p.set_rows(*gbuffer_rows)
+            # reuse_static (DESIGN.md "Static view"): this renderer alone writes its G-buffer sets: it draws them
+            # itself into planes the library allocated, and no hook (after_gbuffer, pt_source, halo) hands them to
+            # code that could write them. A static view then draws each set once and leaves it.
+            own_planes = (self._draw_gbuffer and after_gbuffer is None and pt_source is None and halo is None
+                          and tex_factory is None)
+            p.set_uniform_int("reuse_static", 1 if own_planes else 0)
             self.init_pass.append(p)
             self.gbuf.append(g)
 
