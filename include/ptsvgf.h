@@ -320,6 +320,33 @@ int pt_pass_set_sample_counts(uint32_t pass, void* device_u8);
  * Ignored at spp = 1. NULL unbinds. PT_ERR_STATE under an active pt_set_band
  * partition, as above. No reference counterpart. */
 int pt_pass_set_sample_stats(uint32_t pass, void* device_f32x2);
+/* Per-pixel sample moments for SVGF (path-tracing pass, wavefront kernel,
+ * spp = N > 1): while set, the resolve of a draw stores for every pixel it
+ * resolves device_f32x4[y * width + x] = (mu, nu, r, float(n)), n the
+ * pixel's sample count. With e, a the draw's own emission and albedo texels,
+ * illum_s = (c_s.rgb - e.rgb) / max(a.rgb, 0.001) per channel (0 if a channel
+ * is NaN) and l_s its luminance (0.2125, 0.7154, 0.0721): mu = (l_0 + l_1 +
+ * ...) / float(n), nu = (l_0 l_0 + l_1 l_1 + ...) / float(n), in sample
+ * order; r = 1 / float(n), times 1 / float(frameCounter + 1) when the draw
+ * accumulates. float32, one rounding per operation. Pixels outside the drawn
+ * rows or tile subset keep their contents. Ignored at spp = 1. NULL unbinds.
+ * PT_ERR_STATE under an active pt_set_band partition, as above.
+ *
+ * The plane is meant to be an RGBA32F texture of the frame's size (its
+ * pointer from pt_texture_device_ptr), bound by pt_pass_set_texture as the
+ * optional sampler "gSampleMoments" of the svgf_reproject.frag and
+ * svgf_variance.frag passes that denoise this draw's colour (PT_ERR_ARG for
+ * a texture of another size). With sm its texel, on surface pixels:
+ *   reproject  m0 = (1 - alpha) prev.x + alpha sm.x, m1 likewise with .y,
+ *              variance = max(0, m1 - m0 m0) * sm.z; the rest as without it;
+ *   variance   the spatial estimate runs iff h * sm.w < 4 (h: the history
+ *              length; the shader's rule is h < 4), its sums as without it,
+ *              variance = (m1 - m0 m0) * (4 / (h * sm.w)) * sm.z.
+ * With sm = (lum, lum^2, 1, 1) both passes write the bits they write without
+ * the sampler. A history written without the sampler holds per-frame moments,
+ * one written with it per-sample moments: mixing the two modes over one
+ * history's life is the caller's affair. No reference counterpart. */
+int pt_pass_set_sample_moments(uint32_t pass, void* device_f32x4);
 /* The next draw's sample counts from a draw's statistics, on the library's
  * current stream: for every pixel of the frame out_u8 = 1 where nd_tex.w == 1
  * (background); else the statistics are looked up at the texel holding

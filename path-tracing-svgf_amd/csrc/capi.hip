@@ -948,7 +948,9 @@ int draw_pathtrace_spp(Pass* p, PTParams& k, SceneGPU* sg, int n) {
   rs.y1 = k.y1;
   rs.tile_stride = k.tile_stride;
   rs.tile_offset = k.tile_offset;
-  const ptk::SppAdaptive ad{p->sample_counts, p->sample_stats};
+  if (p->sample_moments && (!k.emission.p || !k.albedo.p))
+    return err(PT_ERR_ARG, "sample moments need the pass's emission and albedo attachments");
+  const ptk::SppAdaptive ad{p->sample_counts, p->sample_stats, p->sample_moments, k.emission, k.albedo};
   int rc;
   const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
   if (rc) return rc;
@@ -963,9 +965,9 @@ int draw_pathtrace(Pass* p) {
   TRY(pass_spp(p, &spp));
   if (spp > 1 && ui(p, "pt_kernel", 0) != 0)
     return err(PT_ERR_ARG, "spp > 1 needs the wavefront path tracer (pt_kernel = 0)");
-  // the count and statistics planes hold whole frames in global rows; a band partition's planes do not
-  if (spp > 1 && (p->sample_counts || p->sample_stats) && band_partition(p->W, p->H))
-    return err(PT_ERR_STATE, "sample counts / statistics cannot be bound under a pt_set_band partition");
+  // the count, statistics and moments planes hold whole frames in global rows; a band partition's planes do not
+  if (spp > 1 && (p->sample_counts || p->sample_stats || p->sample_moments) && band_partition(p->W, p->H))
+    return err(PT_ERR_STATE, "sample counts / statistics / moments cannot be bound under a pt_set_band partition");
   PTParams k;
   SceneGPU* sg = nullptr;
   DrawReads reads;
@@ -1283,6 +1285,8 @@ int draw_svgf(Pass* p, int kind) {
     k.depth_thr = uf(p, "depth_threshold", 0.0f);
     k.normal_thr = uf(p, "normal_threshold", 0.0f);
     k.block = ui(p, "reproj_block", 1);  // A/B (0: lin per tap): the same texels either way
+    // optional: the moments plane of the draw that wrote gColor (pt_pass_set_sample_moments)
+    if (Texture* sm = bound_sampler(p, "gSampleMoments")) TRY(plane_of(sm, p, &k.sm, "gSampleMoments"));
     rc = launch_reproject(k, g.stream);
   } else if (kind == PK_VARIANCE) {
     VarianceParams k;
@@ -1295,6 +1299,7 @@ int draw_svgf(Pass* p, int kind) {
     TRY(att_plane(p, 0, &k.out));
     k.phi_color = uf(p, "gPhiColor", 0.0f);
     k.phi_normal = uf(p, "gPhiNormal", 0.0f);
+    if (Texture* sm = bound_sampler(p, "gSampleMoments")) TRY(plane_of(sm, p, &k.sm, "gSampleMoments"));
     rc = launch_variance(k, g.stream);
   } else if (kind == PK_ATROUS) {
     AtrousParams k;
@@ -2151,6 +2156,16 @@ int pt_pass_set_sample_stats(uint32_t pass, void* device_f32x2) {
   if (device_f32x2 && g.programs[p->program] != PK_PATHTRACE)
     return err(PT_ERR_ARG, "sample statistics need a path-tracing pass");
   p->sample_stats = (float2*)device_f32x2;
+  return PT_OK;
+}
+
+int pt_pass_set_sample_moments(uint32_t pass, void* device_f32x4) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (device_f32x4 && g.programs[p->program] != PK_PATHTRACE)
+    return err(PT_ERR_ARG, "sample moments need a path-tracing pass");
+  p->sample_moments = (float4*)device_f32x4;
   return PT_OK;
 }
 

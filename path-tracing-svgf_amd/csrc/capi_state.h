@@ -132,6 +132,7 @@ struct Pass {
   uint32_t* row_cost = nullptr;  // pt_pass_set_row_cost (not owned)
   uint8_t* sample_counts = nullptr;  // pt_pass_set_sample_counts (not owned)
   float2* sample_stats = nullptr;    // pt_pass_set_sample_stats (not owned)
+  float4* sample_moments = nullptr;  // pt_pass_set_sample_moments (not owned)
   uint32_t* motion_max = nullptr;  // pt_pass_set_motion_bound (not owned)
   unsigned long long* stats = nullptr;  // pt_pass_set_trace_stats (not owned)
   int stats_n = 0;                      // counters that buffer holds (pt_pass_set_trace_stats_n)

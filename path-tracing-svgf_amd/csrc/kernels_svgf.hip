@@ -13,6 +13,18 @@
 // glsl_builtins.h, so these kernels reproduce the CPU oracle bit for bit. The
 // production a-trous (atrous_fast_kernel, kernels_atrous.hip) trades the
 // built-in pow/exp for the hardware exp2/log2 and is checked within tolerance.
+//
+// SVGF from sample moments (sampler gSampleMoments on the reproject and variance passes, the plane a
+// multi-sample draw's resolve writes: (mu, nu, r, n) per pixel = mean luminance and mean squared luminance of the
+// pixel's n demodulated samples, r the factor from a per-sample variance to the variance of the colour the draw
+// wrote). With the plane bound, on surface pixels only:
+//   reproject  m0 = (1 - alpha) pM[0] + alpha sm.x, m1 = (1 - alpha) pM[1] + alpha sm.y,
+//              var = max(0, m1 - m0 m0) * sm.z; everything else (validity, taps, alpha, hist, illum) as without it
+//   variance   the spatial estimate runs iff h * sm.w < 4 (h: the history length), its sums unchanged;
+//              var = m1 - m0 m0, var *= 4 / (h * sm.w), var *= sm.z; the plane is read at the centre only
+// With sm = (lum, lum^2, 1, 1) every output is bit for bit what the passes write without the plane. A history written
+// without the plane holds per-frame moments, one written with it per-sample moments: mixing the two over one
+// history's life is the caller's affair (ptsvgf.Renderer fixes the mode at construction).
 #include <hip/hip_runtime.h>
 
 #include "glsl_builtins.h"
@@ -98,6 +110,8 @@ __device__ __forceinline__ float4 lin_tap(const float4 (&B)[3][3], const Bilin& 
   return lin_blk<(K & 1), (K >> 1)>(B, b);
 }
 
+// SM: the sample-moments plane p.sm is bound (header); false is the shader as it is
+template <bool SM>
 __global__ void __launch_bounds__(256) PT_REPROJ_ATTR reproject_kernel(ReprojParams p) {
   int x = blockIdx.x * 16 + (threadIdx.x & 15);
   int y = p.y0 + blockIdx.y * 16 + (threadIdx.x >> 4);
@@ -241,11 +255,20 @@ __global__ void __launch_bounds__(256) PT_REPROJ_ATTR reproject_kernel(ReprojPar
   }
   hist = f_min(32.0f, valid ? hist + 1.0f : 1.0f);
   float alpha = valid ? f_max(0.2f, 1.0f / hist) : 1.0f;
-  float m0 = lum(illum.x, illum.y, illum.z);
-  float m1 = m0 * m0;
+  float m0, m1, rs = 1.0f;
+  if (SM) {  // the draw's own sample moments (read here, after the taps: nothing above holds it in registers)
+    const float4 sm = ldp(p.sm, x, y);
+    m0 = sm.x;
+    m1 = sm.y;
+    rs = sm.z;
+  } else {
+    m0 = lum(illum.x, illum.y, illum.z);
+    m1 = m0 * m0;
+  }
   m0 = (1.0f - alpha) * pM[0] + alpha * m0;
   m1 = (1.0f - alpha) * pM[1] + alpha * m1;
   float var = f_max(0.0f, m1 - m0 * m0);
+  if (SM) var = var * rs;
   float4 oi, om;
   oi.x = (1.0f - alpha) * pI[0] + alpha * illum.x;
   oi.y = (1.0f - alpha) * pI[1] + alpha * illum.y;
@@ -261,18 +284,27 @@ __global__ void __launch_bounds__(256) PT_REPROJ_ATTR reproject_kernel(ReprojPar
 // written); the 7x7 spatial estimate (svgf_variance.frag:58-110, young histories) reads its taps from the block's
 // illumination, moments and normal/depth staged once in LDS with a 3-texel apron — only in blocks where some pixel
 // needs it. Same taps in the same order as the per-pixel form.
+// SM (the sample-moments plane p.sm is bound, header): the pixel's own texel alone is read, so the staged arrays are
+// the same three.
 constexpr int kVT = 16 + 2 * 3;
+template <bool SM>
 __global__ void __launch_bounds__(256) variance_kernel(VarianceParams p) {
   __shared__ float4 s_il[kVT * kVT], s_mo[kVT * kVT], s_nd[kVT * kVT];
   const int bx = blockIdx.x * 16, by = p.y0 + blockIdx.y * 16;
   const int x = bx + (threadIdx.x & 15), y = by + (threadIdx.x >> 4);
   const bool valid = x < p.W && y < p.y1;
-  float h = 4.0f;
+  float h = 4.0f;  // the values the temporal estimate rests on: frames of history (SM: times the pixel's samples)
+  float rs = 1.0f;
   float4 ic = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nd = ic;
   bool need = false;
   if (valid) {
     h = ldp(p.moments, x, y).z;
     ic = ldp(p.illum, x, y);
+    if (SM) {
+      const float4 sm = ldp(p.sm, x, y);
+      h = h * sm.w;
+      rs = sm.z;
+    }
     if (h < 4.0f) {
       nd = ldp(p.nd, x, y);
       need = nd.w != 1.0f;
@@ -322,6 +354,7 @@ __global__ void __launch_bounds__(256) variance_kernel(VarianceParams p) {
   s0 /= sumW; s1 /= sumW; s2 /= sumW; m0 /= sumW; m1 /= sumW;
   float var = m1 - m0 * m0;
   var *= 4.0f / h;
+  if (SM) var *= rs;
   float4 o;
   o.x = s0; o.y = s1; o.z = s2; o.w = var;
   stp(p.out, x, y, o);
@@ -411,12 +444,14 @@ static dim3 grid16(int W, int rows) { return dim3((W + 15) / 16, (rows + 15) / 1
 
 int launch_reproject(const ReprojParams& p, hipStream_t s) {
   if (p.y1 <= p.y0) return 0;
-  hipLaunchKernelGGL(reproject_kernel, grid16(p.W, p.y1 - p.y0), dim3(256), 0, s, p);
+  if (p.sm.p) hipLaunchKernelGGL(reproject_kernel<true>, grid16(p.W, p.y1 - p.y0), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(reproject_kernel<false>, grid16(p.W, p.y1 - p.y0), dim3(256), 0, s, p);
   return (int)hipGetLastError();
 }
 int launch_variance(const VarianceParams& p, hipStream_t s) {
   if (p.y1 <= p.y0) return 0;
-  hipLaunchKernelGGL(variance_kernel, grid16(p.W, p.y1 - p.y0), dim3(256), 0, s, p);
+  if (p.sm.p) hipLaunchKernelGGL(variance_kernel<true>, grid16(p.W, p.y1 - p.y0), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(variance_kernel<false>, grid16(p.W, p.y1 - p.y0), dim3(256), 0, s, p);
   return (int)hipGetLastError();
 }
 int launch_atrous_exact(const AtrousParams& p, hipStream_t s) {

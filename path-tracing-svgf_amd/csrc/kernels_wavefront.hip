@@ -1927,7 +1927,17 @@ __device__ __forceinline__ float spp_lum(v3 c) { return (0.2125f * c.x + 0.7154f
 // (the loops are unrolled over kMaxBatch and predicated on s < n) and one 8-byte store writes (m, v): the mean in
 // sample order over float(n) and sum (l_s - m)^2 in sample order over float(n - 1); (l_0, -1) at n < 2. Block and
 // thread indices as wf_spp_resolve; no LDS, no atomics; 16 (n + 1) + 1 + 8 bytes per pixel, each touched once.
-template <bool COUNTS, bool STATS>
+// MOMENTS (DESIGN.md "SVGF from sample moments"; tests/sample_moments_ref.cpp): the draw's own emission and albedo
+// texels (two more 16-byte loads) demodulate every sample as svgf_reproject.frag demodulates the mean, illum_s =
+// (c_s - e) / max(a, 0.001) per channel, 0 when a channel is NaN; with l_s = lum(illum_s) in registers, one 16-byte
+// store writes (mu, nu, r, float(n)): mu = (l_0 + l_1 + ...) / float(n) and nu = (l_0 l_0 + l_1 l_1 + ...) / float(n)
+// in sample order, r = 1 / float(n), times the accumulation's mix weight when the draw accumulates.
+__device__ __forceinline__ float spp_demod_lum(v3 c, v3 e, v3 den) {
+  v3 il = mk((c.x - e.x) / den.x, (c.y - e.y) / den.y, (c.z - e.z) / den.z);
+  if (f_isnan(il.x) || f_isnan(il.y) || f_isnan(il.z)) il = splat(0.0f);
+  return spp_lum(il);
+}
+template <bool COUNTS, bool STATS, bool MOMENTS>
 __global__ void __launch_bounds__(256) wf_spp_resolve_adaptive(SppResolve r, SppAdaptive a) {
   const int ntx = (r.W + 15) / 16;
   const int tile = (int)blockIdx.x * r.tile_stride + r.tile_offset;
@@ -1941,6 +1951,15 @@ __global__ void __launch_bounds__(256) wf_spp_resolve_adaptive(SppResolve r, Spp
   float l[kMaxBatch];
   v3 sum = xyz(ldnt(&r.samples[pid]));
   l[0] = spp_lum(sum);
+  v3 e = splat(0.0f), den = splat(1.0f);
+  float mu = 0.0f, nu = 0.0f;  // MOMENTS: the running sums of l_s and l_s l_s of the demodulated samples
+  if (MOMENTS) {
+    e = xyz(pld(a.emission, x, y));
+    const v3 al = xyz(pld(a.albedo, x, y));
+    den = mk(f_max(al.x, 0.001f), f_max(al.y, 0.001f), f_max(al.z, 0.001f));
+    mu = spp_demod_lum(sum, e, den);
+    nu = mu * mu;
+  }
 #pragma unroll
   for (int s = 1; s < kMaxBatch; ++s) {
     l[s] = 0.0f;
@@ -1948,14 +1967,22 @@ __global__ void __launch_bounds__(256) wf_spp_resolve_adaptive(SppResolve r, Spp
       const v3 c = xyz(ldnt(&r.samples[(size_t)s * r.stride + pid]));
       sum = add(sum, c);
       if (STATS) l[s] = spp_lum(c);
+      if (MOMENTS) {
+        const float d = spp_demod_lum(c, e, den);
+        mu = mu + d;
+        nu = nu + d * d;
+      }
     }
   }
   v3 color = divs(sum, (float)n);
+  float rr = 1.0f / (float)n;  // MOMENTS: a per-sample variance to the variance of the colour written below
   if (r.accumulate && r.last.p) {  // :1116-1119
     float4 lc = pld(r.last, x, y);
     color = mixv(xyz(lc), color, 1.0f / (float)(r.frameCounter + 1u));
+    rr = rr * (1.0f / (float)(r.frameCounter + 1u));
   }
   pst(r.color, x, y, f4(color.x, color.y, color.z, 1.0f));
+  if (MOMENTS) a.moments[gp] = f4(mu / (float)n, nu / (float)n, rr, (float)n);
   if (STATS) {
     float m = l[0], v = -1.0f;
     if (n >= 2) {
@@ -2371,12 +2398,21 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
     for (int b = 0; b < nb; ++b) hipLaunchKernelGGL(wf_finalize, dim3(gN), dim3(256), 0, s, ps[b]);
   // every sample's colour is written by now on `s` (the last bounce's finish or wf_finalize; a trace_fork joined
   // before the bounce-1 shade)
-  if (rs && ad && ad->counts && ad->stats)
-    hipLaunchKernelGGL((wf_spp_resolve_adaptive<true, true>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+  if (rs && ad && ad->moments) {
+    if (ad->counts && ad->stats)
+      hipLaunchKernelGGL((wf_spp_resolve_adaptive<true, true, true>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+    else if (ad->counts)
+      hipLaunchKernelGGL((wf_spp_resolve_adaptive<true, false, true>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+    else if (ad->stats)
+      hipLaunchKernelGGL((wf_spp_resolve_adaptive<false, true, true>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+    else
+      hipLaunchKernelGGL((wf_spp_resolve_adaptive<false, false, true>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+  } else if (rs && ad && ad->counts && ad->stats)
+    hipLaunchKernelGGL((wf_spp_resolve_adaptive<true, true, false>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
   else if (rs && ad && ad->counts)
-    hipLaunchKernelGGL((wf_spp_resolve_adaptive<true, false>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+    hipLaunchKernelGGL((wf_spp_resolve_adaptive<true, false, false>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
   else if (rs && ad && ad->stats)
-    hipLaunchKernelGGL((wf_spp_resolve_adaptive<false, true>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
+    hipLaunchKernelGGL((wf_spp_resolve_adaptive<false, true, false>), dim3(ntiles), dim3(256), 0, s, *rs, *ad);
   else if (rs) hipLaunchKernelGGL(wf_spp_resolve, dim3(ntiles), dim3(256), 0, s, *rs);
   return (int)hipGetLastError();
 }
@@ -2399,7 +2435,7 @@ int launch_pathtrace_wavefront_batch(const PTParams* ps, int nb, hipStream_t s, 
 int launch_pathtrace_wavefront_spp(const PTParams* ps, const SppResolve& rs, hipStream_t s, const WfFork* fk,
                                    const SppAdaptive* ad, bool reuse_primary) {
   if (rs.n < 2 || rs.n > kMaxBatch) return (int)hipErrorInvalidValue;
-  if (ad && !ad->counts && !ad->stats) ad = nullptr;
+  if (ad && !ad->counts && !ad->stats && !ad->moments) ad = nullptr;
   const bool re = reuse_primary;
   if (ps[0].wf.spill) return launch_wavefront<kSpillKS, true>(ps, rs.n, s, fk, &rs, ad, re);
   return ps[0].stack_need <= kStackSmall ? launch_wavefront<kStackSmall, false>(ps, rs.n, s, fk, &rs, ad, re)

@@ -182,9 +182,14 @@ struct SppResolve {
 // Per-pixel sample counts and statistics of an spp draw (DESIGN.md "Adaptive sample counts"), both addressed by frame
 // pixel in global rows (y * W + x) and either one optional. counts: pixel's samples n = min(max(c, 1), N); sample s
 // exists iff s < n. stats: the resolve writes (mean, unbiased variance) of the samples' luminances, (l_0, -1) at n < 2.
+// moments (DESIGN.md "SVGF from sample moments"; optional, addressed like the other two): the resolve writes (mu, nu,
+// r, float(n)) of the samples demodulated by the draw's own `emission` and `albedo` planes (read only when moments is
+// set), for the reproject and variance passes' sampler gSampleMoments.
 struct SppAdaptive {
   const uint8_t* counts;
   float2* stats;
+  float4* moments;
+  Plane emission, albedo;
 };
 
 // pt_sample_counts_derive: the next draw's count plane from a draw's statistics, followed along this frame's motion
@@ -340,12 +345,14 @@ struct ReprojParams {
   Plane out_illum, out_moments;
   float inv_w, inv_h, depth_thr, normal_thr;
   int block;  // 1: the four history taps from one 3x3 texel block per plane when they tile it (same texels, same bits)
+  Plane sm;   // gSampleMoments (kernels_svgf.hip header), p == null: not bound
 };
 
 struct VarianceParams {
   int W, H, y0, y1;
   Plane illum, moments, nd, fwidth, out;
   float phi_color, phi_normal;
+  Plane sm;  // gSampleMoments (kernels_svgf.hip header), p == null: not bound
 };
 
 struct AtrousParams {

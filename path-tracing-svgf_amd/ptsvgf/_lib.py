@@ -129,6 +129,7 @@ _PT_SIGS = [
     ("pt_pass_set_row_cost", C.c_int, [_u32, C.c_void_p]),
     ("pt_pass_set_sample_counts", C.c_int, [_u32, C.c_void_p]),
     ("pt_pass_set_sample_stats", C.c_int, [_u32, C.c_void_p]),
+    ("pt_pass_set_sample_moments", C.c_int, [_u32, C.c_void_p]),
     ("pt_sample_counts_derive", C.c_int, [C.c_void_p, _u32, _u32, C.c_float, C.c_float, C.c_int, C.c_void_p]),
     ("pt_sample_counts_pool", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _u32, _u32, C.c_float, C.c_float,
                                         C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),

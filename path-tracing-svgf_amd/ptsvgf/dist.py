@@ -477,6 +477,8 @@ class BandRenderer:
             raise ValueError("the multi-rank renderers take one sample per pixel (spp = 1)")
         if kw.get("adaptive") is not None:
             raise ValueError("the multi-rank renderers take one sample per pixel: no adaptive sample counts")
+        if kw.get("sample_moments"):
+            raise ValueError("the multi-rank renderers take one sample per pixel: no sample moments")
         if ghost_zone and kw.get("pt_source") is None:
             # the margin rows the SVGF passes draw read colour / emission / albedo the band's own path tracer never
             # draws (it covers the band only): without a source of those rows the band silently differs from a frame

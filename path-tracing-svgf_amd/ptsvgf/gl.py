@@ -477,6 +477,12 @@ class RenderPass:
         W * H float32 pairs on the device (0 unbinds)."""
         check(pt().pt_pass_set_sample_stats(self._handle(), C.c_void_p(device_ptr or None)))
 
+    def set_sample_moments(self, device_ptr: int) -> None:
+        """Path-tracing pass, spp > 1: the resolve writes (mu, nu, r, n) of each pixel's demodulated sample
+        luminances into W * H float32 quadruples on the device (0 unbinds): device_ptr() of the RGBA32F
+        texture the reproject and variance passes bind as "gSampleMoments"."""
+        check(pt().pt_pass_set_sample_moments(self._handle(), C.c_void_p(device_ptr or None)))
+
     def set_motion_bound(self, device_ptr: int) -> None:
         """G-buffer pass: store the largest |motion.y| of every draw into a device uint32 (float bits; 0 disables)."""
         check(pt().pt_pass_set_motion_bound(self._handle(), C.c_void_p(device_ptr or None)))

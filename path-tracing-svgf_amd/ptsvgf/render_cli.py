@@ -85,6 +85,8 @@ def main(argv=None) -> int:
                     help="pool the sample statistics over frames, the pooled weight held to W >= 2 (needs --adaptive)")
     ap.add_argument("--adaptive-rule", default="relative", choices=("relative", "absolute"),
                     help="TAU bounds the error relative to the mean luminance, or absolutely (needs --adaptive-pool)")
+    ap.add_argument("--sample-moments", action="store_true",
+                    help="SVGF's variance from the samples' own moments (needs --spp >= 2)")
     ap.add_argument("--sway", type=float, default=None, metavar="DEG",
                     help="bend the plant (object 2) by an 8-bone chain, the angle a sine over the frames of this amplitude")
     ap.add_argument("--device", type=int, default=0)
@@ -98,7 +100,8 @@ def main(argv=None) -> int:
     gl.init(a.device)
     try:
         r = Renderer(scene, a.width, a.height, parameter_config(), mode=a.mode, run_taa=True, run_output=True,
-                     spp=a.spp, adaptive=a.adaptive, adaptive_pool=a.adaptive_pool, adaptive_rule=a.adaptive_rule)
+                     spp=a.spp, adaptive=a.adaptive, adaptive_pool=a.adaptive_pool, adaptive_rule=a.adaptive_rule,
+                     sample_moments=a.sample_moments)
         r.set_view(a.view)
         sway = _sway_setup(r, scene) if a.sway is not None else None
         for f in range(a.frames):

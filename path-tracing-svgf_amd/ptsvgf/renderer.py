@@ -152,7 +152,7 @@ class Renderer:
                  trace_batch: int = 1, front_streams: int | None = None, pt_source=None, pt_flush=None,
                  stage_rows=None, early_history=None, draw_gbuffer: bool = True, fuse_modulate: bool = True,
                  host_pace: bool = False, spp: int = 1, adaptive=None, adaptive_pool=None,
-                 adaptive_rule: str = "relative", adaptive_zeta: float = 0.1):
+                 adaptive_rule: str = "relative", adaptive_zeta: float = 0.1, sample_moments: bool = False):
         """band = (y0, y1, row0, rows) for screen-band sharding; tex_factory(w, h) -> handle allocates the
         frame-sized planes (ptsvgf.dist wraps torch tensors); halo(stage, {plane name: handle}) is called before
         the SVGF passes that read rows beyond the band (dist.HALO_SCHEDULE names the planes); after_gbuffer(set,
@@ -209,10 +209,20 @@ class Renderer:
         depth tolerance of the history, > 0): the counts come from luminance statistics pooled over the slot's draws
         (DESIGN.md "Pooled sample statistics", pt_sample_counts_pool). Every slot owns two pool planes and two count
         planes, swapped every draw; the step runs at every frame of the slot, the first included (which writes the
-        depths and gives N on surfaces, 1 on the background). sample_pool() reads the current pool plane back."""
+        depths and gives N on surfaces, 1 on the background). sample_pool() reads the current pool plane back.
+
+        sample_moments (default False; needs spp >= 2; either driver, any K; composes with adaptive, adaptive_pool and
+        accumulate_color): SVGF's variance from the samples' own moments (DESIGN.md "SVGF from sample moments").
+        Every path-tracing slot owns one RGBA32F texture its draws' resolve fills with (mu, nu, r, n) per pixel
+        (pt_pass_set_sample_moments); the reproject and variance passes of that frame's back end bind it as
+        gSampleMoments. The mode is fixed for the renderer's life: its history holds per-sample moments from the
+        first frame on. sample_moments() reads the last frame's plane back."""
         if mode not in ("fast", "reference"):
             raise ValueError(mode)
         self._pool = self._check_adaptive_pool(adaptive, adaptive_pool, adaptive_rule, adaptive_zeta)
+        self._sm_on = self._check_sample_moments(sample_moments, self._check_spp(spp), band, pt_source)
+        if self._sm_on and int(trace_batch) > 1:
+            raise ValueError("sample_moments needs the slot's own draws: no trace batching")
         self.mode = mode
         self.W, self.H = int(width), int(height)
         self.cfg = config or parameter_config()
@@ -265,6 +275,7 @@ class Renderer:
         self._spp = self._check_spp(spp)
         self.adaptive = self._check_adaptive(adaptive, self._spp)
         self._ad: list = []  # per path-tracing slot: stats / counts (device tensors), last (frame of its last draw)
+        self._sm: list = []  # per path-tracing slot: the texture its resolve writes (sample_moments)
         if self.adaptive is not None and pt_source is not None:
             raise ValueError("adaptive needs the renderer's own path-tracing draws (no pt_source)")
         if not 1 <= self.B <= min(self.K, 8) or (self.B > 1 and mode != "fast"):
@@ -502,6 +513,14 @@ class Renderer:
                 p.set_sample_stats(ad["stats"].data_ptr())
                 p.set_sample_counts(ad["counts"].data_ptr())
                 self._ad.append(ad)
+            if self._sm_on:  # (library-allocated: the resolve addresses it by its device pointer in global rows)
+                import torch
+
+                sm = getTextureRGB32F(W, H)
+                torch.cuda.synchronize()  # its zero fill, before a draw on one of the renderer's own streams
+                self._owned.append(sm)
+                p.set_sample_moments(gl.device_ptr(sm))
+                self._sm.append(sm)
             self.pt_slots.append((p, outs))
         self.pass_path_tracing = PassGroup([p for p, _ in self.pt_slots])  # settings apply to every slot
 
@@ -655,6 +674,30 @@ class Renderer:
         torch.cuda.synchronize()
         return self._ad[(self.frame_index - 1) % len(self.pt_slots)][key].cpu().numpy()
 
+    def sample_moments(self) -> np.ndarray:
+        """The plane (mu, nu, r, n) the last frame's path-tracing draw wrote, (H, W, 4) float32. sample_moments only."""
+        if not self._sm_on:
+            raise ValueError("the renderer was built without sample_moments")
+        if self.frame_index < 1:
+            raise ValueError("no frame drawn yet")
+        import torch
+
+        self.flush()
+        torch.cuda.synchronize()
+        return gl.readback(self._sm[(self.frame_index - 1) % len(self.pt_slots)])
+
+    @staticmethod
+    def _check_sample_moments(on, spp, band=None, pt_source=None) -> bool:
+        if not on:
+            return False
+        if spp < 2:
+            raise ValueError("sample_moments needs spp >= 2: the plane is ignored at one sample per pixel")
+        if band is not None:
+            raise ValueError("sample_moments holds whole frames: no band")
+        if pt_source is not None:
+            raise ValueError("sample_moments needs the renderer's own path-tracing draws (no pt_source)")
+        return True
+
     @staticmethod
     def _check_adaptive(tau, spp):
         if tau is None:
@@ -700,6 +743,7 @@ class Renderer:
     def spp(self, n) -> None:
         n = self._check_spp(n)
         self._check_adaptive(self.adaptive, n)
+        self._check_sample_moments(self._sm_on, n)
         if n == self._spp:
             return
         self._issue_batch()  # frames of an open batch were set up at the old count
@@ -744,6 +788,8 @@ class Renderer:
         rp.set_texture_uniform(GL_TEXTURE_2D, g["normal_depth"], "gNormalAndLinearZ")
         rp.set_texture_uniform(GL_TEXTURE_2D, self.last_normal_depth, "gPrevNormalAndLinearZ")
         rp.set_texture_uniform(GL_TEXTURE_2D, g["fwidth"], "gNormalDepthFwidth")
+        if self._sm_on:
+            rp.set_texture_uniform(GL_TEXTURE_2D, self._sm[self._slot], "gSampleMoments")
         self._draw(rp, "reproject")
         vp = self.variance_compute_pass                        # main.cpp:488-495
         vp.reset_texture_slot()
@@ -753,6 +799,8 @@ class Renderer:
         vp.set_texture_uniform(GL_TEXTURE_2D, self.curMomentHistory, "gMoments_HistoryLength")
         vp.set_texture_uniform(GL_TEXTURE_2D, g["normal_depth"], "gNormalAndLinearZ")
         vp.set_texture_uniform(GL_TEXTURE_2D, g["fwidth"], "gNormalDepthFwidth")
+        if self._sm_on:
+            vp.set_texture_uniform(GL_TEXTURE_2D, self._sm[self._slot], "gSampleMoments")
         self._draw(vp, "variance")
         ap = self.atrous_pass                                  # main.cpp:499-526
         for i in range(cfg.num_atrous_iterations):
@@ -884,6 +932,8 @@ class Renderer:
         rp.set_texture_uniform(GL_TEXTURE_2D, g["normal_depth"], "gNormalAndLinearZ")
         rp.set_texture_uniform(GL_TEXTURE_2D, gp["normal_depth"], "gPrevNormalAndLinearZ")
         rp.set_texture_uniform(GL_TEXTURE_2D, g["fwidth"], "gNormalDepthFwidth")
+        if self._sm_on:
+            rp.set_texture_uniform(GL_TEXTURE_2D, self._sm[ctx["slot"]], "gSampleMoments")
         self._rows(rp, "reproject")
         self._draw(rp, "reproject")
         self._halo("variance", {"illum": self.illum, "moments": self.moments[b], "nd": g["normal_depth"]})
@@ -895,6 +945,8 @@ class Renderer:
         vp.set_texture_uniform(GL_TEXTURE_2D, self.moments[b], "gMoments_HistoryLength")
         vp.set_texture_uniform(GL_TEXTURE_2D, g["normal_depth"], "gNormalAndLinearZ")
         vp.set_texture_uniform(GL_TEXTURE_2D, g["fwidth"], "gNormalDepthFwidth")
+        if self._sm_on:
+            vp.set_texture_uniform(GL_TEXTURE_2D, self._sm[ctx["slot"]], "gSampleMoments")
         self._rows(vp, "variance")
         self._draw(vp, "variance")
         # a-trous chain without copies: i0 var->ping, i1 ping->hist[b] (next frame's history),
