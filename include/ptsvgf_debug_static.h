@@ -33,6 +33,29 @@ int pt_debug_static_key_diff(int kind, const uint64_t* a, const uint64_t* b, int
 int pt_debug_static_key_hit(int kind, const uint64_t* last, int last_valid, const uint64_t* now, int words, int enabled,
                             int* hit);
 
+/* ---- The bounce-0 point-light verdict cache of a path-tracing pass (DESIGN.md "Static view, part 2"; pass uniform
+ * point_cache, default 1; csrc/point_cache.h for the word's layout).
+ *
+ * Of the pass's last draw: the bounce-0 point-light verdicts served from the cache and those queued as rays. Device
+ * counters; the call synchronises the device. PT_ERR_STATE before the pass's first wavefront draw. */
+int pt_debug_point_cache_counts(uint32_t pass, uint64_t* served, uint64_t* queued);
+/* The verdict plane itself, one 16-bit word per pixel of the rows the pass last drew (n: that pixel count, row-major
+ * from the first row drawn). Both synchronise the device. */
+int pt_debug_point_cache_read(uint32_t pass, uint16_t* words, size_t n);
+int pt_debug_point_cache_write(uint32_t pass, const uint16_t* words, size_t n);
+/* The mode of the pass's last draw (0 off, 1 reset, 2 use) and whether the plane holds verdicts now (1) or is stale. */
+int pt_debug_point_cache_mode(uint32_t pass, int* mode, int* valid);
+/* The word's bit operations on the host, no device: op 0 look-up of light arg (*out: -1 as 0xFFFFFFFF not known, 0 lit,
+ * 1 occluded), 1 the pending light (-1 none), 2 mark light arg pending, 3 resolve the pending light with verdict arg. */
+int pt_debug_point_cache_word(int op, uint32_t word, int arg, uint32_t* out);
+/* The cache's key (csrc/static_key.h LightsKey), as pt_debug_static_key_* for the other two: the word count, the first
+ * differing word (-1: equal), and the mode a draw with key `now` gets after the draw that left `last` (last_valid: the
+ * plane holds that draw's verdicts; stage_reused: this draw reads the cached primary hit; enabled: nothing bypasses). */
+int pt_debug_point_cache_key_words(void);
+int pt_debug_point_cache_key_diff(const uint64_t* a, const uint64_t* b, int words, int* field);
+int pt_debug_point_cache_key_mode(const uint64_t* last, int last_valid, const uint64_t* now, int words, int stage_reused,
+                                  int enabled, int* mode);
+
 #ifdef __cplusplus
 }
 #endif

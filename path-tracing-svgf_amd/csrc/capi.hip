@@ -119,8 +119,9 @@ int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1, int nsp = 0) {
   const size_t nl = (size_t)wf_list_capacity(W, rows) * 8;  // 8 list segments
   auto up = [&](size_t v) { return (v + al - 1) / al * al; };
   const size_t lists = up(nl * 4 * kLiveBins) * 2 + up(nl * 4 * (1 + kPointBins));
-  // (the second up(m * 8) of int2: the primary hit plane hit0, 8 bytes per pixel)
-  size_t total = up(f4) * 10 + up(m * 8) * 2 + up(m * 4) + up(m) * 2 + lists * nb + up(m * 8) + up(m * 4) +
+  // (the second up(m * 8) of int2: the primary hit plane hit0, 8 bytes per pixel; up(m * 2): the point-light verdict
+  // plane pcache, 2 bytes per pixel)
+  size_t total = up(f4) * 10 + up(m * 8) * 2 + up(m * 2) + up(m * 4) + up(m) * 2 + lists * nb + up(m * 8) + up(m * 4) +
                  up((size_t)nb * kWfCounters * 4) + (nsp ? up((size_t)nsp * n * 16) : 0);
   if (hipMalloc(&b.base, total) != hipSuccess) { b.base = nullptr; return PT_ERR_HIP; }
   b.gen++;
@@ -131,6 +132,7 @@ int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1, int nsp = 0) {
   for (auto q : f4p) { *q = (float4*)c; c += up(f4); }
   s0.hit = (int2*)c; c += up(m * 8);
   s0.hit0 = (int2*)c; c += up(m * 8);
+  s0.pcache = (uint16_t*)c; c += up(m * 2);
   s0.seed = (uint32_t*)c; c += up(m * 4);
   s0.occ_h = (uint8_t*)c; c += up(m);
   s0.occ_p = (uint8_t*)c; c += up(m);
@@ -152,6 +154,7 @@ int wf_alloc(WFBuffers& b, int W, int rows, int nb = 1, int nsp = 0) {
     st.sh_p = s0.sh_p + o;
     st.hit = s0.hit + o;
     st.hit0 = s0.hit0 + o;
+    st.pcache = s0.pcache + o;
     st.seed = s0.seed + o;
     st.occ_h = s0.occ_h + o;
     st.occ_p = s0.occ_p + o;
@@ -679,6 +682,8 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
   if (lt && lt->target == PT_TEXTURE_BUFFER) {
     k.scene.lights = (const float*)lt->dev;
     k.scene.nlights_buf = (int)(lt->bytes / (6 * sizeof(float)));
+    reads.light_handle = lh;
+    reads.light_ver = lt->version;
   }
   // uniform sampler2DArray material_array (path_tracing.frag:331-364); unbound -> fetches read 0
   Texture* ma = sampler(p, "material_array");
@@ -873,6 +878,32 @@ void primary_cache_note(Pass* p, const ptk::PrimaryKey& key, bool reused, bool o
   }
 }
 
+// The bounce-0 point-light verdict cache of a one-sample wavefront draw (DESIGN.md "Static view, part 2"), after
+// pt_wf_setup: the cache's key of this draw (the primary key and what the bounce-0 shadow ray reads beyond it) and the
+// draw's mode, into k.point_cache. The draw's caller notes the outcome (ptk::point_cache_note).
+ptk::LightsKey point_cache_mode_for(Pass* p, PTParams& k, const ptk::PrimaryKey& pkey, bool stage_reused,
+                                    const DrawReads& reads) {
+  using namespace ptk;
+  LightsKey q{};
+  memcpy(q.w + kLkPrimary0, pkey.w, sizeof(pkey.w));
+  q.w[kLkLightHandle] = reads.light_handle;
+  q.w[kLkLightDev] = key_bits((const void*)k.scene.lights);
+  q.w[kLkLightVer] = reads.light_ver;
+  q.w[kLkPointLightSize] = key_bits(k.pointLightSize);
+  q.w[kLkNlightsBuf] = key_bits(k.scene.nlights_buf);
+  q.w[kLkPointBins] = key_bits(k.point_bins);
+  q.w[kLkPointBinsDev] = key_bits((const void*)(k.point_bins ? k.pbins.hdr : nullptr));
+  q.w[kLkPlane] = key_bits((const void*)k.wf.pcache);
+  // (the counters of shadow_point_rays must stay what they are when statistics are asked for; launch_wavefront
+  // engages the cache only where its shades are folded, `shade_fold && max_depth > 0`: a draw of no bounce launches
+  // no shade at all, so it must not count as the draw that reset the plane)
+  const bool fold = k.shade_fold && k.max_depth > 0;
+  const bool bypass = ui(p, "point_cache", 1) == 0 || p->stats || p->row_cost || k.pointLightSize < 1 ||
+                      k.pointLightSize > kPcLights || k.wf.spill || !fold;
+  k.point_cache = point_cache_mode(p->lcache, q, stage_reused, bypass);
+  return q;
+}
+
 // The side stream and events of path-tracing draws issued on `s` (uniform trace_fork = 1), created on first use: one
 // per draw stream, so frames in flight on different streams do not queue behind each other's shadow walks. An entry
 // lives until its stream is released (pt_stream_release, which the host's stream pool calls when a renderer gives a
@@ -954,6 +985,8 @@ int draw_pathtrace_spp(Pass* p, PTParams& k, SceneGPU* sg, int n) {
   int rc;
   const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
   if (rc) return rc;
+  p->lcache.valid = false;  // (the samples would share one verdict word: the cache is bypassed)
+  p->lcache_last_mode = 0;
   rc = launch_pathtrace_wavefront_spp(ks, rs, g.stream, fk, &ad, reuse);
   primary_cache_note(p, key, reuse, rc == 0);
   if (!rc && k.tiles.cost) p->order.ordered = true;
@@ -983,6 +1016,8 @@ int draw_pathtrace(Pass* p) {
       return err(PT_ERR_ARG, "the megakernel (pt_kernel=1) walks a 32-entry LDS stack; this BVH is deeper: use the "
                              "wavefront path tracer (pt_kernel=0, the default)");
     p->pcache.valid = false;  // (it sorts the pass's tile order by its own costs)
+    p->lcache.valid = false;
+    p->lcache_last_mode = 0;
     rc = launch_pathtrace(k, g.stream);
   } else {                            // 0: wavefront (kernels_wavefront.hip), production
     TRY(wf_alloc(p->wf, k.W, std::max(0, k.y1 - k.y0)));
@@ -992,8 +1027,11 @@ int draw_pathtrace(Pass* p) {
     TRY(pt_wf_setup(p, k, sg, p->wf.st, &key, &reuse));
     const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
     if (rc) return rc;
+    const ptk::LightsKey lkey = point_cache_mode_for(p, k, key, reuse, reads);
     rc = launch_pathtrace_wavefront(k, g.stream, fk, reuse);
     primary_cache_note(p, key, reuse, rc == 0);
+    ptk::point_cache_note(p->lcache, lkey, k.point_cache, rc == 0);
+    p->lcache_last_mode = k.point_cache;
     if (!rc && k.tiles.cost) p->order.ordered = true;
   }
   if (rc) return hip_err((hipError_t)rc, "pathtrace launch");
@@ -1039,7 +1077,10 @@ int draw_pathtrace_batch(Pass** ps, int n) {
   if (wf_spill(h->wf, k[0].stack_need) != PT_OK) return err(PT_ERR_HIP, "spill stack allocation failed");
   // A batch always runs the stage, into the head pass's planes, and sorts every pass's tile order: no pass keeps a key
   // that claims a plane or an order this draw changed. Each counts as a draw that ran the stage.
-  for (int b = 0; b < n; ++b) ps[b]->pcache.valid = false;
+  for (int b = 0; b < n; ++b) {
+    ps[b]->pcache.valid = ps[b]->lcache.valid = false;
+    ps[b]->lcache_last_mode = 0;
+  }
   for (int b = 0; b < n; ++b) TRY(pt_wf_setup(ps[b], k[b], sg, h->wf.stb[b]));
   // the batched shadow launches read frame 0's point-light bins for every frame: frames that do not share them (other
   // lights, another pointLightSize) all walk
@@ -1191,7 +1232,11 @@ int draw_raster(Pass* p) {
   TRY(att_plane(p, 2, &k.motion));
   TRY(att_plane(p, 3, &k.fwidth));
   Texture* fwt = tex_of(p->att[3]);
-  if (!fwt->aux) HIPCHK(hipMalloc((void**)&fwt->aux, (size_t)fwt->W * fwt->rows * 4));
+  if (!fwt->aux) {  // rows no draw has reached read 0 (pt_texture_readback_aux returns the whole plane)
+    const size_t n = (size_t)fwt->W * fwt->rows;
+    HIPCHK(hipMalloc((void**)&fwt->aux, n * 4));
+    HIPCHK(hipMemsetAsync(fwt->aux, 0, n * 4, g.stream));
+  }
   k.fwidth_aux = fwt->aux;
   // the a-trous per-tile surface flags of this G-buffer, marked by the G-buffer kernels as they write the pixels
   TRY(gbuf_flags(p, fwt, k));
@@ -1826,6 +1871,101 @@ int pt_debug_static_key_hit(int kind, const uint64_t* last, int last_valid, cons
   return PT_OK;
 }
 
+// ---- the bounce-0 point-light verdict cache (DESIGN.md "Static view, part 2")
+static int point_cache_pass(const char* who, uint32_t pass, Pass** out) {
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (g.programs[p->program] != PK_PATHTRACE) return err(PT_ERR_ARG, std::string(who) + ": a path-tracing pass");
+  if (!p->wf.base) return err(PT_ERR_STATE, std::string(who) + ": the pass has not drawn with the wavefront path tracer");
+  *out = p;
+  return PT_OK;
+}
+
+int pt_debug_point_cache_counts(uint32_t pass, uint64_t* served, uint64_t* queued) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p;
+  TRY(point_cache_pass("pt_debug_point_cache_counts", pass, &p));
+  HIPCHK(hipDeviceSynchronize());
+  int c[ptk::kWfCtr];  // bounce 0's counters of frame 0
+  HIPCHK(hipMemcpy(c, p->wf.st.counters, sizeof(c), hipMemcpyDeviceToHost));
+  uint64_t q = 0;
+  for (int i = 0; i < 8 * ptk::kPointBins; ++i) q += (uint64_t)c[ptk::kCtrPoint + i];
+  uint64_t sv = 0;
+  for (int i = 0; i < 8; ++i) sv += (uint64_t)c[ptk::kCtrPcServed + i];
+  if (served) *served = sv;
+  if (queued) *queued = q;
+  return PT_OK;
+}
+
+int pt_debug_point_cache_read(uint32_t pass, uint16_t* words, size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p;
+  TRY(point_cache_pass("pt_debug_point_cache_read", pass, &p));
+  if (!words || n != p->wf.n) return err(PT_ERR_ARG, "pt_debug_point_cache_read: one word per pixel of the pass's rows");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(words, p->wf.st.pcache, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+int pt_debug_point_cache_write(uint32_t pass, const uint16_t* words, size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p;
+  TRY(point_cache_pass("pt_debug_point_cache_write", pass, &p));
+  if (!words || n != p->wf.n) return err(PT_ERR_ARG, "pt_debug_point_cache_write: one word per pixel of the pass's rows");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(p->wf.st.pcache, words, n * sizeof(uint16_t), hipMemcpyHostToDevice));
+  return PT_OK;
+}
+
+int pt_debug_point_cache_mode(uint32_t pass, int* mode, int* valid) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (g.programs[p->program] != PK_PATHTRACE) return err(PT_ERR_ARG, "pt_debug_point_cache_mode: a path-tracing pass");
+  if (mode) *mode = p->lcache_last_mode;
+  if (valid) *valid = p->lcache.valid ? 1 : 0;
+  return PT_OK;
+}
+
+int pt_debug_point_cache_word(int op, uint32_t word, int arg, uint32_t* out) {
+  if (!out) return err(PT_ERR_ARG, "pt_debug_point_cache_word: null argument");
+  if ((op == 0 || op == 2) && (arg < 0 || arg >= ptk::kPcLights))
+    return err(PT_ERR_ARG, "pt_debug_point_cache_word: a light index in 0 .. 3");
+  switch (op) {
+    case 0: *out = (uint32_t)ptk::pc_lookup(word, arg); break;
+    case 1: *out = (uint32_t)ptk::pc_pending(word); break;
+    case 2: *out = ptk::pc_mark_pending(word, arg); break;
+    case 3: *out = ptk::pc_resolve(word, arg != 0); break;
+    default: return err(PT_ERR_ARG, "pt_debug_point_cache_word: op 0 (look-up) .. 3 (resolve)");
+  }
+  return PT_OK;
+}
+
+int pt_debug_point_cache_key_words(void) { return (int)ptk::kLkWords; }
+
+int pt_debug_point_cache_key_diff(const uint64_t* a, const uint64_t* b, int words, int* field) {
+  if (!a || !b || !field) return err(PT_ERR_ARG, "pt_debug_point_cache_key_diff: null argument");
+  if (words != (int)ptk::kLkWords) return err(PT_ERR_ARG, "pt_debug_point_cache_key_diff: not the key's word count");
+  ptk::LightsKey ka, kb;
+  memcpy(ka.w, a, sizeof(ka.w));
+  memcpy(kb.w, b, sizeof(kb.w));
+  *field = ptk::lights_key_diff(ka, kb);
+  return PT_OK;
+}
+
+int pt_debug_point_cache_key_mode(const uint64_t* last, int last_valid, const uint64_t* now, int words, int stage_reused,
+                                  int enabled, int* mode) {
+  if (!last || !now || !mode) return err(PT_ERR_ARG, "pt_debug_point_cache_key_mode: null argument");
+  if (words != (int)ptk::kLkWords) return err(PT_ERR_ARG, "pt_debug_point_cache_key_mode: not the key's word count");
+  ptk::PointCache c;
+  ptk::LightsKey k;
+  memcpy(c.key.w, last, sizeof(c.key.w));
+  memcpy(k.w, now, sizeof(k.w));
+  c.valid = last_valid != 0;
+  *mode = ptk::point_cache_mode(c, k, stage_reused != 0, !enabled);
+  return PT_OK;
+}
+
 int pt_texarray_create(int w, int h, int layers, uint32_t* out) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   TRY(ensure_init());
@@ -1992,7 +2132,11 @@ int pt_raster_pass_adopt(uint32_t pass, int y_begin, int y_end) {
     if (y_begin < t->row0 || y_end > t->row0 + t->rows)
       return err(PT_ERR_ARG, "pt_raster_pass_adopt: rows outside the attachments' stored rows");
   }
-  if (!fwt->aux) HIPCHK(hipMalloc((void**)&fwt->aux, (size_t)fwt->W * fwt->rows * 4));
+  if (!fwt->aux) {  // rows no draw has reached read 0 (pt_texture_readback_aux returns the whole plane)
+    const size_t n = (size_t)fwt->W * fwt->rows;
+    HIPCHK(hipMalloc((void**)&fwt->aux, n * 4));
+    HIPCHK(hipMemsetAsync(fwt->aux, 0, n * 4, g.stream));
+  }
   k.fwidth_aux = fwt->aux;
   TRY(gbuf_flags(p, fwt, k));
   const int rc = ptk::launch_gbuffer_adopt(k, g.stream);

@@ -117,6 +117,8 @@ struct Pass {
   TileOrder order;
   ptk::PrimaryCache pcache;  // path-tracing pass: the primary-hit cache (static_key.h, DESIGN.md "Static view")
   ptk::GbufCache gcache;     // rasterize pass: its last completed draw's key (reuse_static)
+  ptk::PointCache lcache;    // path-tracing pass: the bounce-0 point-light verdict cache (DESIGN.md "Static view, part 2")
+  int lcache_last_mode = 0;  // the PointCacheMode of the pass's last draw (pt_debug_point_cache_mode)
   int W = 0, H = 0;
   std::vector<uint32_t> att;
   bool bound = false, final_pass = false;
@@ -229,6 +231,9 @@ struct SharedBuf {
 struct DrawReads {
   SharedBuf* hdr = nullptr;
   SharedBuf* pbins = nullptr;
+  // the pointLights texture the draw bound (0: none): part of the verdict cache's key (static_key.h)
+  uint32_t light_handle = 0;
+  uint64_t light_ver = 0;
 };
 
 // The point-light triangle bins of a scene (ptk::PointBinsDev, kernels_pointbins.hip) for the lights texture a

@@ -1650,7 +1650,15 @@ __device__ __forceinline__ void finish_apply(const PTParams& p, int pid, v3* red
   nt.ppdf = p.pointLightSize != 0 ? (2.0f * PT_PI) / (float)p.pointLightSize : 0.0f;
   v3 cosb = xyz(q3);
   v3 red = *red_io, light = *light_io;
-  v3 hitLight = nee_hit_light(red, nt, p.wf.occ_h[pid] != 0, p.wf.occ_p[pid] != 0);
+  const bool occ_p = p.wf.occ_p[pid] != 0;
+  // The verdict cache's write-back (point_cache.h), only in the launch that consumes bounce 0's verdicts (every other
+  // launch gets kPcOff): the light whose ray the bounce-0 shade queued for this pixel is now known. The five kernels
+  // that write occ_p stay as they are, so a cached verdict is the one the walk produced.
+  if (p.point_cache != kPcOff) {
+    const uint32_t w = p.wf.pcache[pid];
+    if (pc_pending(w) >= 0) p.wf.pcache[pid] = (uint16_t)pc_resolve(w, occ_p);
+  }
+  v3 hitLight = nee_hit_light(red, nt, p.wf.occ_h[pid] != 0, occ_p);
   red = mul(red, divs(cosb, nt.bpdf));
   light = add(light, hitLight);
   *red_io = red;
@@ -1716,6 +1724,7 @@ __device__ __forceinline__ void shade_body(const PTParams& p, int bounce_rt, con
       valid = bins_get(list_in, counts_in, kLiveBins, cap, k, &pid);
     }
     bool push = false, need_h = false, need_p = false;
+    bool served = false;  // (bounce 0, point_cache = use) the point-light verdict came from the cache: no ray
     int pbin = 0;  // point-light list of this ray (light index mod kPointBins)
     int lbin = 0;  // live list of the continuing ray (direction octant)
     if (valid) {
@@ -1725,6 +1734,13 @@ __device__ __forceinline__ void shade_body(const PTParams& p, int bounce_rt, con
       v3 S, d;
       uint32_t seed;
       v3 light, red;
+      // bounce 0 with the verdict cache engaged (point_cache.h): the pixel's word, and whether this thread stores it.
+      // Reset: every pixel stores a fresh word. Use: only a pixel that queues a ray whose verdict is not known yet.
+      // (Folded bounce-0 instantiations only: the unfolded shade, shade_fold = 0, decides `first` at run time and
+      // spilled 32 bytes more with this in it, so the host bypasses the cache for it.)
+      constexpr bool kPc = FOLD && FIRST;
+      uint32_t pcw = 0;
+      bool pc_store = kPc && p.point_cache == kPcReset;
       if (first) {
         S = mk(p.eye[0], p.eye[1], p.eye[2]);
         d = primary_dir(p, x, y);
@@ -1785,9 +1801,10 @@ __device__ __forceinline__ void shade_body(const PTParams& p, int bounce_rt, con
           // calculatePointLight, as if unoccluded (:884-919)
           v3 pcalc = splat(0.0f);
           float4 shp = f4(0.0f, 0.0f, 0.0f, -1.0f);
+          int li = 0;
           if (p.pointLightSize != 0) {
             float ppdf = (2.0f * PT_PI) / (float)p.pointLightSize;
-            int li = (int)(u32_to_unit(wang_hash(&seed)) * (float)p.pointLightSize);
+            li = (int)(u32_to_unit(wang_hash(&seed)) * (float)p.pointLightSize);
             pbin = li & (kPointBins - 1);
             v3 lpos = splat(0.0f), lrad = splat(0.0f);
             if (li >= 0 && li < p.scene.nlights_buf) {
@@ -1810,6 +1827,24 @@ __device__ __forceinline__ void shade_body(const PTParams& p, int bounce_rt, con
           const bool pz = zero_bits(pcalc);
           need_p = shp.w >= 0.0f && !pz;
           need_h = !(pz && zero_bits(hcalc) && zero_bits(bcalc) && __builtin_isfinite(hpdf) && __builtin_isfinite(bpdf));
+          // The verdict "light li is occluded from this pixel's first hit" does not depend on the frame: once a ray
+          // has brought it back (finish_apply), later frames of the same view store it instead of queueing the ray.
+          uint8_t occ_p0 = 0;
+          if (kPc && p.point_cache != kPcOff && need_p && (unsigned)li < (unsigned)kPcLights) {
+            if (p.point_cache == kPcUse) {
+              pcw = p.wf.pcache[pid];
+              const int v = pc_lookup(pcw, li);
+              if (v >= 0) {
+                occ_p0 = (uint8_t)v;
+                need_p = false;
+                served = true;
+              }
+            }
+            if (need_p) {
+              pcw = pc_mark_pending(pcw, li);
+              pc_store = true;
+            }
+          }
           stnt(&p.wf.pend0[pid], f4(hcalc.x, hcalc.y, hcalc.z, hpdf));
           stnt(&p.wf.pend1[pid], f4(pcalc.x, pcalc.y, pcalc.z, bpdf));
           stnt(&p.wf.pend2[pid], f4(bcalc.x, bcalc.y, bcalc.z, 0.0f));
@@ -1820,13 +1855,20 @@ __device__ __forceinline__ void shade_body(const PTParams& p, int bounce_rt, con
           if (!(FOLD && LAST)) stnt(&p.wf.ray_d[pid], f4(L.x, L.y, L.z, 0.0f));
           stnt(&p.wf.red[pid], f4(red.x, red.y, red.z, 0.0f));
           stnt(&p.wf.occ_h[pid], (uint8_t)0);
-          stnt(&p.wf.occ_p[pid], (uint8_t)0);
+          stnt(&p.wf.occ_p[pid], occ_p0);
         } else if (FOLD) {
           terminal_write(p, x, y, light);
         }
       }
       if (!FOLD || (push && !LAST)) stnt(&p.wf.seed[pid], seed);
       if (!FOLD || push) stnt(&p.wf.light[pid], f4(light.x, light.y, light.z, 0.0f));
+      if (pc_store) p.wf.pcache[pid] = (uint16_t)pcw;
+    }
+    if (FOLD && FIRST && p.point_cache == kPcUse) {
+      // pt_debug_point_cache_counts: one add per block that served any, spread over 8 words as the lists' segment
+      // counts are (a 4K frame has 32 400 blocks; per wave into one word the adds queued up at one L2 address)
+      const int n = __syncthreads_count(served);
+      if (threadIdx.x == 0 && n) atomicAdd(&p.wf.counters[kCtrPcServed + (blockIdx.x & 7)], n);
     }
     // HDR and point-light shadow rays go to separate lists so trace waves stay homogeneous
 
@@ -2286,6 +2328,11 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
   const bool split = fk && !DEEP && p.max_depth > 1;
   // paths end in place (shade_fold; a path of no bounce has no shade to end in: wf_finalize writes its colour)
   const bool fold = p.shade_fold && p.max_depth > 0;
+  // The bounce-0 point-light verdict cache (point_cache.h): the mode goes to the bounce-0 shade, which looks verdicts up
+  // and marks the rays it queues, and to the one launch that consumes bounce 0's verdicts (finish_apply), which writes
+  // them back: the bounce-1 shade, or at depth 1 bounce 0's wf_finish. Every other launch gets kPcOff. One frame,
+  // one sample, no deep tree, folded shades: the caller bypasses the cache otherwise (capi.hip point_cache_mode_for).
+  const int pc_mode = (nb == 1 && !rs && !DEEP && fold) ? p.point_cache : (int)kPcOff;
   for (int i = 0; i < p.max_depth; ++i) {
     if (i > 0) closest(i);
     if (i == 1 && split) {
@@ -2293,18 +2340,18 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
       if (e != hipSuccess) return (int)e;
     }
     for (int b = 0; b < nb; ++b) {
-      PTParams shared;
+      PTParams shared = ps[b];
+      shared.point_cache = (i == 0 || (i == 1 && fold)) ? pc_mode : (int)kPcOff;
       if (i == 0) {
         // The bounce-0 shade reads the primary hit plane (above); sample b of an spp draw reads sample 0's (and, the
         // samples being copies of one pass, its tiles.perm_next). No launch of this draw after the stage writes hit0:
         // the bounce-1 trace writes wf.hit. The first-hit planes are sample 0's alone: the folded shade skips the
         // stores of null planes; the unfolded one (shade_fold = 0, A/B) has no such branch and stores into the
         // sample's own colour plane, every texel of which its wf_finalize writes afterwards on `s`.
-        shared = ps[b];
         shared.wf.hit = ps[rs ? 0 : b].wf.hit0;
         if (rs && b > 0) shared.emission = shared.albedo = fold ? Plane{} : ps[b].color;
       }
-      const PTParams& f = i == 0 ? shared : ps[b];
+      const PTParams& f = shared;
       const int* live_in = f.wf.counters + kWfCtr * (i > 0 ? i - 1 : 0);
 #define PT_SHADE_LAUNCH(FOLD, FIRST, LAST)                                                                          \
   hipLaunchKernelGGL((wf_shade<FOLD, FIRST, LAST>), dim3(i == 0 ? gS0 : gL), dim3(256), 0, s, f, i,                  \
@@ -2382,12 +2429,14 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
     // folded: bounce i's verdicts are applied at the top of the bounce-(i + 1) shade; the last bounce's finish ends
     // the paths still alive
     for (int b = 0; b < nb && !(fold && i + 1 < p.max_depth); ++b) {
+      PTParams f = ps[b];
+      f.point_cache = i == 0 ? pc_mode : (int)kPcOff;
       if (fold)
-        hipLaunchKernelGGL(wf_finish<true>, dim3(gL), dim3(256), 0, ss, ps[b], (const int*)lst(ps[b], i),
-                           (const int*)(ps[b].wf.counters + kWfCtr * i), cap);
+        hipLaunchKernelGGL(wf_finish<true>, dim3(gL), dim3(256), 0, ss, f, (const int*)lst(f, i),
+                           (const int*)(f.wf.counters + kWfCtr * i), cap);
       else
-        hipLaunchKernelGGL(wf_finish<false>, dim3(gL), dim3(256), 0, ss, ps[b], (const int*)lst(ps[b], i),
-                           (const int*)(ps[b].wf.counters + kWfCtr * i), cap);
+        hipLaunchKernelGGL(wf_finish<false>, dim3(gL), dim3(256), 0, ss, f, (const int*)lst(f, i),
+                           (const int*)(f.wf.counters + kWfCtr * i), cap);
     }
     if (i == 0 && split) {
       const hipError_t e = hipEventRecord(fk->join, ss);

@@ -23,6 +23,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "point_cache.h"
 #include "pt_layout.h"  // kStack, kWideStride, kNoneRef and the PT_KSTACK / PT_WIDE_STRIDE / PT_WIDE_ORDER defaults
 
 namespace ptk {
@@ -55,7 +56,10 @@ constexpr int kLiveBins = 1;  // live-ray lists (by direction octant, 8 of them,
 constexpr int kCtrHdr = 8 * kLiveBins, kCtrPoint = kCtrHdr + 8, kCtrStrag = kCtrPoint + 8 * kPointBins;
 // per-XCD work-queue heads of the refill traversal kernels launched in bounce i: shadow rays, closest-hit rays
 constexpr int kCtrQShadow = kCtrStrag + 1, kCtrQClosest = kCtrQShadow + 8, kCtrStragC = kCtrQClosest + 8;
-constexpr int kWfCtr = (kCtrStragC + 1 + 63) / 64 * 64;
+// bounce 0's base only: bounce-0 point-light verdicts the verdict cache served, in 8 words by block (point_cache.h;
+// those queued as rays are the kCtrPoint counts)
+constexpr int kCtrPcServed = kCtrStragC + 1;
+constexpr int kWfCtr = (kCtrPcServed + 8 + 63) / 64 * 64;
 constexpr int kWfCounters = 4 * kWfCtr;  // 4 bounces  // "no node" (leaf refs are >= -(2^31 - 1))
 
 struct Plane {          // banded RGBA32F plane
@@ -139,6 +143,9 @@ struct WFState {
   // from the same view skips the stage (DESIGN.md "Static view"). Host side only: launch_wavefront passes it to the
   // primary and bounce-0 launches as their `hit`; no kernel names this field.
   int2* hit0;
+  // The bounce-0 point-light verdicts of this pass's pixels from the view hit0 was traced for (point_cache.h): one
+  // word per pixel, touched only by draws whose PTParams::point_cache is not kPcOff.
+  uint16_t* pcache;
 };
 // Traversal counters of one path-tracing draw (pt_pass_set_trace_stats): rays traced and node + triangle visits
 // per traversal kind, tie re-walks on the reference tree, primary rays retried unbounded after the G-buffer bound, rays
@@ -309,6 +316,9 @@ struct PTParams {
   // over `pbins`; the shadow walks take the HDR rays and the other lights' (uniform point_bins; capi.hip point_bins_for)
   int point_bins;
   PointBinsDev pbins;
+  // the bounce-0 point-light verdict cache's mode for this launch (PointCacheMode, point_cache.h). launch_wavefront
+  // hands it to the bounce-0 shade and to the launch that consumes bounce 0's verdicts; every other launch gets kPcOff.
+  int point_cache;
 };
 
 struct GBufParams {

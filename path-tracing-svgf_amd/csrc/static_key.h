@@ -63,6 +63,55 @@ inline bool primary_cache_hit(const PrimaryCache& c, const PrimaryKey& now, bool
   return !bypass && c.valid && primary_key_diff(c.key, now) < 0;
 }
 
+// ------------------------------------------- the bounce-0 point-light verdicts ---
+// The key of the verdict cache (point_cache.h, DESIGN.md "Static view, part 2"): a verdict is a function of the
+// pixel's first hit point, which the primary key covers, and of what the bounce-0 shadow ray reads beyond it.
+enum LightsKeyField {
+  kLkPrimary0,                             // the draw's whole PrimaryKey
+  kLkLightHandle = kLkPrimary0 + kPkWords, // the pointLights texture: handle, device pointer, Texture::version
+  kLkLightDev, kLkLightVer,
+  kLkPointLightSize, kLkNlightsBuf,        // which light a pixel picks, and which indices read a light at all
+  kLkPointBins, kLkPointBinsDev,           // who decides the ray (the lights' triangle bins or the walk), and the bins
+  kLkPlane,                                // WFState::pcache of this draw (kPkPlaneGen covers the allocation)
+  kLkWords
+};
+
+struct LightsKey {
+  uint64_t w[kLkWords];
+};
+
+inline int lights_key_diff(const LightsKey& a, const LightsKey& b) {
+  for (int i = 0; i < kLkWords; ++i)
+    if (a.w[i] != b.w[i]) return i;
+  return -1;
+}
+
+// The verdict cache of a path-tracing pass: the key of the draw that reset the plane, and whether the plane still
+// holds verdicts of that key (false: stale).
+struct PointCache {
+  LightsKey key{};
+  bool valid = false;
+};
+
+// The mode of a draw (PointCacheMode: 0 off, 1 reset, 2 use). stage_reused: the draw reads the cached primary hit
+// (primary_cache_hit). bypass: point_cache = 0, trace statistics or a row-cost buffer bound, pointLightSize outside
+// 1 .. 4, a deep tree, shade_fold = 0 or max_tracing_depth = 0 (no folded shade runs). A draw that runs the primary
+// stage, or a bypassed one, is off and leaves the plane stale (point_cache_note); the first draw that reuses the stage with the plane stale, or under another key, resets it;
+// a later draw under the reset draw's key uses it. A moving camera therefore never touches the plane.
+inline int point_cache_mode(const PointCache& c, const LightsKey& now, bool stage_reused, bool bypass) {
+  if (bypass || !stage_reused) return 0;
+  return c.valid && lights_key_diff(c.key, now) < 0 ? 2 : 1;
+}
+// after the draw's launch (ok: it succeeded)
+inline void point_cache_note(PointCache& c, const LightsKey& now, int mode, bool ok) {
+  if (mode == 0 || !ok) {
+    c.valid = false;
+  } else if (mode == 1) {
+    c.key = now;
+    c.valid = true;
+  }
+}
+
 // ---------------------------------------------------------------- the G-buffer draw ---
 // The key of a rasterize pass's draw (draw_raster): everything the draw reads, and the state of everything it writes
 // as its last completed draw left it. With the pass's int uniform reuse_static set (the caller's statement that nothing

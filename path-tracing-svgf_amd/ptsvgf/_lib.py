@@ -160,6 +160,16 @@ _PT_SIGS = [
                                            C.POINTER(C.c_int)]),
     ("pt_debug_static_key_hit", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64), C.c_int,
                                           C.c_int, C.POINTER(C.c_int)]),
+    ("pt_debug_point_cache_counts", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("pt_debug_point_cache_read", C.c_int, [_u32, C.POINTER(C.c_uint16), C.c_size_t]),
+    ("pt_debug_point_cache_write", C.c_int, [_u32, C.POINTER(C.c_uint16), C.c_size_t]),
+    ("pt_debug_point_cache_mode", C.c_int, [_u32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("pt_debug_point_cache_word", C.c_int, [C.c_int, C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
+    ("pt_debug_point_cache_key_words", C.c_int, []),
+    ("pt_debug_point_cache_key_diff", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int,
+                                                C.POINTER(C.c_int)]),
+    ("pt_debug_point_cache_key_mode", C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_int,
+                                                C.c_int, C.POINTER(C.c_int)]),
 ]
 
 _PTS_SIGS = [

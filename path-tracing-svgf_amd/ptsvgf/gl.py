@@ -291,6 +291,40 @@ def static_key_hit(kind: int, last, last_valid: bool, now, enabled: bool) -> boo
     return bool(hit.value)
 
 
+def point_cache_word(op: int, word: int, arg: int = 0) -> int:
+    """pt_debug_point_cache_word: the verdict word's bit operations (csrc/point_cache.h) on the host. op 0: look-up of
+    light `arg` (-1 not known, 0 lit, 1 occluded); 1: the pending light (-1 none); 2: mark light `arg` pending;
+    3: resolve the pending light with verdict `arg`."""
+    out = C.c_uint32()
+    check(pt().pt_debug_point_cache_word(int(op), int(word), int(arg), C.byref(out)))
+    return C.c_int32(out.value).value if op in (0, 1) else out.value
+
+
+def point_cache_key_words() -> int:
+    """pt_debug_point_cache_key_words: 64-bit words of the verdict cache's key (csrc/static_key.h LightsKey)."""
+    return check(pt().pt_debug_point_cache_key_words())
+
+
+def point_cache_key_diff(a, b) -> int:
+    """pt_debug_point_cache_key_diff: the first word in which two keys differ, -1 when they are equal."""
+    a, pa = _key_ptr(a)
+    b, pb = _key_ptr(b)
+    field = C.c_int()
+    check(pt().pt_debug_point_cache_key_diff(pa, pb, int(min(a.size, b.size)), C.byref(field)))
+    return field.value
+
+
+def point_cache_key_mode(last, last_valid: bool, now, stage_reused: bool, enabled: bool) -> int:
+    """pt_debug_point_cache_key_mode: the mode (0 off, 1 reset, 2 use) of a draw with key `now` after the draw that
+    left `last`."""
+    last, pl = _key_ptr(last)
+    now, pn = _key_ptr(now)
+    mode = C.c_int()
+    check(pt().pt_debug_point_cache_key_mode(pl, 1 if last_valid else 0, pn, int(min(last.size, now.size)),
+                                             1 if stage_reused else 0, 1 if enabled else 0, C.byref(mode)))
+    return mode.value
+
+
 class PtTileSeg(C.Structure):
     _fields_ = [("y_begin", C.c_int), ("y_end", C.c_int), ("offset", C.c_int), ("packed", C.c_void_p)]
 
@@ -494,6 +528,31 @@ class RenderPass:
         runs, reuses = C.c_uint64(), C.c_uint64()
         check(pt().pt_debug_stage_counts(self._handle(), C.byref(runs), C.byref(reuses)))
         return runs.value, reuses.value
+
+    def point_cache_counts(self):
+        """pt_debug_point_cache_counts (DESIGN.md "Static view, part 2"): (served, queued), the bounce-0 point-light
+        verdicts of this path-tracing pass's last draw that came from the cache / that were queued as rays.
+        Synchronises the device."""
+        served, queued = C.c_uint64(), C.c_uint64()
+        check(pt().pt_debug_point_cache_counts(self._handle(), C.byref(served), C.byref(queued)))
+        return served.value, queued.value
+
+    def point_cache_mode(self):
+        """pt_debug_point_cache_mode: (mode of the last draw: 0 off, 1 reset, 2 use; plane valid)."""
+        mode, valid = C.c_int(), C.c_int()
+        check(pt().pt_debug_point_cache_mode(self._handle(), C.byref(mode), C.byref(valid)))
+        return mode.value, bool(valid.value)
+
+    def point_cache_read(self, n: int):
+        """pt_debug_point_cache_read: the verdict plane, one uint16 per pixel of the rows last drawn (n of them)."""
+        a = np.empty(int(n), np.uint16)
+        check(pt().pt_debug_point_cache_read(self._handle(), a.ctypes.data_as(C.POINTER(C.c_uint16)), a.size))
+        return a
+
+    def point_cache_write(self, words) -> None:
+        """pt_debug_point_cache_write: replaces the verdict plane (tests of the cache's effect)."""
+        a = np.ascontiguousarray(words, np.uint16)
+        check(pt().pt_debug_point_cache_write(self._handle(), a.ctypes.data_as(C.POINTER(C.c_uint16)), a.size))
 
     def destroy(self) -> None:
         if self._h is not None:
