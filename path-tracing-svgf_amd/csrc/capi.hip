@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "../../include/ptsvgf_debug_pointbins.h"
+#include "../../include/ptsvgf_debug_background.h"
 #include "../../include/ptsvgf_debug_static.h"
 #include "../../include/ptsvgf_scene.h"
 #include "capi_state.h"
@@ -699,6 +700,10 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
   Texture* hc = sampler(p, "hdrCache", &hch);
   if (!hm || !hc || !hm->dev || !hc->dev) return err(PT_ERR_MISSING_TEXTURE, "path_tracing needs hdrMap and hdrCache");
   k.hdr = Tex{(const float4*)hm->dev, hm->W, hm->H};
+  reads.hdr_handle = hmh;
+  reads.hdr_ver = hm->version;
+  reads.cache_handle = hch;
+  reads.cache_ver = hc->version;
   k.cache = Tex{(const float4*)hc->dev, hc->W, hc->H};
   k.hdr_pdf = Tex{nullptr, 0, 0};
   // A/B switch hdr_merge (default 1): the NEE's radiance and pdf fetches at one direction from one merged texture
@@ -904,6 +909,39 @@ ptk::LightsKey point_cache_mode_for(Pass* p, PTParams& k, const ptk::PrimaryKey&
   return q;
 }
 
+// The static background (DESIGN.md "Static view, part 3"), after a one-sample wavefront draw of the whole frame without
+// accumulation: the colour attachment's miss texels are the content of the draw's MissKey (static_key.h), whichever
+// slot's plane this is; the texture also remembers the draw's primary content and whose hit0 holds its primary hits,
+// for the quiet-tile flags. Any other path-tracing draw leaves the stamp att_plane made: fresh.
+void bg_note_colour(Pass* p, const PTParams& k, const ptk::PrimaryKey& key, const DrawReads& reads) {
+  using namespace ptk;
+  Texture* ct = tex_of(p->att[0]);
+  if (!ct || k.accumulate || k.y0 != 0 || k.y1 != k.H || k.tile_stride != 1 || band_partition(k.W, k.H) ||
+      ct->row0 != 0 || ct->rows != k.H || !k.wf.hit0)
+    return;
+  const PrimaryKey pc = primary_content(key);
+  MissKey m{};
+  memcpy(m.w + kMkPrimary0, pc.w, sizeof(pc.w));
+  m.w[kMkHdrHandle] = reads.hdr_handle;
+  m.w[kMkHdrDev] = key_bits((const void*)k.hdr.p);
+  m.w[kMkHdrVer] = reads.hdr_ver;
+  m.w[kMkHdrW] = key_bits(k.hdr.W);
+  m.w[kMkHdrH] = key_bits(k.hdr.H);
+  m.w[kMkCacheHandle] = reads.cache_handle;
+  m.w[kMkCacheDev] = key_bits((const void*)k.cache.p);
+  m.w[kMkCacheVer] = reads.cache_ver;
+  m.w[kMkMerged] = k.hdr_pdf.p != nullptr;
+  m.w[kMkClamp] = key_bits(k.clamp_threshold);
+  m.w[kMkAccumulate] = key_bits(k.accumulate);
+  m.w[kMkMaxDepth] = key_bits(k.max_depth);
+  m.w[kMkShadeFold] = k.shade_fold;
+  m.w[kMkSpp] = 1;
+  ct->bg = BgStamp{g.bg_miss.of(m.w, kMkWords, &g.bg_serial), kBgWhole};
+  ct->bg_prim = g.bg_prim.of(pc.w, kPkWords, &g.bg_serial);
+  ct->bg_pass = p;
+  ct->bg_pass_gen = p->wf.gen;
+}
+
 // The side stream and events of path-tracing draws issued on `s` (uniform trace_fork = 1), created on first use: one
 // per draw stream, so frames in flight on different streams do not queue behind each other's shadow walks. An entry
 // lives until its stream is released (pt_stream_release, which the host's stream pool calls when a renderer gives a
@@ -1033,6 +1071,7 @@ int draw_pathtrace(Pass* p) {
     ptk::point_cache_note(p->lcache, lkey, k.point_cache, rc == 0);
     p->lcache_last_mode = k.point_cache;
     if (!rc && k.tiles.cost) p->order.ordered = true;
+    if (!rc) bg_note_colour(p, k, key, reads);
   }
   if (rc) return hip_err((hipError_t)rc, "pathtrace launch");
   return note_reads(reads);
@@ -1303,13 +1342,147 @@ int draw_raster(Pass* p) {
   for (int i = 0; i < 4; ++i) tex_of(p->att[i])->raster_stamp = serial;
   p->gcache.valid = gbuf_key(p, src, &p->gcache.key);
   p->gcache.runs++;
+  // the static background (DESIGN.md "Static view, part 3"): which pixels of this set are background is a function of
+  // the key's content, whichever set's planes these are (an elided draw leaves the id as it leaves the planes)
+  if (p->gcache.valid && k.y0 == 0 && k.y1 == k.H && !band_partition(k.W, k.H) && fwt->row0 == 0 && fwt->rows == k.H) {
+    const ptk::GbufKey c = ptk::gbuf_content(p->gcache.key, ptk::key_bits((const void*)src));
+    fwt->bg_gbuf = g.bg_gbuf.of(c.w, ptk::kGkWords, &g.bg_serial);
+  }
   return PT_OK;
+}
+
+// ---- the static background of the SVGF chain (DESIGN.md "Static view, part 3"; static_key.h has the rules)
+// static_background (int uniform of a reproject, variance or a-trous pass, default 0): the caller states that nothing
+// outside the library writes the pass's textures. PTSVGF_STATIC_BACKGROUND=0 in the environment forces it off (A/B).
+bool bg_env_off() {
+  static const bool off = [] {
+    const char* e = getenv("PTSVGF_STATIC_BACKGROUND");
+    return e && atoi(e) == 0;
+  }();
+  return off;
+}
+bool bg_whole(const Texture* t, int H) { return t && t->row0 == 0 && t->rows == H; }
+QuietSet* bg_set_of(uint64_t id) {
+  if (id)
+    for (QuietSet& q : g.bg_sets)
+      if (q.id == id) return &q;
+  return nullptr;
+}
+// What bypasses every SVGF draw alike: the switch, the environment, a row subset or band.
+int bg_bypass(Pass* p, int y0, int y1) {
+  if (ui(p, "static_background", 0) == 0) return PT_BG_R_UNIFORM;
+  if (bg_env_off()) return PT_BG_R_ENV;
+  if (y0 != 0 || y1 != p->H || band_partition(p->W, p->H)) return PT_BG_R_ROWS;
+  return PT_BG_R_NONE;
+}
+// Builds set `id` for the colour plane ct and the depth-fwidth attachment ft of a W x H frame, on the draw's stream:
+// from ft's compact plane and the primary plane of the pass that wrote ct, if it still holds that draw's hits.
+int bg_build_set(uint64_t id, const Texture* ct, const Texture* ft, int W, int H, bool* built) {
+  *built = false;
+  Pass* pp = nullptr;
+  for (auto& kv : g.passes)
+    if (kv.second.get() == ct->bg_pass) pp = kv.second.get();
+  if (!pp || pp->wf.gen != ct->bg_pass_gen || !pp->pcache.valid || !pp->wf.st.hit0 || !ft->aux || !ft->aux_valid)
+    return PT_OK;
+  const ptk::PrimaryKey pc = ptk::primary_content(pp->pcache.key);
+  if (g.bg_prim.of(pc.w, ptk::kPkWords, &g.bg_serial) != ct->bg_prim) return PT_OK;
+  QuietSet& q = g.bg_sets[g.bg_next];
+  g.bg_next = (g.bg_next + 1) % kQuietSets;
+  // the oldest set's allocation is taken again: draws issued on this stream have read it by the time the build runs;
+  // draws on other streams are waited for (a set goes out of use kQuietSets views later, so this is rare)
+  if (q.flags && (q.mixed || q.last_stream != g.stream)) HIPCHK(hipDeviceSynchronize());
+  q.id = 0;
+  const size_t off16 = ptk::atrous_flag_bytes(W, 0, H), n16 = (size_t)((W + 15) / 16) * ((H + 15) / 16);
+  const size_t offc = (off16 + n16 + 3) / 4 * 4, need = offc + 6 * sizeof(uint32_t);
+  if (q.cap < need) {
+    if (q.flags) (void)hipFree(q.flags);
+    q.flags = nullptr;
+    q.cap = 0;
+    HIPCHK(hipMalloc((void**)&q.flags, need));
+    q.cap = need;
+  }
+  const int rc = ptk::launch_quiet_flags(ft->aux, ft->row0, pp->wf.st.hit0, W, H, q.flags, q.flags + off16,
+                                         (uint32_t*)(q.flags + offc), g.stream);
+  if (rc) return hip_err((hipError_t)rc, "quiet-tile flags");
+  q.id = id;
+  q.gbuf = ft->bg_gbuf;
+  q.W = W;
+  q.H = H;
+  q.off16 = off16;
+  q.off_counts = offc;
+  q.last_stream = g.stream;
+  q.mixed = false;
+  *built = true;
+  return PT_OK;
+}
+// One SVGF draw's decision. Before the draw's att_plane calls: begin() reads the stamps as the draw finds them; after
+// the launch: finish() stamps the outputs and records the mode.
+struct BgDraw {
+  int reason = PT_BG_R_NONE;
+  uint64_t set = 0;
+  QuietSet* qs = nullptr;
+  bool skip = false;
+  int npairs = 0;
+  Texture* out[2] = {nullptr, nullptr};
+  ptk::BgStamp in[2], was[2];
+  bool mod[2] = {false, false};
+  int in_off = 0;  // an input was written by a bypassed draw of the chain: its reason
+  void pair(const Texture* i, Texture* o, bool modulated) {
+    if (i && i->bg_off && !in_off) in_off = i->bg_off;
+    in[npairs] = i ? i->bg : ptk::BgStamp{};
+    was[npairs] = o ? o->bg : ptk::BgStamp{};
+    out[npairs] = o;
+    mod[npairs++] = modulated;
+  }
+  // the set is known (0: none): may the draw skip its tiles?
+  void decide() {
+    qs = bg_set_of(set);
+    if (!qs) set = 0;
+    if (!reason && in_off) reason = in_off;  // the chain was bypassed above this draw
+    if (reason) return;
+    if (!set) {
+      reason = PT_BG_R_NO_SET;
+      return;
+    }
+    skip = true;
+    for (int i = 0; i < npairs; ++i) skip = skip && ptk::bg_pair_quiet(in[i], was[i], set, mod[i]);
+    if (!skip) reason = PT_BG_R_STAMPS;
+  }
+  void finish(Pass* p, int shape, bool ok) {
+    const bool off = reason >= PT_BG_R_UNIFORM && reason <= PT_BG_R_NO_PLANE;
+    for (int i = 0; i < npairs; ++i)
+      if (out[i]) {
+        out[i]->bg = ptk::bg_copy(in[i], ok && !off ? set : 0, mod[i], &g.bg_serial);
+        out[i]->bg_off = off ? reason : 0;
+      }
+    if (qs && skip) {
+      qs->mixed = qs->mixed || qs->last_stream != g.stream;
+      qs->last_stream = g.stream;
+    }
+    p->bg_mode = off ? PT_BG_OFF : skip ? PT_BG_SKIP : PT_BG_ARMED;
+    p->bg_reason = reason;
+    p->bg_set = off ? 0 : set;
+    p->bg_shape = shape;
+  }
+};
+// The set of a variance or a-trous draw: the one its input's stamp holds for, provided it was built for the G-buffer
+// content of this draw's depth-fwidth attachment and the frame's size.
+uint64_t bg_set_from_input(const Texture* in, const Texture* ft, int W, int H) {
+  const QuietSet* q = in && in->bg.id ? bg_set_of(in->bg.scope) : nullptr;
+  return q && ft->bg_gbuf && q->gbuf == ft->bg_gbuf && q->W == W && q->H == H ? q->id : 0;
+}
+// gNormalAndLinearZ and gNormalDepthFwidth are attachments of one G-buffer draw, and the compact plane is there: the
+// kernels' background tests (nd.w == 1, the compact plane's sign) then agree with the flags' content
+bool bg_one_gbuffer(const Texture* nd, const Texture* ft) {
+  return nd && ft && ft->aux && ft->aux_valid && ft->raster_stamp != 0 && nd->raster_stamp == ft->raster_stamp;
 }
 
 int draw_svgf(Pass* p, int kind) {
   int y0, y1;
   rows_of(p, &y0, &y1);
   int rc = 0;
+  BgDraw bg;
+  if (kind == PK_REPROJECT || kind == PK_VARIANCE || kind == PK_ATROUS) bg.reason = bg_bypass(p, y0, y1);
   if (kind == PK_REPROJECT) {
     ReprojParams k;
     memset(&k, 0, sizeof(k));
@@ -1323,6 +1496,10 @@ int draw_svgf(Pass* p, int kind) {
     TRY(plane_of(sampler(p, "gNormalAndLinearZ"), p, &k.nd, "gNormalAndLinearZ"));
     TRY(plane_of(sampler(p, "gPrevNormalAndLinearZ"), p, &k.prev_nd, "gPrevNormalAndLinearZ"));
     TRY(plane_of(sampler(p, "gNormalDepthFwidth"), p, &k.fwidth, "gNormalDepthFwidth"));
+    if (p->att.size() >= 2) {  // (the stamps as the draw finds them: att_plane makes the outputs' fresh)
+      bg.pair(sampler(p, "gColor"), tex_of(p->att[0]), false);
+      bg.pair(sampler(p, "gPrevMoments_HistoryLength"), tex_of(p->att[1]), false);
+    }
     TRY(att_plane(p, 0, &k.out_illum));
     TRY(att_plane(p, 1, &k.out_moments));
     k.inv_w = uf(p, "inv_screen_width", 0.0f);
@@ -1332,7 +1509,35 @@ int draw_svgf(Pass* p, int kind) {
     k.block = ui(p, "reproj_block", 1);  // A/B (0: lin per tap): the same texels either way
     // optional: the moments plane of the draw that wrote gColor (pt_pass_set_sample_moments)
     if (Texture* sm = bound_sampler(p, "gSampleMoments")) TRY(plane_of(sm, p, &k.sm, "gSampleMoments"));
+    // static background: the set of this draw's (primary content, G-buffer content) pair, built by the second draw
+    // that meets the pair; every other case forgets the pair, so no set outlives a bypass
+    {
+      const Texture *ct = sampler(p, "gColor"), *ft = sampler(p, "gNormalDepthFwidth");
+      if (!bg.reason && k.sm.p) bg.reason = PT_BG_R_SAMPLE_MOMENTS;
+      if (!bg.reason && !(bg_whole(ct, p->H) && bg_whole(ft, p->H) && bg_whole(bg.out[0], p->H) &&
+                          bg_whole(bg.out[1], p->H) && bg_whole(sampler(p, "gPrevMoments_HistoryLength"), p->H)))
+        bg.reason = PT_BG_R_ROWS;
+      if (!bg.reason && !bg_one_gbuffer(sampler(p, "gNormalAndLinearZ"), ft)) bg.reason = PT_BG_R_NO_PLANE;
+      if (!bg.reason && !(ct->bg_prim && ft->bg_gbuf)) bg.reason = PT_BG_R_NO_CONTENT;
+      bool build = false;
+      // (a pass with the switch off takes no part: it leaves the choice to the passes that have it on)
+      if (bg.reason != PT_BG_R_UNIFORM && bg.reason != PT_BG_R_ENV)
+        bg.set = ptk::quiet_set_for(g.bg_choice, bg.reason ? 0 : ct->bg_prim, bg.reason ? 0 : ft->bg_gbuf,
+                                    &g.bg_serial, &build);
+      if (build) {
+        bool built = false;
+        TRY(bg_build_set(bg.set, ct, ft, k.W, k.H, &built));
+        if (!built) {  // (no primary plane to read: PT_BG_R_NO_PLANE, and the next draw tries again)
+          g.bg_choice.set = bg.set = 0;
+          bg.reason = PT_BG_R_NO_PLANE;
+        }
+      }
+      bg.in_off = 0;  // (the head of the chain: what bypassed the last frame's draws does not bind this one)
+      bg.decide();
+      if (bg.skip) k.busy16 = bg.qs->flags + bg.qs->off16;
+    }
     rc = launch_reproject(k, g.stream);
+    bg.finish(p, 5, rc == 0);
   } else if (kind == PK_VARIANCE) {
     VarianceParams k;
     memset(&k, 0, sizeof(k));
@@ -1341,11 +1546,23 @@ int draw_svgf(Pass* p, int kind) {
     TRY(plane_of(sampler(p, "gMoments_HistoryLength"), p, &k.moments, "gMoments_HistoryLength"));
     TRY(plane_of(sampler(p, "gNormalAndLinearZ"), p, &k.nd, "gNormalAndLinearZ"));
     TRY(plane_of(sampler(p, "gNormalDepthFwidth"), p, &k.fwidth, "gNormalDepthFwidth"));
+    if (!p->att.empty()) bg.pair(sampler(p, "gIllumination"), tex_of(p->att[0]), false);
     TRY(att_plane(p, 0, &k.out));
     k.phi_color = uf(p, "gPhiColor", 0.0f);
     k.phi_normal = uf(p, "gPhiNormal", 0.0f);
     if (Texture* sm = bound_sampler(p, "gSampleMoments")) TRY(plane_of(sm, p, &k.sm, "gSampleMoments"));
+    {
+      const Texture *it = sampler(p, "gIllumination"), *ft = sampler(p, "gNormalDepthFwidth");
+      if (!bg.reason && k.sm.p) bg.reason = PT_BG_R_SAMPLE_MOMENTS;
+      if (!bg.reason && !(bg_whole(it, p->H) && bg_whole(ft, p->H) && bg_whole(bg.out[0], p->H)))
+        bg.reason = PT_BG_R_ROWS;
+      if (!bg.reason && !bg_one_gbuffer(sampler(p, "gNormalAndLinearZ"), ft)) bg.reason = PT_BG_R_NO_PLANE;
+      if (!bg.reason) bg.set = bg_set_from_input(it, ft, k.W, k.H);
+      bg.decide();
+      if (bg.skip) k.busy16 = bg.qs->flags + bg.qs->off16;
+    }
     rc = launch_variance(k, g.stream);
+    bg.finish(p, 5, rc == 0);
   } else if (kind == PK_ATROUS) {
     AtrousParams k;
     memset(&k, 0, sizeof(k));
@@ -1353,6 +1570,8 @@ int draw_svgf(Pass* p, int kind) {
     TRY(plane_of(sampler(p, "gIllumination"), p, &k.illum, "gIllumination"));
     TRY(plane_of(sampler(p, "gNormalAndLinearZ"), p, &k.nd, "gNormalAndLinearZ"));
     TRY(plane_of(sampler(p, "gNormalDepthFwidth"), p, &k.fwidth, "gNormalDepthFwidth"));
+    if (!p->att.empty()) bg.pair(sampler(p, "gIllumination"), tex_of(p->att[0]), false);
+    if (ui(p, "fuse_modulate", 0) && p->att.size() >= 2) bg.pair(sampler(p, "gIllumination"), tex_of(p->att[1]), true);
     TRY(att_plane(p, 0, &k.out));
     if (k.out.p == k.illum.p) return err(PT_ERR_ARG, "a-trous output aliases its input (GL feedback loop)");
     k.step = ui(p, "gStepSize", 1);
@@ -1394,12 +1613,29 @@ int draw_svgf(Pass* p, int kind) {
           return err(PT_ERR_ARG, "fused modulate: a plane does not store the draw's rows");
       if (k.mod.p == k.illum.p || k.mod.p == k.out.p) return err(PT_ERR_ARG, "fused modulate target aliases the a-trous planes");
     }
+    {
+      // static background: only the tiled kernel with this draw's own tile flags skips (k.tile_any set: the
+      // production variant, a step of 1 .. 16, the compact plane), and only over whole-frame planes, which is also what
+      // makes launch_atrous_fast choose it (same_geometry)
+      const Texture *it = sampler(p, "gIllumination"), *ft = sampler(p, "gNormalDepthFwidth");
+      if (!bg.reason && !(bg_whole(it, p->H) && bg_whole(ft, p->H) && bg_whole(bg.out[0], p->H) &&
+                          (bg.npairs < 2 || bg_whole(bg.out[1], p->H)) &&
+                          bg_whole(sampler(p, "gNormalAndLinearZ"), p->H)))
+        bg.reason = PT_BG_R_ROWS;
+      if (!bg.reason && !k.fwidth.aux) bg.reason = PT_BG_R_NO_PLANE;
+      if (!bg.reason && !k.tile_any) bg.reason = PT_BG_R_KERNEL;
+      if (!bg.reason && !bg_one_gbuffer(sampler(p, "gNormalAndLinearZ"), ft)) bg.reason = PT_BG_R_NO_PLANE;
+      if (!bg.reason) bg.set = bg_set_from_input(it, ft, k.W, k.H);
+      bg.decide();
+      if (bg.skip) k.busy = bg.qs->flags + ptk::atrous_flag_offset(si, k.W, 0, k.H);
+    }
     if (ui(p, "exact", 0)) rc = launch_atrous_exact(k, g.stream);          // bit-exact form (tests)
     else if (ui(p, "atrous_variant", 0) == 1) rc = launch_atrous_simple(k, g.stream);  // A/B: generic
     else if (ui(p, "atrous_variant", 0) == 2) rc = launch_atrous_step(k, g.stream);    // A/B: step kernel
     else rc = launch_atrous_fast(k, g.stream);                             // LDS-tiled (production)
     if (rc == PT_OK && k.mod.p && (ui(p, "exact", 0) || ui(p, "atrous_variant", 0) != 0))
       rc = launch_modulate_after(k, g.stream);
+    bg.finish(p, si < 0 ? 0 : si, rc == 0);
   } else if (kind == PK_MODULATE) {
     ModulateParams k;
     memset(&k, 0, sizeof(k));
@@ -1507,6 +1743,8 @@ int pt_shutdown(void) {
   for (auto& kv : g.scenes) free_scene(kv.second);
   for (auto& kv : g.hdr_merged) free_hdr_merged(kv.second);
   g.hdr_merged.clear();
+  for (QuietSet& q : g.bg_sets)
+    if (q.flags) (void)hipFree(q.flags);
   for (auto& kv : g.forks) {
     (void)hipEventDestroy(kv.second.fork);
     (void)hipEventDestroy(kv.second.join);
@@ -1871,6 +2109,129 @@ int pt_debug_static_key_hit(int kind, const uint64_t* last, int last_valid, cons
   return PT_OK;
 }
 
+// ---- the static background of the SVGF chain (DESIGN.md "Static view, part 3")
+int pt_debug_bg_counts(uint32_t pass, int* mode, int* reason, uint64_t* skipped, uint64_t* total) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (mode) *mode = p->bg_mode;
+  if (reason) *reason = p->bg_reason;
+  if (skipped) *skipped = 0;
+  if (total) *total = 0;
+  if (p->bg_mode == PT_BG_OFF) return PT_OK;
+  const int S = 1 << p->bg_shape, nx = ptk::atrous_tile_nx(S), tj = ptk::atrous_tile_tj(S);
+  const uint64_t n = p->bg_shape == 5 ? (uint64_t)((p->W + 15) / 16) * ((p->H + 15) / 16)
+                                      : (uint64_t)((p->W + 64 * nx - 1) / (64 * nx)) * ((p->H + S * tj - 1) / (S * tj)) * S;
+  if (total) *total = n;
+  const QuietSet* q = bg_set_of(p->bg_set);
+  if (p->bg_mode != PT_BG_SKIP || !q || !skipped) return PT_OK;
+  uint32_t busy[6];
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(busy, q->flags + q->off_counts, sizeof(busy), hipMemcpyDeviceToHost));
+  *skipped = n - busy[p->bg_shape];
+  return PT_OK;
+}
+
+int pt_debug_bg_stamp(uint32_t tex, uint64_t* id, uint64_t* scope) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  const Texture* t = tex_of(tex);
+  if (!t) return err(PT_ERR_INVALID_HANDLE, "invalid texture");
+  if (id) *id = t->bg.id;
+  if (scope) *scope = t->bg.scope;
+  return PT_OK;
+}
+
+int pt_debug_bg_poke_hit0(uint32_t pass, int x, int y, int tri, float t) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (g.programs[p->program] != PK_PATHTRACE || !p->wf.st.hit0)
+    return err(PT_ERR_STATE, "pt_debug_bg_poke_hit0: a path-tracing pass that has drawn with the wavefront path tracer");
+  if (x < 0 || x >= p->W || y < 0 || (size_t)y * p->W + x >= p->wf.n)
+    return err(PT_ERR_ARG, "pt_debug_bg_poke_hit0: pixel outside the rows the pass drew");
+  int2 v;
+  v.x = tri;
+  memcpy(&v.y, &t, sizeof(t));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(p->wf.st.hit0 + (size_t)y * p->W + x, &v, sizeof(v), hipMemcpyHostToDevice));
+  return PT_OK;
+}
+
+int pt_debug_bg_fresh(uint64_t* serial, uint64_t* id, uint64_t* scope) {
+  if (!serial || !id || !scope) return err(PT_ERR_ARG, "pt_debug_bg_fresh: null argument");
+  const ptk::BgStamp s = ptk::bg_fresh(serial);
+  *id = s.id;
+  *scope = s.scope;
+  return PT_OK;
+}
+
+int pt_debug_bg_copy(uint64_t in_id, uint64_t in_scope, uint64_t set, int modulated, uint64_t* serial, uint64_t* id,
+                     uint64_t* scope) {
+  if (!serial || !id || !scope) return err(PT_ERR_ARG, "pt_debug_bg_copy: null argument");
+  const ptk::BgStamp s = ptk::bg_copy(ptk::BgStamp{in_id, in_scope}, set, modulated != 0, serial);
+  *id = s.id;
+  *scope = s.scope;
+  return PT_OK;
+}
+
+int pt_debug_bg_pair_quiet(uint64_t in_id, uint64_t in_scope, uint64_t out_id, uint64_t out_scope, uint64_t set,
+                           int modulated, int* quiet) {
+  if (!quiet) return err(PT_ERR_ARG, "pt_debug_bg_pair_quiet: null argument");
+  *quiet = ptk::bg_pair_quiet(ptk::BgStamp{in_id, in_scope}, ptk::BgStamp{out_id, out_scope}, set, modulated != 0) ? 1 : 0;
+  return PT_OK;
+}
+
+int pt_debug_bg_quiet_set(uint64_t* state, uint64_t prim, uint64_t gbuf, uint64_t* serial, uint64_t* set, int* build) {
+  if (!state || !serial || !set || !build) return err(PT_ERR_ARG, "pt_debug_bg_quiet_set: null argument");
+  ptk::QuietChoice c;
+  c.prim = state[0];
+  c.gbuf = state[1];
+  c.set = state[2];
+  bool b = false;
+  *set = ptk::quiet_set_for(c, prim, gbuf, serial, &b);
+  *build = b ? 1 : 0;
+  state[0] = c.prim;
+  state[1] = c.gbuf;
+  state[2] = c.set;
+  return PT_OK;
+}
+
+int pt_debug_bg_miss_key_words(void) { return (int)ptk::kMkWords; }
+
+int pt_debug_bg_miss_key_diff(const uint64_t* a, const uint64_t* b, int words, int* field) {
+  if (!a || !b || !field) return err(PT_ERR_ARG, "pt_debug_bg_miss_key_diff: null argument");
+  if (words != (int)ptk::kMkWords) return err(PT_ERR_ARG, "pt_debug_bg_miss_key_diff: not the key's word count");
+  ptk::MissKey ka, kb;
+  memcpy(ka.w, a, sizeof(ka.w));
+  memcpy(kb.w, b, sizeof(kb.w));
+  *field = ptk::miss_key_diff(ka, kb);
+  return PT_OK;
+}
+
+int pt_debug_bg_miss_key_id(const uint64_t* key, int words, uint64_t* id) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  if (!key || !id) return err(PT_ERR_ARG, "pt_debug_bg_miss_key_id: null argument");
+  if (words != (int)ptk::kMkWords) return err(PT_ERR_ARG, "pt_debug_bg_miss_key_id: not the key's word count");
+  *id = g.bg_miss.of(key, words, &g.bg_serial);
+  return PT_OK;
+}
+
+int pt_debug_bg_key_content(int kind, const uint64_t* key, int words, uint64_t source, uint64_t* out) {
+  TRY(static_key_args("pt_debug_bg_key_content", kind, key, key, words, out));
+  if (kind == 0) {
+    ptk::PrimaryKey k;
+    memcpy(k.w, key, sizeof(k.w));
+    k = ptk::primary_content(k);
+    memcpy(out, k.w, sizeof(k.w));
+  } else {
+    ptk::GbufKey k;
+    memcpy(k.w, key, sizeof(k.w));
+    k = ptk::gbuf_content(k, source);
+    memcpy(out, k.w, sizeof(k.w));
+  }
+  return PT_OK;
+}
+
 // ---- the bounce-0 point-light verdict cache (DESIGN.md "Static view, part 2")
 static int point_cache_pass(const char* who, uint32_t pass, Pass** out) {
   Pass* p = pass_of(pass);
@@ -2196,6 +2557,10 @@ int pt_tiles_copy(const uint32_t* tex, int ntex, int tile_y0, int stride, const 
     for (int j = 0; j < ntex; ++j) {  // new texels, as after a draw
       ts[j]->version++;
       ts[j]->raster_stamp = 0;
+      ts[j]->bg = ptk::bg_fresh(&g.bg_serial);
+      ts[j]->bg_prim = ts[j]->bg_gbuf = 0;
+      ts[j]->bg_pass = nullptr;
+      ts[j]->bg_off = 0;
     }
   return PT_OK;
 }

@@ -4,7 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -34,6 +36,17 @@ struct Texture {
   // the serial of the draw_raster that wrote this attachment last (Lib::raster_serial); 0 once anything else in the
   // library wrote the texture (tex_written): part of the G-buffer draw's key (static_key.h)
   uint64_t raster_stamp = 0;
+  // the background stamp (static_key.h, DESIGN.md "Static view, part 3"): what this texture holds on background
+  // tiles. With it, on a colour plane a one-sample wavefront draw wrote: the draw's primary content id and the pass
+  // whose hit0 holds its primary hits (with the allocation's generation); on a depth-fwidth attachment draw_raster
+  // wrote: the draw's G-buffer content id. tex_written clears the three and makes the stamp fresh.
+  ptk::BgStamp bg;
+  // the reason (ptsvgf_debug_background.h) of the bypassed SVGF draw that wrote this texture last, 0: none. The draws
+  // further down the chain that read it are bypassed for the same reason, and say so.
+  int bg_off = 0;
+  uint64_t bg_prim = 0, bg_gbuf = 0;
+  const void* bg_pass = nullptr;
+  uint64_t bg_pass_gen = 0;
   // compact one-float side plane of the stored rows: a depth-fwidth attachment's fwidth.y with the background flag, a
   // world-position attachment's primary-ray bound for rays from aux_eye (draw_raster)
   float* aux = nullptr;
@@ -136,6 +149,10 @@ struct Pass {
   float2* sample_stats = nullptr;    // pt_pass_set_sample_stats (not owned)
   float4* sample_moments = nullptr;  // pt_pass_set_sample_moments (not owned)
   uint32_t* motion_max = nullptr;  // pt_pass_set_motion_bound (not owned)
+  // an SVGF pass's last draw (ptsvgf_debug_background.h): BgMode, BgReason, the quiet-tile set it worked with and the
+  // tile shape it skips by (0 .. 4: the a-trous steps, 5: 16 x 16 blocks)
+  int bg_mode = 0, bg_reason = 0, bg_shape = 0;
+  uint64_t bg_set = 0;
   unsigned long long* stats = nullptr;  // pt_pass_set_trace_stats (not owned)
   int stats_n = 0;                      // counters that buffer holds (pt_pass_set_trace_stats_n)
 };
@@ -234,6 +251,9 @@ struct DrawReads {
   // the pointLights texture the draw bound (0: none): part of the verdict cache's key (static_key.h)
   uint32_t light_handle = 0;
   uint64_t light_ver = 0;
+  // the hdrMap and hdrCache textures the draw bound: part of the miss-colour key (static_key.h)
+  uint32_t hdr_handle = 0, cache_handle = 0;
+  uint64_t hdr_ver = 0, cache_ver = 0;
 };
 
 // The point-light triangle bins of a scene (ptk::PointBinsDev, kernels_pointbins.hip) for the lights texture a
@@ -306,6 +326,35 @@ struct Pose {
   float *sk_tri_weights = nullptr, *sk_r_weights = nullptr;
 };
 
+// A quiet-tile set (static_key.h): per tile of the five a-trous tile shapes (atrous_flag_offset's layout over the whole
+// frame) and per 16 x 16 block, one byte that is 0 iff every pixel of the tile is background in the G-buffer and a miss
+// in the primary plane; then six counts of the non-zero bytes per shape. Read-only once built.
+struct QuietSet {
+  uint64_t id = 0, gbuf = 0;  // the set's id and the G-buffer content it was built for
+  int W = 0, H = 0;
+  unsigned char* flags = nullptr;
+  size_t cap = 0, off16 = 0, off_counts = 0;
+  hipStream_t last_stream = nullptr;  // the stream of the draws that read it, mixed: more than one
+  bool mixed = false;
+};
+constexpr int kQuietSets = 4;
+
+// Content ids by key (static_key.h): equal keys, one id. A small table, oldest out: a key that comes back after it
+// left gets a new id, which only costs the skips of a frame.
+struct ContentIds {
+  std::vector<std::pair<std::vector<uint64_t>, uint64_t>> known;
+  uint64_t of(const uint64_t* w, int n, uint64_t* serial) {
+    for (size_t i = 0; i < known.size(); ++i)
+      if ((int)known[i].first.size() == n && memcmp(known[i].first.data(), w, n * sizeof(uint64_t)) == 0) {
+        if (i + 1 != known.size()) std::rotate(known.begin() + i, known.begin() + i + 1, known.end());
+        return known.back().second;
+      }
+    if (known.size() >= 8) known.erase(known.begin());
+    known.emplace_back(std::vector<uint64_t>(w, w + n), ++*serial);
+    return known.back().second;
+  }
+};
+
 struct Lib {
   bool init = false;
   int device = 0;
@@ -323,6 +372,13 @@ struct Lib {
   bool profiling = false;
   uint64_t raster_serial = 0;  // draw_raster calls that launched (Texture::raster_stamp)
   uint64_t raster_ver = 0;     // RasterScene::version values handed out
+  // the static background (DESIGN.md "Static view, part 3"): the counter of content and quiet-set ids, the ids of the
+  // keys, the reproject draws' choice of a set, and the sets (the newest kQuietSets)
+  uint64_t bg_serial = 0;
+  ContentIds bg_miss, bg_prim, bg_gbuf;
+  ptk::QuietChoice bg_choice;
+  QuietSet bg_sets[kQuietSets];
+  int bg_next = 0;
 };
 
 // defined in capi.hip
@@ -353,6 +409,10 @@ inline void tex_written(Texture* t) {
   t->version++;
   t->aux_valid = false;
   t->raster_stamp = 0;
+  t->bg = ptk::bg_fresh(&g.bg_serial);
+  t->bg_prim = t->bg_gbuf = 0;
+  t->bg_pass = nullptr;
+  t->bg_off = 0;
 }
 int ensure_init();
 int refresh_host(Texture* t);

@@ -382,6 +382,8 @@ __global__ void __launch_bounds__(64 * tile_tj<S>() * tile_nx<S>()) atrous_tile_
   const bool pre = AUX && p.tile_any != nullptr;
   bool tile_any = true;
   if (pre) tile_any = p.tile_any[(g * S + b) * gridDim.x + bx] != 0;
+  // static background: a background tile whose copy is proven to change nothing (AtrousParams::busy)
+  if (pre && !tile_any && p.busy && p.busy[(g * S + b) * gridDim.x + bx] == 0) return;
   if (!pre && own) {  // (with the flags the pixel's own flag is read beside the staging loads, below)
     if (AUX) {
       const float a = p.fwidth.aux[ci];
@@ -506,6 +508,51 @@ int atrous_tile_flags(const Plane& fw, int W, int y0, int y1, unsigned char* fla
   hipLaunchKernelGGL(atrous_flags_kernel, dim3((W + 63) / 64, y1 - y0), dim3(64), 0, s, fw.aux, fw.row0, W, y0, flags,
                      (int)atrous_flag_offset(1, W, y0, y1), (int)atrous_flag_offset(2, W, y0, y1),
                      (int)atrous_flag_offset(3, W, y0, y1), (int)atrous_flag_offset(4, W, y0, y1));
+  return (int)hipGetLastError();
+}
+
+// The quiet-tile flags (launch_quiet_flags, pt_device.h). One wave per 64 columns of a row, as atrous_flags_kernel: a
+// ballot of the pixels that are surface or primary hits, then lane 0 marks the row's a-trous tiles and the first lane
+// of each 16-pixel run its 16 x 16 block.
+__global__ void __launch_bounds__(64) quiet_flags_kernel(const float* __restrict__ aux, int row0,
+                                                        const int2* __restrict__ hit0, int W,
+                                                        unsigned char* __restrict__ flags,
+                                                        unsigned char* __restrict__ flags16, int o1, int o2, int o3,
+                                                        int o4) {
+  const int x0 = blockIdx.x * 64, x = x0 + (int)threadIdx.x, y = (int)blockIdx.y;
+  bool busy = false;
+  if (x < W) busy = !aux_flag(aux[(size_t)(y - row0) * W + x]) || hit0[(size_t)y * W + x].x >= 0;
+  const unsigned long long m = __ballot(busy);
+  if (m == 0ull) return;
+  if (threadIdx.x == 0) {
+    const int off[5] = {0, o1, o2, o3, o4};
+    atrous_mark_tiles(flags, off, W, x0, y);
+  }
+  if ((threadIdx.x & 15) == 0 && ((m >> threadIdx.x) & 0xffffull) != 0ull)  // (a set bit is a pixel inside the frame)
+    flags16[(size_t)(y / 16) * ((W + 15) / 16) + x / 16] = 1;
+}
+// counts[k] += the non-zero bytes of shape k: bytes [off[k], off[k + 1]) of flags
+__global__ void __launch_bounds__(256) quiet_count_kernel(const unsigned char* __restrict__ flags, int n, int o1,
+                                                          int o2, int o3, int o4, int o5,
+                                                          uint32_t* __restrict__ counts) {
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= n || flags[i] == 0) return;
+  const int k = (i >= o1) + (i >= o2) + (i >= o3) + (i >= o4) + (i >= o5);
+  atomicAdd(&counts[k], 1u);
+}
+int launch_quiet_flags(const float* aux, int row0, const int2* hit0, int W, int H, unsigned char* flags,
+                       unsigned char* flags16, uint32_t* counts, hipStream_t s) {
+  if (W <= 0 || H <= 0) return 0;
+  // (the 16 x 16 flags follow the a-trous flags in one allocation, the counts follow both: capi_state.h QuietSet)
+  const size_t n = (size_t)(flags16 - flags) + (size_t)((W + 15) / 16) * ((H + 15) / 16);
+  hipError_t e = hipMemsetAsync(flags, 0, (size_t)((unsigned char*)(counts + 6) - flags), s);
+  if (e != hipSuccess) return (int)e;
+  const int o1 = (int)atrous_flag_offset(1, W, 0, H), o2 = (int)atrous_flag_offset(2, W, 0, H),
+            o3 = (int)atrous_flag_offset(3, W, 0, H), o4 = (int)atrous_flag_offset(4, W, 0, H);
+  hipLaunchKernelGGL(quiet_flags_kernel, dim3((W + 63) / 64, H), dim3(64), 0, s, aux, row0, hit0, W, flags, flags16, o1,
+                     o2, o3, o4);
+  hipLaunchKernelGGL(quiet_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, flags, (int)n, o1, o2, o3,
+                     o4, (int)(flags16 - flags), counts);
   return (int)hipGetLastError();
 }
 

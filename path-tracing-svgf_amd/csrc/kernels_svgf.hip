@@ -113,6 +113,8 @@ __device__ __forceinline__ float4 lin_tap(const float4 (&B)[3][3], const Bilin& 
 // SM: the sample-moments plane p.sm is bound (header); false is the shader as it is
 template <bool SM>
 __global__ void __launch_bounds__(256) PT_REPROJ_ATTR reproject_kernel(ReprojParams p) {
+  // a quiet block (ReprojParams::busy16): both outputs already hold what it would copy into them
+  if (p.busy16 && p.busy16[(size_t)(p.y0 / 16 + blockIdx.y) * gridDim.x + blockIdx.x] == 0) return;
   int x = blockIdx.x * 16 + (threadIdx.x & 15);
   int y = p.y0 + blockIdx.y * 16 + (threadIdx.x >> 4);
   if (x >= p.W || y >= p.y1) return;
@@ -290,6 +292,7 @@ constexpr int kVT = 16 + 2 * 3;
 template <bool SM>
 __global__ void __launch_bounds__(256) variance_kernel(VarianceParams p) {
   __shared__ float4 s_il[kVT * kVT], s_mo[kVT * kVT], s_nd[kVT * kVT];
+  if (p.busy16 && p.busy16[(size_t)(p.y0 / 16 + blockIdx.y) * gridDim.x + blockIdx.x] == 0) return;  // a quiet block
   const int bx = blockIdx.x * 16, by = p.y0 + blockIdx.y * 16;
   const int x = bx + (threadIdx.x & 15), y = by + (threadIdx.x >> 4);
   const bool valid = x < p.W && y < p.y1;

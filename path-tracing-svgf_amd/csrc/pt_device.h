@@ -356,6 +356,9 @@ struct ReprojParams {
   float inv_w, inv_h, depth_thr, normal_thr;
   int block;  // 1: the four history taps from one 3x3 texel block per plane when they tile it (same texels, same bits)
   Plane sm;   // gSampleMoments (kernels_svgf.hip header), p == null: not bound
+  // static background (DESIGN.md "Static view, part 3"): per 16 x 16 block of the frame, 0 iff the host has proven that
+  // the block's stores would change nothing; such a block exits before its first load. Null: every block runs.
+  const unsigned char* busy16;
 };
 
 struct VarianceParams {
@@ -363,6 +366,7 @@ struct VarianceParams {
   Plane illum, moments, nd, fwidth, out;
   float phi_color, phi_normal;
   Plane sm;  // gSampleMoments (kernels_svgf.hip header), p == null: not bound
+  const unsigned char* busy16;  // as ReprojParams::busy16
 };
 
 struct AtrousParams {
@@ -371,6 +375,10 @@ struct AtrousParams {
   int step;
   float phi_color, phi_normal;
   const unsigned char* tile_any;  // tiled kernel: per-tile "holds a surface pixel" flags of this step, or null
+  // tiled kernel, static background (DESIGN.md "Static view, part 3"): in tile_any's layout, 0 iff the host has proven
+  // that the tile's copy (and fused modulate) would store what out (and mod) already hold; such a background tile
+  // returns without the copy. Null: every tile runs.
+  const unsigned char* busy;
   // fused modulate (the last iteration of a frame, fast driver): mod.p != null writes modulate_kernel's output of
   // this draw's rows from `out`'s values, albedo and emission (every plane must store the draw's rows)
   Plane albedo, emission, mod;
@@ -404,6 +412,12 @@ __device__ __forceinline__ void atrous_mark_tiles(unsigned char* flags, const in
 size_t atrous_flag_bytes(int W, int y0, int y1);
 size_t atrous_flag_offset(int si, int W, int y0, int y1);
 int atrous_tile_flags(const Plane& fwidth, int W, int y0, int y1, unsigned char* flags, hipStream_t s);
+// The quiet-tile flags of a whole W x H frame (capi_state.h QuietSet): a byte of `flags` (the a-trous tiles of the five
+// steps, in the layout above over rows [0, H)) and of `flags16` (16 x 16 blocks, row-major, (W + 15) / 16 per row) is
+// set to 1 iff a pixel of the tile is a surface pixel by the compact depth-fwidth plane `aux` (rows from row0) or a
+// hit in the primary plane hit0 (pixel y * W + x); then counts[0 .. 5]: the bytes set per shape. All of them zeroed first.
+int launch_quiet_flags(const float* aux, int row0, const int2* hit0, int W, int H, unsigned char* flags,
+                       unsigned char* flags16, uint32_t* counts, hipStream_t s);
 
 struct ModulateParams {
   int W, H, y0, y1;

@@ -164,4 +164,105 @@ inline bool gbuf_cache_hit(const GbufCache& c, const GbufKey& now, bool enabled)
   return enabled && c.valid && planes && gbuf_key_diff(c.key, now) < 0;
 }
 
+// ------------------------------------------------ the static background of the SVGF chain ---
+// DESIGN.md "Static view, part 3". On a background pixel every SVGF pass copies a texel, so on a standing view a draw
+// stores what its destination already holds. A draw skips a tile only where that is proven, from three facts kept on
+// the host: which tiles are all background (a quiet-tile set, built on the device once per view), what the source
+// holds there (a content id), and that the destination holds the same content there (its stamp).
+
+// The content of a key, as opposed to where the draw that used it put its results: the fields that name a plane, an
+// allocation or scratch are cleared, so the K slots' draws of one view have one content.
+inline PrimaryKey primary_content(const PrimaryKey& k) {
+  PrimaryKey c = k;
+  c.w[kPkSpill] = k.w[kPkSpill] != 0;  // (which instantiation walks, not where its spill columns lie)
+  c.w[kPkPlane] = c.w[kPkPlaneGen] = c.w[kPkTileCost] = c.w[kPkTilePerm] = 0;
+  return c;
+}
+// `source`: the identity of the pass whose triangles the draw reads (its own, or the one it shares); kGkSceneVer is
+// already that pass's. The attachments, their compact planes and the tile flags are where, not what.
+inline GbufKey gbuf_content(const GbufKey& k, uint64_t source) {
+  GbufKey c = k;
+  for (int i = kGkAtt0; i < kGkFwAux; ++i) c.w[i] = 0;
+  c.w[kGkFwAux] = c.w[kGkBoundAux] = c.w[kGkBoundAuxValid] = 0;
+  c.w[kGkAuxEye0] = c.w[kGkAuxEye1] = c.w[kGkAuxEye2] = 0;
+  c.w[kGkTflags] = c.w[kGkTflagsCap] = c.w[kGkTflagsVer] = c.w[kGkTflagsY0] = c.w[kGkTflagsY1] = 0;
+  c.w[kGkSource] = source;
+  return c;
+}
+
+// The key of a miss pixel's colour texel: everything the path tracer reads on the way from the pixel to the texel when
+// the primary ray hits nothing (shade_body's miss branch, terminal_write / wf_finalize; DESIGN.md has the table).
+// frameCounter is not in it: a miss draws no random number that reaches the texel, and the only other read of it, the
+// accumulation's mix, makes the draw no static-background draw at all (kMkAccumulate must be 0 for a content id).
+enum MissKeyField {
+  kMkPrimary0,                          // primary_content() of the draw's PrimaryKey: the ray, and which pixels miss
+  kMkHdrHandle = kMkPrimary0 + kPkWords,  // hdrMap: handle, device pointer, Texture::version, size
+  kMkHdrDev, kMkHdrVer, kMkHdrW, kMkHdrH,
+  kMkCacheHandle, kMkCacheDev, kMkCacheVer,  // hdrCache: the merged texture the fetch reads is built from both
+  kMkMerged,                            // whether the fetch reads the merged texture (hdr_merge and its conditions)
+  kMkClamp,                             // uniform clamp_threshold
+  kMkAccumulate,                        // uniform accumulate
+  kMkMaxDepth, kMkShadeFold,            // which kernels write the texel (folded shade, or wf_finalize)
+  kMkSpp,                               // samples per pixel (a resolve averages them)
+  kMkWords
+};
+struct MissKey {
+  uint64_t w[kMkWords];
+};
+inline int miss_key_diff(const MissKey& a, const MissKey& b) {
+  for (int i = 0; i < kMkWords; ++i)
+    if (a.w[i] != b.w[i]) return i;
+  return -1;
+}
+
+// A texture's background stamp: "on the tiles of `scope` this texture holds content `id`". An id names a content, not
+// a texture: the miss colour of a MissKey, or whatever some texture held when something other than an SVGF copy wrote
+// it last (a fresh id: it equals nothing but its own copies). Ids and quiet-set ids come from one counter, so 0 is
+// never one. Bit 63 tags the modulate's form of a content, (c.xyz, 1).
+constexpr uint64_t kBgWhole = 0;             // scope: the whole texture
+constexpr uint64_t kBgModulated = 1ull << 63;
+struct BgStamp {
+  uint64_t id = 0, scope = kBgWhole;  // id 0: nothing is known
+};
+// rule 1: any writer but an SVGF copy leaves a content of its own
+inline BgStamp bg_fresh(uint64_t* serial) { return BgStamp{++*serial, kBgWhole}; }
+inline bool bg_covers(const BgStamp& s, uint64_t set) { return s.id != 0 && set != 0 && (s.scope == kBgWhole || s.scope == set); }
+inline uint64_t bg_tagged(uint64_t id, bool modulated) { return modulated ? id | kBgModulated : id; }
+// rule 2: after an SVGF draw (elided or not) whose quiet-tile set is `set`, an output holds on those tiles what the
+// input it copies from held there; without a set, or with an input that says nothing about the set, it is fresh
+inline BgStamp bg_copy(const BgStamp& in, uint64_t set, bool modulated, uint64_t* serial) {
+  if (!bg_covers(in, set)) return bg_fresh(serial);
+  return BgStamp{bg_tagged(in.id, modulated), set};
+}
+// rule 3: the draw would store on the set's tiles what `out` already holds there
+inline bool bg_pair_quiet(const BgStamp& in, const BgStamp& out, uint64_t set, bool modulated) {
+  return bg_covers(in, set) && bg_covers(out, set) && out.id == bg_tagged(in.id, modulated);
+}
+
+// Which quiet-tile set a reproject draw works with. A set belongs to one (primary content, G-buffer content) pair; it
+// is built when a draw meets the pair of the draw before it, so a moving camera builds none and pays the compare.
+struct QuietChoice {
+  uint64_t prim = 0, gbuf = 0;  // the last draw's pair
+  uint64_t set = 0;             // the set built for it, 0: none yet
+};
+// returns the draw's set (0: none); *build: the caller builds the flags of the returned (new) set now
+inline uint64_t quiet_set_for(QuietChoice& c, uint64_t prim, uint64_t gbuf, uint64_t* serial, bool* build) {
+  *build = false;
+  if (!prim || !gbuf) {
+    c = QuietChoice{};
+    return 0;
+  }
+  if (c.prim != prim || c.gbuf != gbuf) {
+    c.prim = prim;
+    c.gbuf = gbuf;
+    c.set = 0;
+    return 0;
+  }
+  if (!c.set) {
+    c.set = ++*serial;
+    *build = true;
+  }
+  return c.set;
+}
+
 }  // namespace ptk

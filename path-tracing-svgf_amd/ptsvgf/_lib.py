@@ -170,6 +170,22 @@ _PT_SIGS = [
                                                 C.POINTER(C.c_int)]),
     ("pt_debug_point_cache_key_mode", C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_int,
                                                 C.c_int, C.POINTER(C.c_int)]),
+    # include/ptsvgf_debug_background.h
+    ("pt_debug_bg_counts", C.c_int, [_u32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64)]),
+    ("pt_debug_bg_stamp", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("pt_debug_bg_poke_hit0", C.c_int, [_u32, C.c_int, C.c_int, C.c_int, C.c_float]),
+    ("pt_debug_bg_fresh", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("pt_debug_bg_copy", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("pt_debug_bg_pair_quiet", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
+                                         C.POINTER(C.c_int)]),
+    ("pt_debug_bg_quiet_set", C.c_int, [C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    ("pt_debug_bg_miss_key_words", C.c_int, []),
+    ("pt_debug_bg_miss_key_diff", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
+    ("pt_debug_bg_miss_key_id", C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64)]),
+    ("pt_debug_bg_key_content", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
 ]
 
 _PTS_SIGS = [

@@ -422,6 +422,13 @@ def device_ptr(tex: int) -> int:
     return p.value or 0
 
 
+def background_stamp(tex: int):
+    """pt_debug_bg_stamp: (content id, scope) of a texture's background stamp (DESIGN.md "Static view, part 3")."""
+    i, sc = C.c_uint64(), C.c_uint64()
+    check(pt().pt_debug_bg_stamp(tex, C.byref(i), C.byref(sc)))
+    return i.value, sc.value
+
+
 def destroy_texture(tex: int) -> None:
     check(pt().pt_texture_destroy(tex))
 
@@ -529,6 +536,18 @@ class RenderPass:
         check(pt().pt_debug_stage_counts(self._handle(), C.byref(runs), C.byref(reuses)))
         return runs.value, reuses.value
 
+    def background_counts(self):
+        """pt_debug_bg_counts (DESIGN.md "Static view, part 3"): (mode, reason, skipped, total) of this SVGF pass's last
+        draw: mode 0 off / 1 armed / 2 skip, the reason of a bypass (include/ptsvgf_debug_background.h), the tiles the
+        draw skipped and those it has. Synchronises the device when the draw skipped."""
+        mode, reason, skipped, total = C.c_int(), C.c_int(), C.c_uint64(), C.c_uint64()
+        check(pt().pt_debug_bg_counts(self._handle(), C.byref(mode), C.byref(reason), C.byref(skipped), C.byref(total)))
+        return mode.value, reason.value, skipped.value, total.value
+
+    def poke_primary_hit(self, x: int, y: int, tri: int, t: float) -> None:
+        """pt_debug_bg_poke_hit0: make pixel (x, y) of this path-tracing pass's primary plane a hit of triangle tri."""
+        check(pt().pt_debug_bg_poke_hit0(self._handle(), x, y, tri, t))
+
     def point_cache_counts(self):
         """pt_debug_point_cache_counts (DESIGN.md "Static view, part 2"): (served, queued), the bounce-0 point-light
         verdicts of this path-tracing pass's last draw that came from the cache / that were queued as rays.
@@ -599,6 +618,13 @@ class Rasterize_RenderPass(RenderPass):
         one bound now), for object motion vectors; prev_ptr None (or 0) drops the records."""
         check(pt().pt_raster_pass_set_prev_vertices(self._handle(), C.c_void_p(prev_ptr or None),
                                                     C.c_void_p(cur_ptr or None), n_floats))
+
+    def bind_shared(self, src: "Rasterize_RenderPass") -> None:
+        """bindData for a pass that draws src's triangles: the attachments, then share_vertices."""
+        h = self._handle()
+        for t in self.colorAttachments:
+            check(pt().pt_pass_add_color_attachment(h, t))
+        self.share_vertices(src)
 
     def share_vertices(self, src: "Rasterize_RenderPass") -> None:
         """pt_raster_pass_share: draw src's triangles and tree (src bound on its own)."""

@@ -152,7 +152,8 @@ class Renderer:
                  trace_batch: int = 1, front_streams: int | None = None, pt_source=None, pt_flush=None,
                  stage_rows=None, early_history=None, draw_gbuffer: bool = True, fuse_modulate: bool = True,
                  host_pace: bool = False, spp: int = 1, adaptive=None, adaptive_pool=None,
-                 adaptive_rule: str = "relative", adaptive_zeta: float = 0.1, sample_moments: bool = False):
+                 adaptive_rule: str = "relative", adaptive_zeta: float = 0.1, sample_moments: bool = False,
+                 static_background: bool = True):
         """band = (y0, y1, row0, rows) for screen-band sharding; tex_factory(w, h) -> handle allocates the
         frame-sized planes (ptsvgf.dist wraps torch tensors); halo(stage, {plane name: handle}) is called before
         the SVGF passes that read rows beyond the band (dist.HALO_SCHEDULE names the planes); after_gbuffer(set,
@@ -216,7 +217,15 @@ class Renderer:
         Every path-tracing slot owns one RGBA32F texture its draws' resolve fills with (mu, nu, r, n) per pixel
         (pt_pass_set_sample_moments); the reproject and variance passes of that frame's back end bind it as
         gSampleMoments. The mode is fixed for the renderer's life: its history holds per-sample moments from the
-        first frame on. sample_moments() reads the last frame's plane back."""
+        first frame on. sample_moments() reads the last frame's plane back.
+
+        static_background (default True; one-GPU fast driver only, under the conditions of the G-buffer's
+        reuse_static and without bands, stage rows, sample moments or accumulation): the reproject, variance and
+        a-trous passes get the int uniform static_background = 1, so on a standing view their draws skip the tiles
+        that are all background and already hold what the draw would store (DESIGN.md "Static view, part 3"). Same
+        bits in every plane. The G-buffer sets then share one copy of the triangles from construction on, as they do
+        after rebuild_bvh. PTSVGF_STATIC_BACKGROUND=0 in the environment forces it off, here (the renderer is then
+        constructed as with static_background=False) and in the library."""
         if mode not in ("fast", "reference"):
             raise ValueError(mode)
         self._pool = self._check_adaptive_pool(adaptive, adaptive_pool, adaptive_rule, adaptive_zeta)
@@ -327,11 +336,18 @@ class Renderer:
         self._motion_records = self._motion_pending = False
         self._last_raster =np.ascontiguousarray(scene.raster, np.float32).reshape(-1)
         raster_prog = _prog("rasterize_frag.frag", "rasterize_vert.vert")
+        # static_background: the SVGF passes of this renderer write planes nothing else writes (reuse_static's
+        # condition below), and every draw of a frame covers the whole frame with one sample's colour and its own
+        # history. PTSVGF_STATIC_BACKGROUND=0 turns it off here as in the library, so that such a process is
+        # constructed as with static_background=False.
+        self._static_bg = (bool(static_background) and os.environ.get("PTSVGF_STATIC_BACKGROUND", "1") != "0"
+                           and self._draw_gbuffer and after_gbuffer is None and pt_source is None and halo is None
+                           and tex_factory is None and mode == "fast" and band is None and stage_rows is None
+                           and early_history is None and not self._sm_on and not self.cfg.accumulate_color)
         for b in range(nbuf):
             g = dict(world=tex(W, H), normal_depth=tex(W, H), velocity=tex(W, H), fwidth=tex(W, H))
             p = Rasterize_RenderPass(raster_prog, W, H)
             p.colorAttachments += [g["world"], g["normal_depth"], g["velocity"], g["fwidth"]]
-            p.bindData(scene.raster)
             p.set_uniform_int("screen_width", W)
             p.set_uniform_int("screen_height", H)
             if gbuffer_rows is not None:
@@ -342,6 +358,12 @@ class Renderer:
             own_planes = (self._draw_gbuffer and after_gbuffer is None and pt_source is None and halo is None
                           and tex_factory is None)
             p.set_uniform_int("reuse_static", 1 if own_planes else 0)
+            # one copy of the triangles for every set: the sets of one view then have one G-buffer content, which
+            # is what lets a quiet-tile set serve the frames of all of them
+            if b > 0 and self._static_bg:
+                p.bind_shared(self.init_pass[0])
+            else:
+                p.bindData(scene.raster)
             self.init_pass.append(p)
             self.gbuf.append(g)
 
@@ -458,6 +480,7 @@ class Renderer:
         for p in self.reproject + [self.variance_compute_pass, *self.atrous_to.values(), *self.atrous_mod_to.values()]:
             p.set_uniform_float("inv_screen_width", 1.0 / W)
             p.set_uniform_float("inv_screen_height", 1.0 / H)
+            p.set_uniform_int("static_background", 1 if self._static_bg else 0)
 
     # ------------------------------------------------------------- frame ---
     def _ensure_slots(self, n: int) -> None:
