@@ -140,6 +140,16 @@ int pt_texture2d_wrap(void* device_ptr, int width, int height, uint32_t* out_tex
     the library does not see writes to wrapped memory: a wrapped hdrMap / hdrCache whose contents change must be
     wrapped again (a new handle) for the path tracer's merged environment to be rebuilt */
 int pt_texbuffer_create(const void* host_data, size_t bytes, uint32_t fmt, uint32_t* out_tex); /* RGB32F */
+/* Moving point lights (DESIGN.md "Moving point lights"): replaces lights first .. first + count - 1 of the lights
+ * texture buffer a path-tracing pass binds as pointLights. A light is 6 floats, position then colour, as in
+ * main.cpp's light list. Draws already enqueued, on any stream, still read the values they were enqueued with; draws
+ * issued after the call read the new ones. The call does not wait for the device. What was cached per light follows
+ * the lights whose position changed bitwise: the triangle bins of such a light are set aside (its shadow rays walk
+ * the tree) and rebuilt once it has stood for `point_bins_settle` path-tracing draws (int uniform of the
+ * path-tracing pass, >= 0, default 8; 0: at the first draw after the move), and the static view's verdict cache
+ * forgets that light alone. A colour-only change invalidates nothing. Same bits as a fresh buffer with these lights.
+ * PT_ERR_INVALID_HANDLE: not a texture buffer; PT_ERR_ARG: null data, or a range outside the buffer. */
+int pt_lights_update(uint32_t lights_tex, int first, int count, const float* pos_rgb6);
 /* GPU BVH builder for dynamic scenes. The reference builds once on the host
  * (buildBVHwithSAH, Utils/BVH.h:42-173, main.cpp:88-96) and encodes triangles and nodes (main.cpp:101-151);
  * this builds a Karras LBVH on the device from the DEVICE contents of tri_in (Triangle_encoded texels, e.g.
@@ -433,9 +443,10 @@ int pt_trace_stats_total(void);
  * from (tri_tex, node_tex), as the last path-tracing draw of that scene built
  * them; PT_ERR_STATE when it has none. Synchronises the device.
  * info8x4[8 * l ..] for light l < lights: [0] != 0 the light has no usable bins
- * (its rays walk), [1] entries, [2..4] float bits of the light position the
+ * (its rays walk; 2: it moved, pt_lights_update, and its lists are pending), [1] entries, [2..4] float bits of the light position the
  * bins were built around, [5] float bits of the coordinate magnitude the build
- * assumed, [6] entries of its catch-all list, [7] 0.
+ * assumed, [6] entries of its catch-all list, [7] the (triangle, face) boxes
+ * of more than 64 cells its last build binned a wave each.
  * dims4: cells per cube-face edge, lights, entries a light has room for, bytes
  * per entry (a light's lists hold [1] * that many bytes).
  * *bytes: the allocation. Any output may be NULL. */

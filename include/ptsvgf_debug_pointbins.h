@@ -21,6 +21,13 @@ extern "C" {
 int pt_debug_point_bins_overlap(const float* px, const float* py, int n, float fw, int R, int cx0, int cy0, int cx1,
                                 int cy1, uint8_t* kept, size_t cap, int* degenerate);
 
+/* The lists of one light of the scene's bins (pt_point_bins_info), as they lie on the device: hdr receives the
+ * 6 R R + 1 cell headers (first entry, entries), two ints each (hdr_cap: ints of room), ent the light's used entries,
+ * two 32-bit words each (ent_cap: words of room), *entries their count (-1: the light has no usable lists, and ent
+ * is left alone). Synchronises the device. hdr, ent, entries may be NULL. */
+int pt_debug_point_bins_read(uint32_t tri_tex, uint32_t node_tex, int light, int32_t* hdr, size_t hdr_cap,
+                             uint32_t* ent, size_t ent_cap, int* entries);
+
 #ifdef __cplusplus
 }
 #endif

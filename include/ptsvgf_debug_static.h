@@ -45,8 +45,12 @@ int pt_debug_point_cache_read(uint32_t pass, uint16_t* words, size_t n);
 int pt_debug_point_cache_write(uint32_t pass, const uint16_t* words, size_t n);
 /* The mode of the pass's last draw (0 off, 1 reset, 2 use) and whether the plane holds verdicts now (1) or is stale. */
 int pt_debug_point_cache_mode(uint32_t pass, int* mode, int* valid);
+/* The lights (bit i: light i) the cache forgot at the top of the pass's last draw, because pt_lights_update had moved
+ * them since the cache's key; 0 for a draw that forgot nothing. */
+int pt_debug_point_cache_forgotten(uint32_t pass, uint32_t* mask);
 /* The word's bit operations on the host, no device: op 0 look-up of light arg (*out: -1 as 0xFFFFFFFF not known, 0 lit,
- * 1 occluded), 1 the pending light (-1 none), 2 mark light arg pending, 3 resolve the pending light with verdict arg. */
+ * 1 occluded), 1 the pending light (-1 none), 2 mark light arg pending, 3 resolve the pending light with verdict arg,
+ * 5 forget the lights of the bit mask arg (moved lights, pt_lights_update). Op 4 is none and stays PT_ERR_ARG. */
 int pt_debug_point_cache_word(int op, uint32_t word, int arg, uint32_t* out);
 /* The cache's key (csrc/static_key.h LightsKey), as pt_debug_static_key_* for the other two: the word count, the first
  * differing word (-1: equal), and the mode a draw with key `now` gets after the draw that left `last` (last_valid: the

@@ -584,6 +584,10 @@ int bins_for(RasterBins& b, int n, int W, int y0, int y1, int cap, Bins* out) {
 // wavefront path tracer decides point-light shadow rays by the lights' triangle bins (wf_shadow_point_bins), 0 = they
 // walk the tree with the HDR rays. Same bits either way.
 constexpr int kPointBinsDefault = 1;
+// uniform point_bins_settle: the path-tracing draws a moved light must stand before its lists are rebuilt (0: at the
+// first draw after the move). 8 is a placeholder: the measured break-even of walking against rebuilding is about 27
+// frames, with a spread too wide to adopt (DESIGN.md "Moving point lights").
+constexpr int kPointBinsSettle = 8;
 // The point-light bins of a path-tracing draw (PTParams::point_bins / pbins), built or rebuilt on the draw's stream
 // when stale. Off (the rays walk) without 1 .. kPointBins lights all present in the lights buffer, or when a triangle
 // sits in two leaves (the condition that keeps primary_raster at 2: tri_leaf names one leaf per triangle).
@@ -602,9 +606,14 @@ int point_bins_for(Pass* p, SceneGPU* sg, Texture* lt, uint32_t lh, PTParams& k,
   // the polygon's box (A/B; same verdicts, longer lists)
   const int tight = ui(p, "point_bins_tight", 1) ? 1 : 0;
   PointBinsGPU& m = sg->pbins;
-  const bool stale = !m.sb.buf || m.tri_ver != sg->tri_ver || m.node_ver != sg->node_ver || m.ntris != sg->ntris ||
-                     m.light_handle != lh || m.light_dev != lt->dev || m.light_ver != lt->version || m.nl != nl ||
-                     m.R != R || m.tight != tight;
+  // the lights texture of the last build at a newer version, by pt_lights_update alone (only it keeps stamps): the
+  // lights whose position stamp is newer are stale one by one, below; anything else rebuilds every light's lists
+  const bool same_but_lights = m.sb.buf && m.tri_ver == sg->tri_ver && m.node_ver == sg->node_ver &&
+                               m.ntris == sg->ntris && m.light_handle == lh && m.nl == nl && m.R == R && m.tight == tight;
+  const bool updated = same_but_lights && reads.light_stamps && reads.light_count >= nl &&
+                       (m.light_dev != lt->dev || m.light_ver != lt->version);
+  const bool stale = !same_but_lights || (!updated && (m.light_dev != lt->dev || m.light_ver != lt->version));
+  auto stamp_of = [&](int l) { return reads.light_stamps && l < reads.light_count ? reads.light_stamps[l] : 0; };
   if (stale) {
     const size_t need = ptk::point_bins_bytes(sg->ntris, nl, R, tight);
     HIPCHK(m.sb.renew(need));
@@ -620,11 +629,38 @@ int point_bins_for(Pass* p, SceneGPU* sg, Texture* lt, uint32_t lh, PTParams& k,
     m.nl = nl;
     m.R = R;
     m.tight = tight;
+    for (int l = 0; l < ptk::kPointBins; ++l) {
+      m.per_light[l] = ptk::LightBinsState{};
+      m.per_light[l].built = m.per_light[l].seen = stamp_of(l);
+    }
     if (getenv("PTSVGF_SCENE_INFO"))
       fprintf(stderr, "ptsvgf point-light bins: %d lights, R = %d, %zu B allocated (headers %zu B per light)\n", nl, R,
               need, (size_t)(6 * R * R + 1) * sizeof(int2));
   }
   HIPCHK(m.sb.wait_built(g.stream));
+  // Moving lights (DESIGN.md "Moving point lights"), once per draw and light (lights_key.h light_bins_step): a light
+  // that moved is marked (info[l][0] = 2: its rays walk) and, once it has stood for point_bins_settle draws, gets its
+  // lists rebuilt, alone and in place. Both write what the draws in flight on other streams read, so this stream
+  // first waits for their recorded reads; draws issued later wait for this write's event as for a build. No host wait.
+  if (same_but_lights && (updated || m.light_ver == lt->version)) {
+    const int settle = std::max(0, ui(p, "point_bins_settle", kPointBinsSettle));
+    bool wrote = false;
+    for (int l = 0; l < nl; ++l) {
+      const int act = ptk::light_bins_step(m.per_light[l], stamp_of(l), settle);
+      if (act != ptk::kLbMark && act != ptk::kLbRebuild) continue;
+      if (!wrote)
+        for (auto& u : m.sb.uses)
+          if (u.first != g.stream) HIPCHK(hipStreamWaitEvent(g.stream, u.second, 0));
+      wrote = true;
+      const int rc = act == ptk::kLbMark
+                         ? ptk::launch_point_bins_mark_moved(m.dev, l, g.stream)
+                         : ptk::launch_point_bins_rebuild_light(k.scene, nl, R, tight, m.sb.buf, l, g.stream);
+      if (rc) return hip_err((hipError_t)rc, "point-light bins of a moved light");
+    }
+    if (wrote) HIPCHK(m.sb.mark_built(g.stream));
+    m.light_dev = lt->dev;
+    m.light_ver = lt->version;
+  }
   reads.pbins = &m.sb;
   k.point_bins = 1;
   k.pbins = m.dev;
@@ -685,6 +721,12 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
     k.scene.nlights_buf = (int)(lt->bytes / (6 * sizeof(float)));
     reads.light_handle = lh;
     reads.light_ver = lt->version;
+    if (lt->lights) {  // pt_lights_update wrote it: this version's copy runs on another stream, and is read until noted
+      HIPCHK(lt->lights->sb.wait_built(g.stream));
+      reads.lights = &lt->lights->sb;
+      reads.light_stamps = lt->lights->pos_stamp.data();
+      reads.light_count = (int)lt->lights->pos_stamp.size();
+    }
   }
   // uniform sampler2DArray material_array (path_tracing.frag:331-364); unbound -> fetches read 0
   Texture* ma = sampler(p, "material_array");
@@ -886,8 +928,9 @@ void primary_cache_note(Pass* p, const ptk::PrimaryKey& key, bool reused, bool o
 // The bounce-0 point-light verdict cache of a one-sample wavefront draw (DESIGN.md "Static view, part 2"), after
 // pt_wf_setup: the cache's key of this draw (the primary key and what the bounce-0 shadow ray reads beyond it) and the
 // draw's mode, into k.point_cache. The draw's caller notes the outcome (ptk::point_cache_note).
+// *forgets: the draw uses the cache after forgetting the lights of *forget (the mask may be 0: a colour-only update).
 ptk::LightsKey point_cache_mode_for(Pass* p, PTParams& k, const ptk::PrimaryKey& pkey, bool stage_reused,
-                                    const DrawReads& reads) {
+                                    const DrawReads& reads, bool* forgets, uint32_t* forget) {
   using namespace ptk;
   LightsKey q{};
   memcpy(q.w + kLkPrimary0, pkey.w, sizeof(pkey.w));
@@ -905,7 +948,18 @@ ptk::LightsKey point_cache_mode_for(Pass* p, PTParams& k, const ptk::PrimaryKey&
   const bool fold = k.shade_fold && k.max_depth > 0;
   const bool bypass = ui(p, "point_cache", 1) == 0 || p->stats || p->row_cost || k.pointLightSize < 1 ||
                       k.pointLightSize > kPcLights || k.wf.spill || !fold;
-  k.point_cache = point_cache_mode(p->lcache, q, stage_reused, bypass);
+  // a lights buffer that pt_lights_update moved on forgets the moved lights' bits instead of resetting every word
+  // (lights_key.h); a texture without stamps (never updated) has no lights to name: it resets as ever
+  *forget = 0;
+  bool fg = false;
+  k.point_cache = point_cache_mode_lights(p->lcache, q, stage_reused, bypass, &fg);
+  if (fg && !reads.light_stamps) {
+    k.point_cache = kPcReset;
+    fg = false;
+  }
+  *forgets = fg;
+  if (fg) *forget = lights_moved_mask(reads.light_stamps, std::min(reads.light_count, (int)kPcLights),
+                                      p->lcache.key.w[kLkLightVer]);
   return q;
 }
 
@@ -981,6 +1035,7 @@ const ptk::WfFork* wf_fork(Pass* p, hipStream_t s, int* rc) {
 int note_reads(const DrawReads& r) {
   if (r.pbins) HIPCHK(r.pbins->note_read(g.stream));
   if (r.hdr) HIPCHK(r.hdr->note_read(g.stream));
+  if (r.lights) HIPCHK(r.lights->note_read(g.stream));
   return PT_OK;
 }
 
@@ -1065,11 +1120,15 @@ int draw_pathtrace(Pass* p) {
     TRY(pt_wf_setup(p, k, sg, p->wf.st, &key, &reuse));
     const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
     if (rc) return rc;
-    const ptk::LightsKey lkey = point_cache_mode_for(p, k, key, reuse, reads);
-    rc = launch_pathtrace_wavefront(k, g.stream, fk, reuse);
+    bool forgets = false;
+    uint32_t forget = 0;
+    const ptk::LightsKey lkey = point_cache_mode_for(p, k, key, reuse, reads, &forgets, &forget);
+    rc = forget ? ptk::launch_point_cache_forget(k.wf.pcache, p->wf.n, forget, g.stream) : 0;
+    if (!rc) rc = launch_pathtrace_wavefront(k, g.stream, fk, reuse);
     primary_cache_note(p, key, reuse, rc == 0);
-    ptk::point_cache_note(p->lcache, lkey, k.point_cache, rc == 0);
+    ptk::point_cache_note_lights(p->lcache, lkey, k.point_cache, forgets, rc == 0);
     p->lcache_last_mode = k.point_cache;
+    p->lcache_last_forgot = forget;
     if (!rc && k.tiles.cost) p->order.ordered = true;
     if (!rc) bg_note_colour(p, k, key, reads);
   }
@@ -1732,6 +1791,7 @@ int pt_shutdown(void) {
   (void)hipDeviceSynchronize();
   for (auto& kv : g.textures) {
     Texture* t = kv.second.get();
+    free_lights(t);
     if (t->owned && t->dev) (void)hipFree(t->dev);
     if (t->aux) (void)hipFree(t->aux);
     if (t->tflags) (void)hipFree(t->tflags);
@@ -1782,6 +1842,8 @@ int pt_stream_release(void* s) {
   // the stream's last reads of the merged environments and of the scenes' point-light bins: done before the entry goes
   for (auto& kv : g.hdr_merged) kv.second.sb.forget(st);
   for (auto& kv : g.scenes) kv.second.pbins.sb.forget(st);
+  for (auto& kv : g.textures)
+    if (kv.second->lights) kv.second->lights->sb.forget(st);
   if (g.stream == st) g.stream = g.own;
   return PT_OK;
 }
@@ -2297,7 +2359,8 @@ int pt_debug_point_cache_word(int op, uint32_t word, int arg, uint32_t* out) {
     case 1: *out = (uint32_t)ptk::pc_pending(word); break;
     case 2: *out = ptk::pc_mark_pending(word, arg); break;
     case 3: *out = ptk::pc_resolve(word, arg != 0); break;
-    default: return err(PT_ERR_ARG, "pt_debug_point_cache_word: op 0 (look-up) .. 3 (resolve)");
+    case 5: *out = ptk::pc_forget(word, (uint32_t)arg); break;  // (4 stays no op: it has always been refused)
+    default: return err(PT_ERR_ARG, "pt_debug_point_cache_word: op 0 (look-up) .. 3 (resolve), 5 (forget)");
   }
   return PT_OK;
 }
@@ -2393,6 +2456,7 @@ int pt_texture_destroy(uint32_t tex) {
   auto it = g.textures.find(tex);
   if (it == g.textures.end()) return err(PT_ERR_INVALID_HANDLE, "invalid texture");
   (void)hipStreamSynchronize(g.stream);
+  free_lights(it->second.get());  // every version of an updated lights buffer (dev is one of them)
   if (it->second->owned && it->second->dev) (void)hipFree(it->second->dev);
   if (it->second->aux) (void)hipFree(it->second->aux);
   if (it->second->tflags) (void)hipFree(it->second->tflags);

@@ -17,8 +17,11 @@
 #include "../../include/ptsvgf.h"
 #include "pt_device.h"
 #include "static_key.h"
+#include "lights_key.h"
 
 namespace ptapi {
+
+struct LightVersions;
 
 enum ProgKind { PK_PATHTRACE = 1, PK_REPROJECT, PK_VARIANCE, PK_ATROUS, PK_MODULATE, PK_BLIT, PK_SAVE, PK_OUTPUT, PK_TAA,
                 PK_RASTER };
@@ -66,6 +69,8 @@ struct Texture {
   uint64_t refit_tri_ver = 0, refit_node_ver = 0;
   // pt_bvh_refit wrote dev in place; host is brought up to date by its readers (refresh_host)
   bool host_stale = false;
+  // a lights buffer pt_lights_update has written (capi_lights.hip; owned): dev is then lights->sb.buf
+  LightVersions* lights = nullptr;
 };
 
 struct Uniform {
@@ -132,6 +137,7 @@ struct Pass {
   ptk::GbufCache gcache;     // rasterize pass: its last completed draw's key (reuse_static)
   ptk::PointCache lcache;    // path-tracing pass: the bounce-0 point-light verdict cache (DESIGN.md "Static view, part 2")
   int lcache_last_mode = 0;  // the PointCacheMode of the pass's last draw (pt_debug_point_cache_mode)
+  uint32_t lcache_last_forgot = 0;  // the lights that draw's cache forgot first (pt_debug_point_cache_forgotten)
   int W = 0, H = 0;
   std::vector<uint32_t> att;
   bool bound = false, final_pass = false;
@@ -243,11 +249,27 @@ struct SharedBuf {
   }
 };
 
+// The device versions of a lights texture buffer that pt_lights_update changes (DESIGN.md "Moving point lights"). An
+// update never writes memory a queued draw may read: it takes a version that nothing in flight reads (SharedBuf::renew:
+// the draws note their reads of the current one), copies the whole host copy into it through a pinned staging buffer
+// of its own on the current stream, and makes it Texture::dev. The buffer pt_texbuffer_create made is read by draws
+// that noted nothing, so the first update sets it aside for good (`first`) and it is freed with the texture.
+struct LightVersions {
+  SharedBuf sb;
+  void* first = nullptr;
+  hipStream_t upload = nullptr;     // the copies' stream (non-blocking, created by the first update)
+  std::map<void*, void*> staging;   // per device version: its pinned host buffer (free again when the version is)
+  std::vector<uint64_t> pos_stamp;  // per light: the Texture::version at which its position last changed bitwise
+};
+
 // What the draw being issued reads of the shared buffers (pt_params, point_bins_for), noted on its stream after a
 // successful launch (note_reads). Local to the draw call, which holds g_mu throughout.
 struct DrawReads {
   SharedBuf* hdr = nullptr;
   SharedBuf* pbins = nullptr;
+  SharedBuf* lights = nullptr;  // the device version of an updated lights buffer (LightVersions)
+  const uint64_t* light_stamps = nullptr;  // its per-light position stamps (null: never updated, all 0)
+  int light_count = 0;
   // the pointLights texture the draw bound (0: none): part of the verdict cache's key (static_key.h)
   uint32_t light_handle = 0;
   uint64_t light_ver = 0;
@@ -267,6 +289,8 @@ struct PointBinsGPU {
   uint32_t light_handle = 0;
   const void* light_dev = nullptr;
   int nl = 0, R = 0, ntris = 0, tight = 0;
+  // per light: the position stamp its lists were built for, and how long a moved light has stood (lights_key.h)
+  ptk::LightBinsState per_light[ptk::kPointBins];
 };
 
 struct SceneGPU {
@@ -422,6 +446,8 @@ void free_trees(Texture* t);
 void free_refit(Texture* t);
 void free_raster_refit(RasterScene& r);
 void free_pose(Pose& p);
+// defined in capi_lights.hip: the versions of an updated lights buffer, the current one (t->dev) included
+void free_lights(Texture* t);
 
 // (T: the device type, or the host tree builder's Float4 for float4)
 template <class T, class D>

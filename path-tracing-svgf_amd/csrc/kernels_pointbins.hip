@@ -28,8 +28,8 @@ namespace {
 constexpr int kScanThreads = 1024;
 
 struct PbLayout {
-  size_t info, hdr, cnt, tmp, ent, total;
-  int cap;
+  size_t info, hdr, cnt, tmp, ent, lrg, total;
+  int cap, lrg_cap;
 };
 // entries a light's lists have room for. Measured on the bench scene (30 633 triangles, lights 0.3 .. 1 from the
 // geometry), the largest light's entries per triangle at R = 32 / 64 / 128: 4.6 / 8.9 / 20.0 by the polygon (the test
@@ -47,7 +47,10 @@ inline PbLayout pb_layout(int ntris, int nl, int R, int tight) {
   l.hdr = l.cnt + up((size_t)nl * ncell1 * sizeof(int));
   l.tmp = l.hdr + up((size_t)nl * ncell1 * sizeof(int2));
   l.ent = l.tmp + up((size_t)l.cap * sizeof(uint4));
-  l.total = l.ent + up((size_t)nl * l.cap * sizeof(uint2));
+  // the large boxes' work list (pb_bin_large): a record per (triangle, face), so it cannot overflow
+  l.lrg_cap = (int)std::min<size_t>((size_t)6 * (size_t)std::max(ntris, 1), (size_t)1 << 30);
+  l.lrg = l.ent + up((size_t)nl * l.cap * sizeof(uint2));
+  l.total = l.lrg + up((size_t)nl * l.lrg_cap * sizeof(uint32_t));
   return l;
 }
 
@@ -60,8 +63,17 @@ struct PbBuild {
   uint2* ent;    // nl x cap: entries (PointBinsDev), each cell ascending by near
   int R, nl, cap;
   int tight;     // cells by the projected polygon (pb_overlap.h), 0: every cell of its box
-  int l0;        // the scatter's and the sort's light (their grids have one light)
+  int l0;        // the first light of the grid (the scatter's and the sort's grids have one light; so does every
+                 // kernel of a one-light rebuild, launch_point_bins_rebuild_light)
+  int ln;        // lights pb_lights sets up, from l0
+  uint32_t* lrg; // nl x lrg_cap: per light the (triangle << 3 | face) records of the boxes pb_bin left to pb_bin_large;
+                 // their count is info[l][7]
+  int lrg_cap;
+  int large_min; // a box of more cells than this is left to pb_bin_large (kPbLargeCells; INT_MAX: none is)
 };
+
+// a (triangle, face) box of more cells than one wave's worth is binned by a wave, not by one thread
+constexpr int kPbLargeCells = 64;
 
 // largest finite coordinate magnitude of the triangles' vertices (a positive float's bits order as an int's)
 __global__ void __launch_bounds__(256) pb_extent(PbBuild b) {
@@ -80,7 +92,8 @@ __global__ void __launch_bounds__(256) pb_extent(PbBuild b) {
 }
 
 __global__ void __launch_bounds__(64) pb_lights(PbBuild b) {
-  const int l = threadIdx.x;
+  if ((int)threadIdx.x >= b.ln) return;
+  const int l = b.l0 + threadIdx.x;
   if (l >= b.nl) return;
   int* f = b.info + l * kPointBinsInfo;
   const float* lp = b.sc.lights + 6 * l;
@@ -97,14 +110,17 @@ __global__ void __launch_bounds__(64) pb_lights(PbBuild b) {
 
 constexpr uint32_t kBoxEmpty = 0x000000ffu;  // x0 = 255 > x1 = 0
 
-// One thread per (triangle, light blockIdx.y): the triangle's cell box and near bound on each face, or the catch-all
-// list. SCATTER = false counts the cells, true writes the entries (the same arithmetic, so the same cells).
-template <bool SCATTER>
-__global__ void __launch_bounds__(256) pb_bin(PbBuild b) {
-  const int i = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y + b.l0;
-  if (i >= b.sc.ntris) return;
-  const int* f = b.info + l * kPointBinsInfo;
-  if (f[0]) return;  // no usable bins for this light
+// Triangle i of light l: the triangle's cell box and near bound on each face, or the catch-all list. SCATTER = false
+// counts the cells, true writes the entries (the same arithmetic, so the same cells).
+// LARGE = false (pb_bin, one thread per triangle): the cells of every face's box, but a box of more than
+// b.large_min cells is left to pb_bin_large: the count pass appends (triangle, face) to the light's work list, the
+// scatter pass skips it (the list is still there). LARGE = true (pb_bin_large, one wave per record, every lane with
+// the same i): face fc_only alone, the lanes striding over its box's cells. Both run this one body, so a cell is
+// kept, and its entry formed, by the same arithmetic whoever emits it: the set of entries is the serial loop's, and
+// pb_sort's (near, triangle) order makes the lists identical.
+template <bool SCATTER, bool LARGE>
+__device__ __forceinline__ void pb_tri(const PbBuild& b, int i, int l, int fc_only, int lane) {
+  int* f = b.info + l * kPointBinsInfo;
   const int R = b.R, ncell = 6 * R * R;
   int* cnt = b.cnt + (size_t)l * (ncell + 1);
   const int2* hdr = b.hdr + (size_t)l * (ncell + 1);
@@ -194,13 +210,22 @@ __global__ void __launch_bounds__(256) pb_bin(PbBuild b) {
     nearf[fc] = fmaxf(fmaxf(ds, wmin) * 0.99999f - e, 0.0f);
   }
   if (catchall) {
-    emit(ncell, 0.0f, 0xff00ff00u);
+    if (!LARGE) emit(ncell, 0.0f, 0xff00ff00u);  // (no record names a catch-all triangle)
     return;
   }
   for (int fc = 0; fc < 6; ++fc) {
+    if (LARGE && fc != fc_only) continue;
     const uint32_t bx = box[fc];
     const int cx0 = bx & 255u, cx1 = (bx >> 8) & 255u, cy0 = (bx >> 16) & 255u, cy1 = bx >> 24;
     if (cx0 > cx1) continue;
+    const int bw = cx1 - cx0 + 1, ncells = bw * (cy1 - cy0 + 1);
+    if (LARGE != (ncells > b.large_min)) {  // the other kernel's box
+      if (!LARGE && !SCATTER) {
+        const int slot = atomicAdd(f + 7, 1);
+        if (slot < b.lrg_cap) b.lrg[(size_t)l * b.lrg_cap + slot] = ((uint32_t)i << 3) | (uint32_t)fc;
+      }
+      continue;
+    }
     // tight: of the box's cells only those the projected polygon, widened by fw, reaches (pb_overlap.h); the box's
     // every cell when it has at most two or the polygon is degenerate (edges.n = 0 keeps all)
     PbEdges edges;
@@ -216,20 +241,52 @@ __global__ void __launch_bounds__(256) pb_bin(PbBuild b) {
     }
     // the extent inside each cell in 1 / 256 of a cell: (x0, x1, y0, y1), 8 bits each; pb_sort keeps the high 4
     auto q = [](float v) { return (uint32_t)min(max((int)floorf(v * 256.0f), 0), 255); };
-    for (int cy = cy0; cy <= cy1; ++cy)
-      for (int cx = cx0; cx <= cx1; ++cx)
-        if (pb_cell_kept(edges, fwf[fc], cx, cy, R))
-          emit((fc * R + cy) * R + cx, nearf[fc],
-               q(ext[fc][0] - (float)cx) | (q(ext[fc][1] - (float)cx) << 8) | (q(ext[fc][2] - (float)cy) << 16) |
-                   (q(ext[fc][3] - (float)cy) << 24));
+    auto cell = [&](int cx, int cy) {
+      if (pb_cell_kept(edges, fwf[fc], cx, cy, R))
+        emit((fc * R + cy) * R + cx, nearf[fc],
+             q(ext[fc][0] - (float)cx) | (q(ext[fc][1] - (float)cx) << 8) | (q(ext[fc][2] - (float)cy) << 16) |
+                 (q(ext[fc][3] - (float)cy) << 24));
+    };
+    if (LARGE) {
+      for (int c = lane; c < ncells; c += 64) cell(cx0 + c % bw, cy0 + c / bw);
+    } else {
+      for (int cy = cy0; cy <= cy1; ++cy)
+        for (int cx = cx0; cx <= cx1; ++cx) cell(cx, cy);
+    }
   }
 }
 
-// One block per light: headers (first entry, entries) from the cell counts, which are zeroed for the scatter; a
+// One thread per (triangle, light blockIdx.y + l0).
+template <bool SCATTER>
+__global__ void __launch_bounds__(256) pb_bin(PbBuild b) {
+  const int i = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y + b.l0;
+  if (i >= b.sc.ntris) return;
+  if (b.info[l * kPointBinsInfo]) return;  // no usable bins for this light
+  pb_tri<SCATTER, false>(b, i, l, 0, 0);
+}
+
+// One wave per record of light blockIdx.y + l0's work list, the grid's waves striding over the records (their count
+// is known on the device only: info[l][7], complete since the count pass's pb_bin ended).
+constexpr int kPbLargeBlocks = 256;
+template <bool SCATTER>
+__global__ void __launch_bounds__(256) pb_bin_large(PbBuild b) {
+  const int l = blockIdx.y + b.l0;
+  const int* f = b.info + l * kPointBinsInfo;
+  if (f[0]) return;
+  const int nrec = min(f[7], b.lrg_cap);
+  const int lane = threadIdx.x & 63, nw = gridDim.x * 4;
+  for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < nrec; r += nw) {
+    const uint32_t rec = b.lrg[(size_t)l * b.lrg_cap + r];
+    const int i = (int)(rec >> 3), fc = (int)(rec & 7u);
+    if (i < b.sc.ntris && fc < 6) pb_tri<SCATTER, true>(b, i, l, fc, lane);
+  }
+}
+
+// One block per light (blockIdx.x + l0): headers (first entry, entries) from the cell counts, which are zeroed for the scatter; a
 // light whose entries exceed `cap` gets no bins.
 __global__ void __launch_bounds__(kScanThreads) pb_scan(PbBuild b) {
   __shared__ int part[kScanThreads];
-  const int l = blockIdx.x, n1 = 6 * b.R * b.R + 1, t = threadIdx.x;
+  const int l = blockIdx.x + b.l0, n1 = 6 * b.R * b.R + 1, t = threadIdx.x;
   int* cnt = b.cnt + (size_t)l * n1;
   int2* hdr = b.hdr + (size_t)l * n1;
   const int per = (n1 + kScanThreads - 1) / kScanThreads, lo = min(t * per, n1), hi = min(lo + per, n1);
@@ -282,6 +339,9 @@ __global__ void __launch_bounds__(256) pb_sort(PbBuild b) {
   }
 }
 
+// (a record packs the triangle into 29 bits)
+inline int pb_large_min(int ntris) { return ntris < (1 << 29) ? kPbLargeCells : 0x7fffffff; }
+
 }  // namespace
 
 size_t point_bins_bytes(int ntris, int nl, int R, int tight) { return pb_layout(ntris, nl, R, tight).total; }
@@ -293,20 +353,65 @@ int launch_point_bins_build(const SceneDev& sc, int nl, int R, int tight, void* 
   const PbLayout lay = pb_layout(sc.ntris, nl, R, tight);
   char* c = (char*)base;
   PbBuild b{sc, (int*)(c + lay.info), (int*)(c + lay.cnt), (int2*)(c + lay.hdr), (uint4*)(c + lay.tmp),
-            (uint2*)(c + lay.ent), R, nl, lay.cap, tight ? 1 : 0, 0};
+            (uint2*)(c + lay.ent), R, nl, lay.cap, tight ? 1 : 0, 0, nl, (uint32_t*)(c + lay.lrg), lay.lrg_cap,
+            pb_large_min(sc.ntris)};
   hipError_t e = hipMemsetAsync(base, 0, lay.hdr, s);  // info and the cell counts
   if (e != hipSuccess) return (int)e;
   const int gt = (sc.ntris + 255) / 256, n1 = 6 * R * R + 1;
   if (gt > 0) hipLaunchKernelGGL(pb_extent, dim3(gt), dim3(256), 0, s, b);
   hipLaunchKernelGGL(pb_lights, dim3(1), dim3(64), 0, s, b);
   if (gt > 0) hipLaunchKernelGGL(pb_bin<false>, dim3(gt, nl), dim3(256), 0, s, b);
-  hipLaunchKernelGGL(pb_scan, dim3(nl), dim3(kScanThreads), 0, s, b);
+  if (gt > 0) hipLaunchKernelGGL(pb_bin_large<false>, dim3(kPbLargeBlocks, nl), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(pb_scan, dim3(nl), dim3(kScanThreads), 0, s, b);  // (b.l0 = 0: every light)
   for (b.l0 = 0; b.l0 < nl; ++b.l0) {  // one scatter buffer serves every light in turn
     if (gt > 0) hipLaunchKernelGGL(pb_bin<true>, dim3(gt, 1), dim3(256), 0, s, b);
+    if (gt > 0) hipLaunchKernelGGL(pb_bin_large<true>, dim3(kPbLargeBlocks, 1), dim3(256), 0, s, b);
     hipLaunchKernelGGL(pb_sort, dim3((n1 + 3) / 4, 1), dim3(256), 0, s, b);
   }
   *out = PointBinsDev{b.hdr, b.ent, b.info, R, nl, lay.cap};
   return (int)hipGetLastError();
+}
+
+// The lists of light l alone, in place, around the position sc.lights holds for it now: the full build's kernels
+// restricted to that light (its info record, cell counts, headers and entry section; the scatter buffer is shared and
+// the stream orders its users). The scene's magnitude (pb_extent) is a function of the triangles, which have not
+// changed, and stays. The other lights' sections are not touched. The caller orders this after every draw that reads
+// the bins (capi.hip point_bins_for).
+int launch_point_bins_rebuild_light(const SceneDev& sc, int nl, int R, int tight, void* base, int l, hipStream_t s) {
+  if (nl < 1 || nl > kPointBins || R < 1 || R > kPointBinsMaxR || !base || !sc.lights || !sc.tri_leaf || l < 0 ||
+      l >= nl)
+    return (int)hipErrorInvalidValue;
+  const PbLayout lay = pb_layout(sc.ntris, nl, R, tight);
+  char* c = (char*)base;
+  PbBuild b{sc, (int*)(c + lay.info), (int*)(c + lay.cnt), (int2*)(c + lay.hdr), (uint4*)(c + lay.tmp),
+            (uint2*)(c + lay.ent), R, nl, lay.cap, tight ? 1 : 0, l, 1, (uint32_t*)(c + lay.lrg), lay.lrg_cap,
+            pb_large_min(sc.ntris)};
+  const int gt = (sc.ntris + 255) / 256, n1 = 6 * R * R + 1;
+  // this light's cell counts (the last scatter left its fill counts there) and its info record
+  hipError_t e = hipMemsetAsync(b.cnt + (size_t)l * n1, 0, (size_t)n1 * sizeof(int), s);
+  if (e == hipSuccess) e = hipMemsetAsync(b.info + l * kPointBinsInfo, 0, kPointBinsInfo * sizeof(int), s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(pb_lights, dim3(1), dim3(64), 0, s, b);
+  if (gt > 0) hipLaunchKernelGGL(pb_bin<false>, dim3(gt, 1), dim3(256), 0, s, b);
+  if (gt > 0) hipLaunchKernelGGL(pb_bin_large<false>, dim3(kPbLargeBlocks, 1), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(pb_scan, dim3(1), dim3(kScanThreads), 0, s, b);
+  if (gt > 0) hipLaunchKernelGGL(pb_bin<true>, dim3(gt, 1), dim3(256), 0, s, b);
+  if (gt > 0) hipLaunchKernelGGL(pb_bin_large<true>, dim3(kPbLargeBlocks, 1), dim3(256), 0, s, b);
+  hipLaunchKernelGGL(pb_sort, dim3((n1 + 3) / 4, 1), dim3(256), 0, s, b);
+  return (int)hipGetLastError();
+}
+
+// info[l][0] = 2: light l moved and its lists are pending; both trace kernels walk for any non-zero value
+int launch_point_bins_mark_moved(const PointBinsDev& pb, int l, hipStream_t s) {
+  if (!pb.info || l < 0 || l >= pb.nl) return (int)hipErrorInvalidValue;
+  return (int)hipMemsetD32Async((hipDeviceptr_t)(pb.info + l * kPointBinsInfo), 2, 1, s);
+}
+
+// where light l's headers and entries lie in a build's allocation (pt_debug_point_bins_read)
+void point_bins_sections(int ntris, int nl, int R, int tight, int l, size_t* hdr_off, size_t* ent_off) {
+  const PbLayout lay = pb_layout(ntris, nl, R, tight);
+  *hdr_off = lay.hdr + (size_t)l * ((size_t)6 * R * R + 1) * sizeof(int2);
+  *ent_off = lay.ent + (size_t)l * lay.cap * sizeof(uint2);
 }
 
 }  // namespace ptk

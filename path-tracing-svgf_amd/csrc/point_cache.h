@@ -36,5 +36,14 @@ constexpr uint32_t pc_resolve(uint32_t w, bool occluded) {
   w |= 1u << li;
   return occluded ? (w | (1u << (4 + li))) : (w & ~(1u << (4 + li)));
 }
+// the lights of `mask` (bit i: light i) moved (pt_lights_update): their known and occluded bits are cleared, and the
+// pending field too if it names one of them (its ray went to the old position). The other lights' bits stay.
+constexpr uint32_t pc_forget(uint32_t w, uint32_t mask) {
+  const uint32_t m = mask & ((1u << kPcLights) - 1u);
+  const int li = pc_pending(w);
+  w &= ~(m | (m << 4));
+  if (li >= 0 && li < kPcLights && ((m >> li) & 1u)) w &= ~kPcPendingMask;
+  return w;
+}
 
 }  // namespace ptk

@@ -256,8 +256,9 @@ struct Bins {
 // found to hit (a cell's entries ascend by it; truncating a float >= 0 rounds it down); the box (x0 | x1 << 4 |
 // y0 << 8 | y1 << 12, in 1 / 16 of the cell) holds every direction of the cell from which such a ray can arrive.
 // info: kPointBinsInfo ints per light: [0] != 0: the light has no usable bins (a non-finite position, or the entries
-// overflowed `cap`: its rays walk), [1] entries, [2..4] float bits of the light position the bins were built around,
-// [5] float bits of Mtot, the coordinate magnitude of the scene plus the light's, [6] the catch-all list's entries.
+// overflowed `cap`: its rays walk; 2: the light moved and its lists are pending, capi.hip point_bins_for), [1] entries, [2..4] float bits of the light position the bins were built around,
+// [5] float bits of Mtot, the coordinate magnitude of the scene plus the light's, [6] the catch-all list's entries,
+// [7] the (triangle, face) boxes of the light's last build that went to pb_bin_large (kernels_pointbins.hip).
 constexpr int kPointBinsInfo = 8;
 constexpr int kPointBinsMaxR = 128;  // (the build packs a cell box into 4 x 8 bits)
 struct PointBinsDev {
@@ -508,6 +509,14 @@ size_t point_bins_bytes(int ntris, int nl, int R, int tight);
 constexpr int kPointBinsEntryBytes = 8;
 int launch_point_bins_build(const SceneDev& sc, int nl, int R, int tight, void* base, PointBinsDev* out,
                             hipStream_t s);
+// Moving point lights: light l's lists rebuilt in place around its position in sc.lights, the other
+// lights' sections untouched; info[l][0] = 2 ("moved, bins pending": its rays walk); a light's sections in `base`.
+int launch_point_bins_rebuild_light(const SceneDev& sc, int nl, int R, int tight, void* base, int l, hipStream_t s);
+int launch_point_bins_mark_moved(const PointBinsDev& pb, int l, hipStream_t s);
+void point_bins_sections(int ntris, int nl, int R, int tight, int l, size_t* hdr_off, size_t* ent_off);
+// The verdict cache forgets the lights of `mask` (pc_forget, point_cache.h) on the n words of `plane`
+// (kernels_lights.hip).
+int launch_point_cache_forget(uint16_t* plane, size_t n, uint32_t mask, hipStream_t s);
 }  // namespace ptk
 
 namespace ptk {

@@ -91,6 +91,7 @@ _PT_SIGS = [
     ("pt_texture2d_upload", C.c_int, [_u32, C.c_int, C.c_int, _u32, _fp]),
     ("pt_texture2d_wrap", C.c_int, [_vp, C.c_int, C.c_int, _u32p]),
     ("pt_texbuffer_create", C.c_int, [_vp, C.c_size_t, _u32, _u32p]),
+    ("pt_lights_update", C.c_int, [_u32, C.c_int, C.c_int, _fp]),
     ("pt_bvh_build", C.c_int, [_u32, C.c_int, C.c_int, _u32, _u32, C.POINTER(C.c_int), _fp]),
     ("pt_bvh_refit", C.c_int, [_u32, _u32, _u32, _fp]),
     ("pt_texarray_create", C.c_int, [C.c_int, C.c_int, C.c_int, _u32p]),
@@ -153,7 +154,18 @@ _PT_SIGS = [
     # include/ptsvgf_debug_pointbins.h
     ("pt_debug_point_bins_overlap", C.c_int, [_fp, _fp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int)]),
+    ("pt_debug_point_bins_read", C.c_int, [_u32, _u32, C.c_int, C.POINTER(C.c_int32), C.c_size_t, _u32p, C.c_size_t,
+                                           C.POINTER(C.c_int)]),
+    # include/ptsvgf_debug_lights.h
+    ("pt_debug_lights_moved_mask", C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_uint64, _u32p]),
+    ("pt_debug_lights_settle", C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    ("pt_debug_lights_key_mode", C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_int,
+                                           C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("pt_debug_lights_key_field", C.c_int, [C.c_int]),
+    ("pt_debug_lights_state", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int,
+                                        C.POINTER(C.c_int)]),
     # include/ptsvgf_debug_static.h
+    ("pt_debug_point_cache_forgotten", C.c_int, [_u32, _u32p]),
     ("pt_debug_stage_counts", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("pt_debug_static_key_words", C.c_int, [C.c_int]),
     ("pt_debug_static_key_diff", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int,

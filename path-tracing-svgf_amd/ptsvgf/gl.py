@@ -90,6 +90,73 @@ def texture_buffer(data: np.ndarray) -> int:
     return h.value
 
 
+def lights_update(tex: int, first: int, lights) -> None:
+    """pt_lights_update: replaces lights first .. of the lights texture buffer `tex` by `lights` ((n, 6) float32:
+    position, colour). Draws already enqueued keep the values they were enqueued with; nothing waits for the device."""
+    a = np.ascontiguousarray(lights, dtype=np.float32).reshape(-1, 6)
+    check(pt().pt_lights_update(tex, int(first), a.shape[0], fptr(a)))
+
+
+def lights_state(tex: int, nl: int = 4) -> dict:
+    """pt_debug_lights_state (include/ptsvgf_debug_lights.h): {"version", "pos_stamps" (per light: the version at which
+    its position last changed, 0 never), "device_versions" (device buffers the texture owns)}."""
+    ver, n = C.c_uint64(), C.c_int()
+    st = (C.c_uint64 * max(nl, 1))()
+    check(pt().pt_debug_lights_state(tex, C.byref(ver), st, int(nl), C.byref(n)))
+    return {"version": ver.value, "pos_stamps": [int(v) for v in st][:nl], "device_versions": n.value}
+
+
+def lights_moved_mask(pos_stamps, since: int) -> int:
+    """pt_debug_lights_moved_mask: bit l for every light whose position stamp is newer than `since`. Host only."""
+    a, pa = _key_ptr(pos_stamps)
+    m = C.c_uint32()
+    check(pt().pt_debug_lights_moved_mask(pa, int(a.size), int(since), C.byref(m)))
+    return m.value
+
+
+def lights_settle(stamps, settle: int) -> list:
+    """pt_debug_lights_settle: what consecutive draws do with one light's bins (built at stamp 0) as they meet
+    `stamps`: 0 keep, 1 mark moved, 2 still marked, 3 rebuild. Host only."""
+    a, pa = _key_ptr(stamps)
+    out = (C.c_int * max(int(a.size), 1))()
+    check(pt().pt_debug_lights_settle(pa, int(a.size), int(settle), out))
+    return [int(v) for v in out][:a.size]
+
+
+def lights_key_mode(last, last_valid: bool, now, stage_reused: bool, enabled: bool) -> tuple:
+    """pt_debug_lights_key_mode: (mode 0 off / 1 reset / 2 use, forgets) of a draw with verdict-cache key `now` after
+    the draw that left `last`, with the moved-lights rule. Host only."""
+    last, pl = _key_ptr(last)
+    now, pn = _key_ptr(now)
+    mode, forget = C.c_int(), C.c_int()
+    check(pt().pt_debug_lights_key_mode(pl, 1 if last_valid else 0, pn, int(min(last.size, now.size)),
+                                        1 if stage_reused else 0, 1 if enabled else 0, C.byref(mode), C.byref(forget)))
+    return mode.value, bool(forget.value)
+
+
+def lights_key_field(which: int) -> int:
+    """pt_debug_lights_key_field: the key word of 0 the lights handle, 1 their device pointer, 2 their version, 3
+    point_bins, 4 the bins' device pointer."""
+    return check(pt().pt_debug_lights_key_field(int(which)))
+
+
+def point_bins_read(tri_tex: int, node_tex: int, light: int):
+    """pt_debug_point_bins_read: (hdr (6 R R + 1, 2) int32, ent (entries, 2) uint32) of one light's lists as they lie
+    on the device; (hdr, None) for a light without usable lists."""
+    R = point_bins_info(tri_tex, node_tex)["R"]
+    n1 = 6 * R * R + 1
+    hdr = np.zeros((n1, 2), np.int32)
+    n = C.c_int()
+    check(pt().pt_debug_point_bins_read(tri_tex, node_tex, int(light), hdr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        hdr.size, None, 0, C.byref(n)))
+    if n.value < 0:
+        return hdr, None
+    ent = np.zeros((n.value, 2), np.uint32)
+    check(pt().pt_debug_point_bins_read(tri_tex, node_tex, int(light), None, 0,
+                                        ent.ctypes.data_as(C.POINTER(C.c_uint32)), ent.size, C.byref(n)))
+    return hdr, ent
+
+
 def buffer_readback(tex: int) -> np.ndarray:
     """Device contents of a texture buffer as flat float32 (3 floats per RGB32F texel)."""
     w, _, _ = texture_info(tex)
@@ -232,14 +299,16 @@ def lbvh_trees(tex: int, source: int = 0) -> dict:
 def point_bins_info(tri_tex: int, node_tex: int) -> dict:
     """pt_point_bins_info: the point-light triangle bins the last path-tracing draw of the scene (tri_tex, node_tex)
     built: cells per face edge R, lights, entry capacity per light, bytes per entry, allocated bytes, and per light
-    {"off": no usable bins, "entries", "list_bytes" (entries x entry_bytes), "catch_all", "pos", "magnitude"}."""
+    {"off": no usable bins (2: the light moved, its bins are pending), "entries", "list_bytes" (entries x
+    entry_bytes), "catch_all", "pos", "magnitude", "large": (triangle, face) boxes its last build binned a wave each}."""
     info = (C.c_int * 32)()
     dims = (C.c_int * 4)()
     nbytes = C.c_size_t()
     check(pt().pt_point_bins_info(tri_tex, node_tex, info, dims, C.byref(nbytes)))
     raw = np.array(list(info), np.int32).reshape(4, 8)
     lights = [{"off": int(r[0]), "entries": int(r[1]), "list_bytes": int(r[1]) * dims[3], "catch_all": int(r[6]),
-               "pos": r[2:5].view(np.float32).tolist(), "magnitude": float(r[5:6].view(np.float32)[0])}
+               "pos": r[2:5].view(np.float32).tolist(), "magnitude": float(r[5:6].view(np.float32)[0]),
+               "large": int(r[7])}
               for r in raw[:dims[1]]]
     return {"R": dims[0], "lights": dims[1], "cap": dims[2], "entry_bytes": dims[3], "bytes": nbytes.value,
             "per_light": lights}
@@ -294,7 +363,7 @@ def static_key_hit(kind: int, last, last_valid: bool, now, enabled: bool) -> boo
 def point_cache_word(op: int, word: int, arg: int = 0) -> int:
     """pt_debug_point_cache_word: the verdict word's bit operations (csrc/point_cache.h) on the host. op 0: look-up of
     light `arg` (-1 not known, 0 lit, 1 occluded); 1: the pending light (-1 none); 2: mark light `arg` pending;
-    3: resolve the pending light with verdict `arg`."""
+    3: resolve the pending light with verdict `arg`; 5: forget the lights of the bit mask `arg` (4 is no op)."""
     out = C.c_uint32()
     check(pt().pt_debug_point_cache_word(int(op), int(word), int(arg), C.byref(out)))
     return C.c_int32(out.value).value if op in (0, 1) else out.value
@@ -561,6 +630,13 @@ class RenderPass:
         mode, valid = C.c_int(), C.c_int()
         check(pt().pt_debug_point_cache_mode(self._handle(), C.byref(mode), C.byref(valid)))
         return mode.value, bool(valid.value)
+
+    def point_cache_forgotten(self) -> int:
+        """pt_debug_point_cache_forgotten: the lights (bit i: light i) the verdict cache forgot at the top of the
+        pass's last draw; 0: none."""
+        m = C.c_uint32()
+        check(pt().pt_debug_point_cache_forgotten(self._handle(), C.byref(m)))
+        return m.value
 
     def point_cache_read(self, n: int):
         """pt_debug_point_cache_read: the verdict plane, one uint16 per pixel of the rows last drawn (n of them)."""

@@ -5,6 +5,7 @@ written as PNG and, optionally, the selected plane's raw floats as PFM.
     python -m ptsvgf.render_cli --width 800 --height 800 --frames 8 --view final_pic --png out.png
 
 --sway DEG bends the bench scene's plant on the device each frame (Renderer.set_skin / skin_objects).
+--light-orbit DEG turns point light 0 about the scene's vertical axis each frame (Renderer.set_lights).
 """
 from __future__ import annotations
 
@@ -61,6 +62,29 @@ def _sway_setup(r, scene, obj: int = 2):
     return lambda deg: skin.chain_bones(base, tip, SWAY_BONES, deg, (0.0, 0.0, 1.0))
 
 
+def _light_orbit_setup(scene, light: int = 0):
+    """--light-orbit: frame count -> the light's record turned by that many steps about the vertical (y) axis through
+    the middle of the scene's bounds. Each position is turned from the first one, so the steps do not accumulate
+    rounding."""
+    from . import skin
+
+    if scene.lights.shape[0] <= light:
+        raise SystemExit(f"--light-orbit: the scene has no light {light}")
+    tp = skin.corner_positions(scene.tri_enc)
+    tp = tp[np.all(np.isfinite(tp), axis=1)]
+    cx, cz = ((tp[:, 0].min() + tp[:, 0].max()) / 2, (tp[:, 2].min() + tp[:, 2].max()) / 2) if len(tp) else (0.0, 0.0)
+    rec0 = np.array(scene.lights[light], np.float64)
+
+    def at(deg: float) -> np.ndarray:
+        c, s = np.cos(np.radians(deg)), np.sin(np.radians(deg))
+        x, z = rec0[0] - cx, rec0[2] - cz
+        rec = rec0.copy()
+        rec[0], rec[2] = cx + c * x + s * z, cz - s * x + c * z
+        return rec.astype(np.float32)
+
+    return at
+
+
 def main(argv=None) -> int:
     from . import gl
     from .camera import parameter_config
@@ -89,6 +113,8 @@ def main(argv=None) -> int:
                     help="SVGF's variance from the samples' own moments (needs --spp >= 2)")
     ap.add_argument("--sway", type=float, default=None, metavar="DEG",
                     help="bend the plant (object 2) by an 8-bone chain, the angle a sine over the frames of this amplitude")
+    ap.add_argument("--light-orbit", type=float, default=0.0, metavar="DEG",
+                    help="turn point light 0 about the scene's vertical axis by DEG per frame (moving light)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
 
@@ -104,7 +130,10 @@ def main(argv=None) -> int:
                      sample_moments=a.sample_moments)
         r.set_view(a.view)
         sway = _sway_setup(r, scene) if a.sway is not None else None
+        light_at = _light_orbit_setup(scene) if a.light_orbit else None
         for f in range(a.frames):
+            if light_at is not None:
+                r.set_lights(light_at(a.light_orbit * (f + 1)), first=0)
             if a.orbit:
                 r.camera.orbit(a.orbit, 0.0)
             if sway is not None:

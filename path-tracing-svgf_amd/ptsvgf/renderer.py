@@ -153,7 +153,7 @@ class Renderer:
                  stage_rows=None, early_history=None, draw_gbuffer: bool = True, fuse_modulate: bool = True,
                  host_pace: bool = False, spp: int = 1, adaptive=None, adaptive_pool=None,
                  adaptive_rule: str = "relative", adaptive_zeta: float = 0.1, sample_moments: bool = False,
-                 static_background: bool = True):
+                 static_background: bool = True, light_settle: int | None = None):
         """band = (y0, y1, row0, rows) for screen-band sharding; tex_factory(w, h) -> handle allocates the
         frame-sized planes (ptsvgf.dist wraps torch tensors); halo(stage, {plane name: handle}) is called before
         the SVGF passes that read rows beyond the band (dist.HALO_SCHEDULE names the planes); after_gbuffer(set,
@@ -375,6 +375,11 @@ class Renderer:
         self.accumulate = bool(self.cfg.accumulate_color)
         nslots = max(self.K, 2) if (self.accumulate and mode == "fast") else self.K
         self.pt_slots = []
+        # set_lights: the path-tracing draws a moved light stands before its triangle bins are rebuilt (uniform
+        # point_bins_settle); None: the library's default
+        if light_settle is not None and int(light_settle) < 0:
+            raise ValueError(f"light_settle must be >= 0, got {light_settle}")
+        self._light_settle = None if light_settle is None else int(light_settle)
         self._pt_prune = prune
         self._ensure_slots(nslots)
         self._use_slot(0)
@@ -515,6 +520,8 @@ class Renderer:
             # (profiles/point_bins/ab_first.log): off then. With frames in flight the library's default holds.
             if self.K == 1:
                 p.set_uniform_int("point_bins", 0)
+            if self._light_settle is not None:
+                p.set_uniform_int("point_bins_settle", self._light_settle)
             # a ray still walking past VISIT_BUDGET node + triangle visits is finished by the wave-cooperative walk
             # (same bits): the launches no longer end on a few long walks. Round 5, same box (profiles/r05/serial/):
             # one frame at a time with lane refill 145.2 -> 160.8 fps at 4K (budgets 128 / 512: 151.3 / 151.8; refill
@@ -773,6 +780,22 @@ class Renderer:
         self._spp = n
         for p, _ in self.pt_slots:
             p.set_spp(n)
+
+    def set_lights(self, lights, first: int = 0) -> None:
+        """Moving point lights (pt_lights_update): lights first .. first + n - 1 become `lights` ((n, 6): position,
+        colour) from the next frame() on. The frames in flight are not flushed and keep the lights they were issued
+        with; only an open path-tracing batch (trace_batch > 1), whose draws are still to be issued, is issued first.
+        A light whose position changed walks the tree until it has stood for light_settle frames; then its triangle
+        bins are rebuilt. Same bits as a renderer built on these lights."""
+        a = np.ascontiguousarray(lights, dtype=np.float32).reshape(-1, 6)
+        first = int(first)
+        if first < 0 or first + a.shape[0] > self.scene.lights.shape[0]:
+            raise ValueError(f"set_lights: lights {first} .. {first + a.shape[0] - 1} of {self.scene.lights.shape[0]}")
+        self._issue_batch()
+        gl.lights_update(self.pointLightBuffer, first, a)
+        new = np.array(self.scene.lights, dtype=np.float32, copy=True)
+        new[first:first + a.shape[0]] = a
+        self.scene.lights = new
 
     def _issue_batch(self) -> None:
         """Draw the open batch's path tracers on the stream of its last frame, after all its G-buffers."""
