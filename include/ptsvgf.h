@@ -466,7 +466,14 @@ int pt_point_bins_info(uint32_t tri_tex, uint32_t node_tex, int* info8x4, int* d
  *    left them launches nothing and returns PT_OK. The library tracks its own
  *    writes (draws of any pass, uploads, pt_tiles_copy, adopt) and every call that
  *    changes the triangles; a pass with a motion bound always draws.
- *    PTSVGF_STATIC_REUSE=0 in the environment forces 0. */
+ *    PTSVGF_STATIC_REUSE=0 in the environment forces 0.
+ *  - path-tracing pass, int uniform reuse_static (default 0): the same statement
+ *    about its three attachments. Then a one-sample, whole-frame draw that reuses
+ *    the primary stage, and finds on its attachments the records of an earlier
+ *    draw with the same view, scene, environment and settings, leaves its miss
+ *    pixels and the emission and albedo planes as they are (DESIGN.md "Static
+ *    view, part 4"; include/ptsvgf_debug_firsthit.h). The environment variable
+ *    forces this 0 as well. */
 int pt_pass_draw(uint32_t pass);
 /* Draw `count` (1..8) path-tracing passes — the frames of a batch, each with its
  * own uniforms, samplers and attachments, one scene, size and band — as one

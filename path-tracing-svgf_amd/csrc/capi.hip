@@ -17,6 +17,7 @@
 
 #include "../../include/ptsvgf_debug_pointbins.h"
 #include "../../include/ptsvgf_debug_background.h"
+#include "../../include/ptsvgf_debug_firsthit.h"
 #include "../../include/ptsvgf_debug_static.h"
 #include "../../include/ptsvgf_scene.h"
 #include "capi_state.h"
@@ -227,6 +228,7 @@ void free_pass(Pass* p) {
   if (p->wf.spill) (void)hipFree(p->wf.spill);
   if (p->order.cost) (void)hipFree(p->order.cost);
   if (p->order.perm) (void)hipFree(p->order.perm);
+  if (p->busy) (void)hipFree(p->busy);
   if (p->ev0) (void)hipEventDestroy(p->ev0);
   if (p->ev1) (void)hipEventDestroy(p->ev1);
 }
@@ -918,6 +920,7 @@ void primary_cache_note(Pass* p, const ptk::PrimaryKey& key, bool reused, bool o
     if (ok) p->pcache.reuses++;
     return;  // (a failed launch wrote nothing into hit0)
   }
+  p->busy_valid = false;  // the busy-tile list is that of the stage before this one
   p->pcache.valid = ok;
   if (ok) {
     p->pcache.key = key;
@@ -967,12 +970,22 @@ ptk::LightsKey point_cache_mode_for(Pass* p, PTParams& k, const ptk::PrimaryKey&
 // accumulation: the colour attachment's miss texels are the content of the draw's MissKey (static_key.h), whichever
 // slot's plane this is; the texture also remembers the draw's primary content and whose hit0 holds its primary hits,
 // for the quiet-tile flags. Any other path-tracing draw leaves the stamp att_plane made: fresh.
+ptk::MissKey miss_key_of(const PTParams& k, const ptk::PrimaryKey& key, const DrawReads& reads);
 void bg_note_colour(Pass* p, const PTParams& k, const ptk::PrimaryKey& key, const DrawReads& reads) {
   using namespace ptk;
   Texture* ct = tex_of(p->att[0]);
   if (!ct || k.accumulate || k.y0 != 0 || k.y1 != k.H || k.tile_stride != 1 || band_partition(k.W, k.H) ||
       ct->row0 != 0 || ct->rows != k.H || !k.wf.hit0)
     return;
+  const PrimaryKey pc = primary_content(key);
+  const MissKey m = miss_key_of(k, key, reads);
+  ct->bg = BgStamp{g.bg_miss.of(m.w, kMkWords, &g.bg_serial), kBgWhole};
+  ct->bg_prim = g.bg_prim.of(pc.w, kPkWords, &g.bg_serial);
+  ct->bg_pass = p;
+  ct->bg_pass_gen = p->wf.gen;
+}
+ptk::MissKey miss_key_of(const PTParams& k, const ptk::PrimaryKey& key, const DrawReads& reads) {
+  using namespace ptk;
   const PrimaryKey pc = primary_content(key);
   MissKey m{};
   memcpy(m.w + kMkPrimary0, pc.w, sizeof(pc.w));
@@ -990,10 +1003,111 @@ void bg_note_colour(Pass* p, const PTParams& k, const ptk::PrimaryKey& key, cons
   m.w[kMkMaxDepth] = key_bits(k.max_depth);
   m.w[kMkShadeFold] = k.shade_fold;
   m.w[kMkSpp] = 1;
-  ct->bg = BgStamp{g.bg_miss.of(m.w, kMkWords, &g.bg_serial), kBgWhole};
-  ct->bg_prim = g.bg_prim.of(pc.w, kPkWords, &g.bg_serial);
-  ct->bg_pass = p;
-  ct->bg_pass_gen = p->wf.gen;
+  return m;
+}
+
+// PTSVGF_STATIC_REUSE=0 in the environment forces every reuse_static off (A/B)
+bool reuse_static_env_off() {
+  static const bool env_off = [] {
+    const char* e = getenv("PTSVGF_STATIC_REUSE");
+    return e && atoi(e) == 0;
+  }();
+  return env_off;
+}
+
+// The bounce-0 shade's keep mode (DESIGN.md "Static view, part 4") of a one-sample wavefront draw.
+// What the three attachments say before the draw: read before pt_params, whose att_plane renews all of it.
+struct FirstHitBefore {
+  ptk::BgStamp colour;
+  uint64_t emission = 0, albedo = 0;
+};
+FirstHitBefore first_hit_before(Pass* p) {
+  FirstHitBefore b;
+  Texture* t[3] = {nullptr, nullptr, nullptr};
+  for (size_t i = 0; i < 3 && i < p->att.size(); ++i) t[i] = tex_of(p->att[i]);
+  if (t[0]) b.colour = t[0]->bg;
+  if (t[1]) b.emission = t[1]->first_hit;
+  if (t[2]) b.albedo = t[2]->first_hit;
+  return b;
+}
+// The pass's last draw was none that could keep: a sampled or batched draw, or the megakernel's.
+void first_hit_off(Pass* p, int reason) {
+  p->fh_mode = ptk::kFhOff;
+  p->fh_reason = reason;
+}
+// After pt_wf_setup: the draw's mode, and for a draw that is not bypassed the content id of its FirstHitKey in *first.
+// A kept draw gets k.busy, the pass's busy-tile list, built here on the draw's stream when the primary stage ran since
+// it was last built; in the verdict cache's reset mode the words of the pixels the kept draw does not visit are
+// cleared here instead (a fresh word is 0).
+int first_hit_mode_for(Pass* p, PTParams& k, const SceneGPU* sg, const ptk::PrimaryKey& key, bool stage_reused,
+                       const DrawReads& reads, const FirstHitBefore& before, uint64_t* first) {
+  using namespace ptk;
+  *first = 0;
+  uint32_t bypass = 0;
+  auto by = [&](bool c, int r) { if (c) bypass |= 1u << r; };
+  bool whole = k.y0 == 0 && k.y1 == k.H && !band_partition(k.W, k.H);
+  for (int i = 0; i < 3; ++i) {
+    const Texture* t = tex_of(p->att[i]);
+    whole = whole && t && t->row0 == 0 && t->rows == k.H;
+  }
+  by(ui(p, "reuse_static", 0) == 0, kFhrUniform);
+  by(reuse_static_env_off(), kFhrEnv);
+  by(p->stats || p->row_cost, kFhrStats);
+  by(k.tile_stride != 1, kFhrTiles);
+  by(!whole, kFhrRows);
+  by(k.wf.spill != nullptr, kFhrDeep);
+  by(!k.shade_fold, kFhrUnfolded);
+  by(k.max_depth <= 0, kFhrDepth0);
+  by(k.accumulate != 0, kFhrAccumulate);
+  uint64_t miss = 0;
+  if (!bypass) {
+    const MissKey m = miss_key_of(k, key, reads);
+    miss = g.bg_miss.of(m.w, kMkWords, &g.bg_serial);
+    const PrimaryKey pc = primary_content(key);
+    FirstHitKey f{};
+    memcpy(f.w + kFkPrimary0, pc.w, sizeof(pc.w));
+    f.w[kFkTriShade] = key_bits((const void*)k.scene.tri_shade);
+    f.w[kFkTriShadeVer] = sg->tri_ver;
+    uint32_t mh = 0;
+    const Texture* ma = sampler(p, "material_array", &mh);
+    if (k.scene.texarr && ma) {
+      f.w[kFkMatHandle] = mh;
+      f.w[kFkMatDev] = key_bits((const void*)k.scene.texarr);
+      f.w[kFkMatVer] = ma->version;
+      f.w[kFkMatW] = key_bits(k.scene.tex_w);
+      f.w[kFkMatH] = key_bits(k.scene.tex_h);
+      f.w[kFkMatLayers] = key_bits(k.scene.tex_layers);
+    }
+    *first = g.bg_first.of(f.w, kFkWords, &g.bg_serial);
+  }
+  p->fh_mode = first_hit_mode(bypass, stage_reused, before.colour, before.emission, before.albedo, miss, *first,
+                              &p->fh_reason);
+  if (p->fh_mode != kFhKeep) return PT_OK;
+  const int ntiles = wf_subset_tiles(k.W, k.H, 1, 0);
+  if (p->busy_n != ntiles) {
+    if (p->busy) (void)hipFree(p->busy);
+    p->busy = nullptr;
+    p->busy_n = 0;
+    p->busy_valid = false;
+    HIPCHK(hipMalloc((void**)&p->busy, busy_tiles_ints(ntiles) * sizeof(int)));
+    p->busy_n = ntiles;
+  }
+  if (!p->busy_valid) {
+    const int rc = launch_busy_tiles(k, p->busy, g.stream);
+    if (rc) return hip_err((hipError_t)rc, "busy-tile list");
+    p->busy_valid = true;
+  }
+  if (k.point_cache == kPcReset) HIPCHK(hipMemsetAsync(k.wf.pcache, 0, p->wf.n * sizeof(uint16_t), g.stream));
+  k.busy = p->busy;
+  return PT_OK;
+}
+// after the launch of a draw first_hit_mode_for gave a mode: a draw that was not bypassed has left emission and albedo
+// holding the content `first` (bg_note_colour stamps the colour); a failed one leaves what att_plane left: nothing
+void first_hit_note(Pass* p, uint64_t first, bool ok) {
+  if (!ok || p->fh_mode == ptk::kFhOff) return;
+  if (Texture* t = tex_of(p->att[1])) t->first_hit = first;
+  if (Texture* t = tex_of(p->att[2])) t->first_hit = first;
+  if (p->fh_mode == ptk::kFhKeep) p->fh_kept++;
 }
 
 // The side stream and events of path-tracing draws issued on `s` (uniform trace_fork = 1), created on first use: one
@@ -1097,9 +1211,11 @@ int draw_pathtrace(Pass* p) {
   PTParams k;
   SceneGPU* sg = nullptr;
   DrawReads reads;
+  const FirstHitBefore before = first_hit_before(p);  // (pt_params' att_plane makes the attachments' stamps fresh)
   TRY(pt_params(p, k, sg, reads));
   int rc;
   if (spp > 1) {
+    first_hit_off(p, ptk::kFhrSpp);
     TRY(draw_pathtrace_spp(p, k, sg, spp));
     return note_reads(reads);
   }
@@ -1111,6 +1227,7 @@ int draw_pathtrace(Pass* p) {
     p->pcache.valid = false;  // (it sorts the pass's tile order by its own costs)
     p->lcache.valid = false;
     p->lcache_last_mode = 0;
+    first_hit_off(p, ptk::kFhrMegakernel);
     rc = launch_pathtrace(k, g.stream);
   } else {                            // 0: wavefront (kernels_wavefront.hip), production
     TRY(wf_alloc(p->wf, k.W, std::max(0, k.y1 - k.y0)));
@@ -1123,9 +1240,12 @@ int draw_pathtrace(Pass* p) {
     bool forgets = false;
     uint32_t forget = 0;
     const ptk::LightsKey lkey = point_cache_mode_for(p, k, key, reuse, reads, &forgets, &forget);
+    uint64_t first = 0;
+    TRY(first_hit_mode_for(p, k, sg, key, reuse, reads, before, &first));
     rc = forget ? ptk::launch_point_cache_forget(k.wf.pcache, p->wf.n, forget, g.stream) : 0;
     if (!rc) rc = launch_pathtrace_wavefront(k, g.stream, fk, reuse);
     primary_cache_note(p, key, reuse, rc == 0);
+    first_hit_note(p, first, rc == 0);
     ptk::point_cache_note_lights(p->lcache, lkey, k.point_cache, forgets, rc == 0);
     p->lcache_last_mode = k.point_cache;
     p->lcache_last_forgot = forget;
@@ -1178,6 +1298,7 @@ int draw_pathtrace_batch(Pass** ps, int n) {
   for (int b = 0; b < n; ++b) {
     ps[b]->pcache.valid = ps[b]->lcache.valid = false;
     ps[b]->lcache_last_mode = 0;
+    first_hit_off(ps[b], ptk::kFhrBatch);
   }
   for (int b = 0; b < n; ++b) TRY(pt_wf_setup(ps[b], k[b], sg, h->wf.stb[b]));
   // the batched shadow launches read frame 0's point-light bins for every frame: frames that do not share them (other
@@ -1295,12 +1416,9 @@ bool gbuf_key(Pass* p, const Pass* src, ptk::GbufKey* out) {
 // reuse_static (int uniform of a rasterize pass, default 0): the caller states that nothing outside the library writes
 // this pass's attachments between its draws. PTSVGF_STATIC_REUSE=0 in the environment forces it off (A/B).
 bool reuse_static_on(Pass* p) {
-  static const bool env_off = [] {
-    const char* e = getenv("PTSVGF_STATIC_REUSE");
-    return e && atoi(e) == 0;
-  }();
-  return !env_off && ui(p, "reuse_static", 0) != 0;
+  return !reuse_static_env_off() && ui(p, "reuse_static", 0) != 0;
 }
+
 
 int draw_raster(Pass* p) {
   Pass* src = p->raster_src ? pass_of(p->raster_src) : p;
@@ -2216,6 +2334,73 @@ int pt_debug_bg_poke_hit0(uint32_t pass, int x, int y, int tri, float t) {
   memcpy(&v.y, &t, sizeof(t));
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(p->wf.st.hit0 + (size_t)y * p->W + x, &v, sizeof(v), hipMemcpyHostToDevice));
+  // the plane is no longer what the stage wrote: the busy-tile list and the first-hit records were derived from that
+  p->busy_valid = false;
+  for (size_t i = 1; i < 3 && i < p->att.size(); ++i)
+    if (Texture* at = tex_of(p->att[i])) at->first_hit = 0;
+  return PT_OK;
+}
+
+// ---- the bounce-0 shade's keep mode (DESIGN.md "Static view, part 4")
+int pt_debug_firsthit_last(uint32_t pass, int* mode, int* reason, uint64_t* kept) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (g.programs[p->program] != PK_PATHTRACE) return err(PT_ERR_ARG, "pt_debug_firsthit_last: a path-tracing pass");
+  if (mode) *mode = p->fh_mode;
+  if (reason) *reason = p->fh_reason;
+  if (kept) *kept = p->fh_kept;
+  return PT_OK;
+}
+
+int pt_debug_firsthit_busy(uint32_t pass, int* busy, int* tiles) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  Pass* p = pass_of(pass);
+  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
+  if (g.programs[p->program] != PK_PATHTRACE) return err(PT_ERR_ARG, "pt_debug_firsthit_busy: a path-tracing pass");
+  if (!busy || !tiles) return err(PT_ERR_ARG, "pt_debug_firsthit_busy: null argument");
+  *busy = -1;
+  *tiles = ptk::wf_subset_tiles(p->W, p->H, 1, 0);
+  if (!p->busy || !p->busy_valid) return PT_OK;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(busy, p->busy, sizeof(int), hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+int pt_debug_firsthit_record(uint32_t tex, uint64_t* id) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  const Texture* t = tex_of(tex);
+  if (!t) return err(PT_ERR_INVALID_HANDLE, "invalid texture");
+  if (!id) return err(PT_ERR_ARG, "pt_debug_firsthit_record: null argument");
+  *id = t->first_hit;
+  return PT_OK;
+}
+
+int pt_debug_firsthit_key_words(void) { return (int)ptk::kFkWords; }
+
+int pt_debug_firsthit_key_diff(const uint64_t* a, const uint64_t* b, int words, int* field) {
+  if (!a || !b || !field) return err(PT_ERR_ARG, "pt_debug_firsthit_key_diff: null argument");
+  if (words != (int)ptk::kFkWords) return err(PT_ERR_ARG, "pt_debug_firsthit_key_diff: not the key's word count");
+  ptk::FirstHitKey ka, kb;
+  memcpy(ka.w, a, sizeof(ka.w));
+  memcpy(kb.w, b, sizeof(kb.w));
+  *field = ptk::first_hit_key_diff(ka, kb);
+  return PT_OK;
+}
+
+int pt_debug_firsthit_key_id(const uint64_t* key, int words, uint64_t* id) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  if (!key || !id) return err(PT_ERR_ARG, "pt_debug_firsthit_key_id: null argument");
+  if (words != (int)ptk::kFkWords) return err(PT_ERR_ARG, "pt_debug_firsthit_key_id: not the key's word count");
+  *id = g.bg_first.of(key, words, &g.bg_serial);
+  return PT_OK;
+}
+
+int pt_debug_firsthit_decide(uint32_t bypass, int stage_reused, uint64_t colour_id, uint64_t colour_scope,
+                             uint64_t emission, uint64_t albedo, uint64_t miss, uint64_t first, int* mode, int* reason) {
+  if (!mode || !reason) return err(PT_ERR_ARG, "pt_debug_firsthit_decide: null argument");
+  *mode = ptk::first_hit_mode(bypass, stage_reused != 0, ptk::BgStamp{colour_id, colour_scope}, emission, albedo, miss,
+                              first, reason);
   return PT_OK;
 }
 

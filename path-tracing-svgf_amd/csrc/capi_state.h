@@ -50,6 +50,10 @@ struct Texture {
   uint64_t bg_prim = 0, bg_gbuf = 0;
   const void* bg_pass = nullptr;
   uint64_t bg_pass_gen = 0;
+  // the first-hit record (static_key.h, DESIGN.md "Static view, part 4"): on an emission or albedo attachment a
+  // qualifying one-sample wavefront draw wrote, the content id of that draw's FirstHitKey; 0: nothing is known.
+  // tex_written clears it.
+  uint64_t first_hit = 0;
   // compact one-float side plane of the stored rows: a depth-fwidth attachment's fwidth.y with the background flag, a
   // world-position attachment's primary-ray bound for rays from aux_eye (draw_raster)
   float* aux = nullptr;
@@ -138,6 +142,14 @@ struct Pass {
   ptk::PointCache lcache;    // path-tracing pass: the bounce-0 point-light verdict cache (DESIGN.md "Static view, part 2")
   int lcache_last_mode = 0;  // the PointCacheMode of the pass's last draw (pt_debug_point_cache_mode)
   uint32_t lcache_last_forgot = 0;  // the lights that draw's cache forgot first (pt_debug_point_cache_forgotten)
+  // path-tracing pass: the bounce-0 shade's keep mode (DESIGN.md "Static view, part 4"). The busy-tile list of the
+  // primary stage that ran last (ptk::launch_busy_tiles; busy_valid: built since that stage, busy_n: the tiles it was
+  // sized and built for), and of the pass's last draw its FirstHitMode / FirstHitReason; the draws that kept.
+  int* busy = nullptr;
+  int busy_n = 0;
+  bool busy_valid = false;
+  int fh_mode = 0, fh_reason = 0;
+  uint64_t fh_kept = 0;
   int W = 0, H = 0;
   std::vector<uint32_t> att;
   bool bound = false, final_pass = false;
@@ -400,6 +412,7 @@ struct Lib {
   // keys, the reproject draws' choice of a set, and the sets (the newest kQuietSets)
   uint64_t bg_serial = 0;
   ContentIds bg_miss, bg_prim, bg_gbuf;
+  ContentIds bg_first;  // of FirstHitKeys (Texture::first_hit)
   ptk::QuietChoice bg_choice;
   QuietSet bg_sets[kQuietSets];
   int bg_next = 0;
@@ -437,6 +450,7 @@ inline void tex_written(Texture* t) {
   t->bg_prim = t->bg_gbuf = 0;
   t->bg_pass = nullptr;
   t->bg_off = 0;
+  t->first_hit = 0;
 }
 int ensure_init();
 int refresh_host(Texture* t);

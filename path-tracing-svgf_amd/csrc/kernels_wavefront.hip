@@ -1701,6 +1701,8 @@ __device__ __forceinline__ void shade_body(const PTParams& p, int bounce_rt, con
   // folded: bounce_rt is any bounce of the instantiation's kind; only `bounce == 0` is decided at compile time
   const int bounce = FOLD && FIRST ? 0 : bounce_rt;
   const bool first = FOLD ? FIRST : bounce == 0;
+  // keep mode (PTParams::busy) exists in the folded bounce-0 shade of a one-sample draw alone
+  constexpr bool kKeep = FOLD && FIRST && !COUNTED;
   // bounce 0: one tile per block. Later bounces: 256 list items per chunk, a block taking chunks blockIdx.x,
   // + gridDim.x, ... (a grid a multiple of kSeg: chunk c appends to segment c % kSeg, as one block per chunk did)
   int total = 0;
@@ -1715,7 +1717,14 @@ __device__ __forceinline__ void shade_body(const PTParams& p, int bounce_rt, con
       // (tiles.perm_next, sorted right after wf_primary): the rays of expensive tiles are appended to
       // the lists first, so every later list-driven trace launch starts its slowest rays first
       const int ntx = (p.W + 15) / 16;
-      const int tile = (p.tiles.cost ? p.tiles.perm_next[blockIdx.x] : (int)blockIdx.x) * p.tile_stride + p.tile_offset;
+      int slot;
+      if (kKeep && p.busy) {  // keep mode: the tiles that hold a primary hit, in the same order (launch_busy_tiles)
+        if ((int)blockIdx.x >= p.busy[0]) return;
+        slot = p.busy[1 + blockIdx.x];
+      } else {
+        slot = p.tiles.cost ? p.tiles.perm_next[blockIdx.x] : (int)blockIdx.x;
+      }
+      const int tile = slot * p.tile_stride + p.tile_offset;
       const int x = (tile % ntx) * 16 + (threadIdx.x & 15), ly = (tile / ntx) * 16 + (threadIdx.x >> 4);
       valid = x < p.W && ly < p.y1 - p.y0;
       pid = ly * p.W + x;
@@ -1757,7 +1766,9 @@ __device__ __forceinline__ void shade_body(const PTParams& p, int bounce_rt, con
         red = xyz(ldnt(&p.wf.red[pid]));
         if (FOLD) finish_apply(p, pid, &red, &light);  // the previous bounce's verdicts (its wf_finish)
       }
-      if (hr.x < 0) {  // miss (:1084-1087)
+      if (kKeep && p.busy && hr.x < 0) {
+        // keep mode: `color`, `emission` and `albedo` already hold what the branch below would store
+      } else if (hr.x < 0) {  // miss (:1084-1087)
         light = add(light, mul(hdr_color(p, d), red));
         // (folded, null planes: a sample after the first of an spp draw, whose first-hit planes are sample 0's; the
         // unfolded instantiation keeps its code: launch_wavefront points such a sample's stores elsewhere)
@@ -1898,6 +1909,58 @@ __global__ void __launch_bounds__(256) PT_SHADE_ATTR wf_shade_counted(PTParams p
                                                                       int sample) {
   shade_body<FOLD, FOLD, LAST, true>(p, 0, nullptr, nullptr, list_out, counts_out, shadow_out, shadow_counts, cap,
                                      sample_counts, sample);
+}
+
+// ------------------------------------------------------- the busy-tile list ---
+// The bounce-0 shade's keep mode visits only the tiles that hold a primary hit (PTParams::busy). Block b looks at the
+// tile the bounce-0 shade's block b takes (p.wf.hit is the primary plane here, as for that shade) and leaves its name
+// in scratch[b], or -1 when every pixel of it misses. Every index comes from the launch geometry: b < ntiles.
+__global__ void __launch_bounds__(256) wf_busy_mark(PTParams p, int* __restrict__ scratch) {
+  const int ntx = (p.W + 15) / 16;
+  const int slot = p.tiles.cost ? p.tiles.perm_next[blockIdx.x] : (int)blockIdx.x;
+  const int tile = slot * p.tile_stride + p.tile_offset;
+  const int x = (tile % ntx) * 16 + (threadIdx.x & 15), ly = (tile / ntx) * 16 + (threadIdx.x >> 4);
+  const bool hit = x < p.W && ly < p.y1 - p.y0 && ldnt(&p.wf.hit[ly * p.W + x]).x >= 0;
+  const int any = __syncthreads_or(hit);
+  if (threadIdx.x == 0) scratch[blockIdx.x] = any ? slot : -1;
+}
+// One block packs the names that are not -1 to busy[1 ..], keeping their order, and writes their number to busy[0].
+// n names at most, so entry 1 + (names before this one) stays below 1 + n.
+__global__ void __launch_bounds__(1024) wf_busy_pack(const int* __restrict__ scratch, int n, int* __restrict__ busy) {
+  __shared__ int wsum[16];
+  __shared__ int base;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (threadIdx.x == 0) base = 0;
+  __syncthreads();
+  for (int c = 0; c < n; c += 1024) {
+    const int i = c + (int)threadIdx.x;
+    const int v = i < n ? scratch[i] : -1;
+    const unsigned long long m = __ballot(v >= 0);
+    if (lane == 0) wsum[w] = __popcll(m);
+    __syncthreads();
+    int off = base;
+    for (int k = 0; k < w; ++k) off += wsum[k];
+    if (v >= 0) busy[1 + off + __popcll(m & ((1ull << lane) - 1ull))] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int t = 0;
+      for (int k = 0; k < 16; ++k) t += wsum[k];
+      base += t;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) busy[0] = base;
+}
+
+int launch_busy_tiles(const PTParams& p, int* busy, hipStream_t s) {
+  const int ntiles = wf_subset_tiles(p.W, std::max(0, p.y1 - p.y0), p.tile_stride, p.tile_offset);
+  if (ntiles <= 0 || !busy || !p.wf.hit0) return (int)hipErrorInvalidValue;
+  PTParams f = p;
+  f.wf.hit = f.wf.hit0;
+  int* scratch = busy + 1 + ntiles;
+  hipLaunchKernelGGL(wf_busy_mark, dim3(ntiles), dim3(256), 0, s, f, scratch);
+  hipLaunchKernelGGL(wf_busy_pack, dim3(1), dim3(1024), 0, s, (const int*)scratch, ntiles, busy);
+  return (int)hipGetLastError();
 }
 
 // ----------------------------------------------------------------- finish ---
@@ -2342,6 +2405,10 @@ int launch_wavefront(const PTParams* ps, int nb, hipStream_t s, const WfFork* fk
     for (int b = 0; b < nb; ++b) {
       PTParams shared = ps[b];
       shared.point_cache = (i == 0 || (i == 1 && fold)) ? pc_mode : (int)kPcOff;
+      // keep mode is the bounce-0 shade's alone, under the verdict cache's conditions (capi.hip first_hit_mode_for);
+      // the first-hit planes go null with it, so the hit pixels' stores into them fall away as a later sample's do
+      shared.busy = (i == 0 && nb == 1 && !rs && !DEEP && fold) ? p.busy : nullptr;
+      if (shared.busy) shared.emission = shared.albedo = Plane{};
       if (i == 0) {
         // The bounce-0 shade reads the primary hit plane (above); sample b of an spp draw reads sample 0's (and, the
         // samples being copies of one pass, its tiles.perm_next). No launch of this draw after the stage writes hit0:

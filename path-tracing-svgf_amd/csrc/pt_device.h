@@ -320,7 +320,19 @@ struct PTParams {
   // the bounce-0 point-light verdict cache's mode for this launch (PointCacheMode, point_cache.h). launch_wavefront
   // hands it to the bounce-0 shade and to the launch that consumes bounce 0's verdicts; every other launch gets kPcOff.
   int point_cache;
+  // The bounce-0 shade's keep mode (DESIGN.md "Static view, part 4"), read by the folded bounce-0 instantiations
+  // alone: non-null when the host has proven (capi.hip first_hit_mode_for) that `color` already holds this draw's miss
+  // texels and `emission` / `albedo` this draw's first-hit texels. A miss pixel then does nothing, launch_wavefront
+  // passes both first-hit planes null, and block b shades tile busy[1 + b] of the pass's busy-tile list (the tiles of
+  // the bounce-0 order that hold a primary hit, in that order; busy[0]: how many), blocks past its length return.
+  const int* busy;
 };
+// The busy-tile list of a whole-frame draw whose primary hit plane (wf.hit0) is complete: busy[0] = the number of
+// tiles with a pixel whose hit0.x >= 0, busy[1 ..] those tiles as the bounce-0 shade names them (tiles.perm_next's
+// entry, or the block index without a tile order), in the shade's order. busy: 2 * ntiles + 1 ints, the upper ntiles
+// scratch. Two launches on s.
+int launch_busy_tiles(const PTParams& p, int* busy, hipStream_t s);
+inline size_t busy_tiles_ints(int ntiles) { return 2 * (size_t)ntiles + 1; }
 
 struct GBufParams {
   int W, H, y0, y1;

@@ -265,4 +265,58 @@ inline uint64_t quiet_set_for(QuietChoice& c, uint64_t prim, uint64_t gbuf, uint
   return c.set;
 }
 
+// ------------------------------------------------ the bounce-0 shade's keep mode ---
+// DESIGN.md "Static view, part 4". On a standing view the bounce-0 shade stores, on every miss pixel, the colour,
+// emission and albedo texels the planes already hold, and on every hit pixel the emission and albedo texels they
+// already hold. A draw leaves those stores out (and does not visit all-miss tiles) only where the host has proven it.
+//
+// The key of a pixel's emission and albedo texels: which pixels hit what and where (the primary content), and what
+// decode_hit reads on the way to Material::emissive and ::baseColor beyond tri_geom, which the primary content covers:
+// the tri_shade records, and the texture array a negative baseColor is fetched from. use_normal_map, the metallic and
+// roughness layers' results and frameCounter reach neither.
+enum FirstHitKeyField {
+  kFkPrimary0,                              // primary_content() of the draw's PrimaryKey
+  kFkTriShade = kFkPrimary0 + kPkWords,     // SceneDev::tri_shade, and the version of the texture it was decoded from
+  kFkTriShadeVer,
+  kFkMatHandle, kFkMatDev, kFkMatVer,       // material_array: handle, device pointer, Texture::version
+  kFkMatW, kFkMatH, kFkMatLayers,           // and its size
+  kFkWords
+};
+struct FirstHitKey {
+  uint64_t w[kFkWords];
+};
+inline int first_hit_key_diff(const FirstHitKey& a, const FirstHitKey& b) {
+  for (int i = 0; i < kFkWords; ++i)
+    if (a.w[i] != b.w[i]) return i;
+  return -1;
+}
+
+// FirstHitMode / FirstHitReason: include/ptsvgf_debug_firsthit.h's PT_FH_* values.
+enum FirstHitMode { kFhOff = 0, kFhFull = 1, kFhKeep = 2 };
+enum FirstHitReason {
+  kFhrNone, kFhrUniform, kFhrEnv, kFhrStats, kFhrSpp, kFhrBatch, kFhrMegakernel, kFhrTiles, kFhrRows, kFhrDeep,
+  kFhrUnfolded, kFhrDepth0, kFhrAccumulate,  // bypasses: mode off; bit (1 << reason) of `bypass` below
+  kFhrStage, kFhrColour, kFhrEmission, kFhrAlbedo,  // full: the stage ran, or an attachment does not hold this content
+  kFhrCount
+};
+// The mode of a draw. bypass: bit r set when bypass reason r holds (the lowest one is reported). stage_reused: the
+// draw reads the cached primary hit. colour: the colour attachment's background stamp as the draw finds it, before
+// its own att_plane renews it; emission, albedo: the attachments' first-hit records as the draw finds them (0: none).
+// miss, first: the content ids of the draw's MissKey and FirstHitKey. A draw that is not bypassed qualifies: kept or
+// not, it leaves the three attachments holding its contents and records that after a successful launch.
+inline int first_hit_mode(uint32_t bypass, bool stage_reused, const BgStamp& colour, uint64_t emission,
+                          uint64_t albedo, uint64_t miss, uint64_t first, int* reason) {
+  for (int r = kFhrUniform; r <= kFhrAccumulate; ++r)
+    if (bypass & (1u << r)) {
+      *reason = r;
+      return kFhOff;
+    }
+  *reason = !stage_reused ? kFhrStage
+            : !(miss && colour.id == miss && colour.scope == kBgWhole) ? kFhrColour
+            : !(first && emission == first) ? kFhrEmission
+            : !(first && albedo == first) ? kFhrAlbedo
+                                          : kFhrNone;
+  return *reason == kFhrNone ? kFhKeep : kFhFull;
+}
+
 }  // namespace ptk

@@ -198,6 +198,15 @@ _PT_SIGS = [
     ("pt_debug_bg_miss_key_diff", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
     ("pt_debug_bg_miss_key_id", C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64)]),
     ("pt_debug_bg_key_content", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    # include/ptsvgf_debug_firsthit.h
+    ("pt_debug_firsthit_last", C.c_int, [_u32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("pt_debug_firsthit_busy", C.c_int, [_u32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("pt_debug_firsthit_record", C.c_int, [_u32, C.POINTER(C.c_uint64)]),
+    ("pt_debug_firsthit_key_words", C.c_int, []),
+    ("pt_debug_firsthit_key_diff", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
+    ("pt_debug_firsthit_key_id", C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64)]),
+    ("pt_debug_firsthit_decide", C.c_int, [_u32, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                           C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 ]
 
 _PTS_SIGS = [

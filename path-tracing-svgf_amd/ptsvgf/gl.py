@@ -613,6 +613,20 @@ class RenderPass:
         check(pt().pt_debug_bg_counts(self._handle(), C.byref(mode), C.byref(reason), C.byref(skipped), C.byref(total)))
         return mode.value, reason.value, skipped.value, total.value
 
+    def first_hit_last(self):
+        """pt_debug_firsthit_last (DESIGN.md "Static view, part 4"): (mode, reason, kept) of this path-tracing pass:
+        its last draw's mode 0 off / 1 full / 2 keep and reason (include/ptsvgf_debug_firsthit.h), its kept draws."""
+        mode, reason, kept = C.c_int(), C.c_int(), C.c_uint64()
+        check(pt().pt_debug_firsthit_last(self._handle(), C.byref(mode), C.byref(reason), C.byref(kept)))
+        return mode.value, reason.value, kept.value
+
+    def first_hit_busy(self):
+        """pt_debug_firsthit_busy: (busy, tiles) of this path-tracing pass's busy-tile list, busy -1 when none stands.
+        Synchronises the device."""
+        busy, tiles = C.c_int(), C.c_int()
+        check(pt().pt_debug_firsthit_busy(self._handle(), C.byref(busy), C.byref(tiles)))
+        return busy.value, tiles.value
+
     def poke_primary_hit(self, x: int, y: int, tri: int, t: float) -> None:
         """pt_debug_bg_poke_hit0: make pixel (x, y) of this path-tracing pass's primary plane a hit of triangle tri."""
         check(pt().pt_debug_bg_poke_hit0(self._handle(), x, y, tri, t))

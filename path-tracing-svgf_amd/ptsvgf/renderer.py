@@ -358,6 +358,7 @@ class Renderer:
             own_planes = (self._draw_gbuffer and after_gbuffer is None and pt_source is None and halo is None
                           and tex_factory is None)
             p.set_uniform_int("reuse_static", 1 if own_planes else 0)
+            self._own_planes = own_planes and band is None  # (the path-tracing passes' reuse_static, _ensure_slots)
             # one copy of the triangles for every set: the sets of one view then have one G-buffer content, which
             # is what lets a quiet-tile set serve the frames of all of them
             if b > 0 and self._static_bg:
@@ -529,6 +530,9 @@ class Renderer:
             p.set_uniform_int("shadow_budget", VISIT_BUDGET)
             p.set_uniform_int("closest_budget", VISIT_BUDGET)
             p.set_uniform_int("trace_batch", self.B)
+            # reuse_static (DESIGN.md "Static view, part 4"): nothing but this slot's own draws writes its three outputs
+            # under the conditions of the G-buffer's; a standing view's bounce-0 shade then keeps what they hold
+            p.set_uniform_int("reuse_static", 1 if self._own_planes else 0)
             p.set_spp(self._spp)
             if self.adaptive is not None:
                 import torch
