@@ -1,7 +1,8 @@
 // capi.hip — implementation of include/ptsvgf.h: the GL-plumbing-shaped C ABI
 // (Utils/render_pass.h:82-182, Utils/shader.h:21-67, Utils/help_func.h:22-32)
 // over HIP device memory and the gfx950 kernels. The entry points of geometry that moves (builds, refits, raster binds,
-// poses) are in capi_geometry.hip; capi_state.h holds what the two share.
+// poses) are in capi_geometry.hip, those of lights that move in capi_lights.hip, and the static view's bookkeeping
+// (keys, caches, quiet-tile sets; the draws here call into it) in capi_static.hip; capi_state.h holds what they share.
 //
 // GL semantics kept:
 //  * RenderPass uniforms are set by name; an unknown name is silently ignored;
@@ -17,8 +18,6 @@
 
 #include "../../include/ptsvgf_debug_pointbins.h"
 #include "../../include/ptsvgf_debug_background.h"
-#include "../../include/ptsvgf_debug_firsthit.h"
-#include "../../include/ptsvgf_debug_static.h"
 #include "../../include/ptsvgf_scene.h"
 #include "capi_state.h"
 #include "glsl_builtins.h"
@@ -67,6 +66,45 @@ int refresh_host(Texture* t) {
   if (t->bytes) HIPCHK(hipMemcpy(t->host.data(), t->dev, t->bytes, hipMemcpyDeviceToHost));
   t->host_stale = false;
   return PT_OK;
+}
+
+// -------------------------------------------------------------- bindings ---
+const Uniform* U(Pass* p, const char* name, int type) {
+  auto it = p->uni.find(name);
+  if (it == p->uni.end()) return nullptr;
+  return it->second.type == type ? &it->second : nullptr;
+}
+int ui(Pass* p, const char* n, int def) {
+  auto it = p->uni.find(n);
+  if (it == p->uni.end()) return def;
+  if (it->second.type == 2 || it->second.type == 4) return it->second.i;
+  if (it->second.type == 3) return (int)it->second.u;
+  return def;
+}
+Texture* sampler(Pass* p, const char* name, uint32_t* handle) {
+  auto it = p->tex.find(name);
+  uint32_t h = it != p->tex.end() ? it->second : g.unit0;
+  if (handle) *handle = h;
+  return tex_of(h);
+}
+
+// pt_set_band holds a partition of W x H frames: a band or stored rows that are not the whole frame
+bool band_partition(int W, int H) {
+  return g.band_h > 0 && W == g.band_w && H == g.band_h &&
+         (g.band_y0 != 0 || g.band_y1 != H || g.band_row0 != 0 || g.band_rows != H);
+}
+
+void rows_of(Pass* p, int* y0, int* y1) {
+  if (p->y_begin >= 0) {
+    *y0 = p->y_begin;
+    *y1 = p->y_end;
+  } else if (g.band_h > 0 && p->W == g.band_w && p->H == g.band_h) {
+    *y0 = g.band_y0;
+    *y1 = g.band_y1;
+  } else {
+    *y0 = 0;
+    *y1 = p->H;
+  }
 }
 
 }  // namespace ptapi
@@ -396,22 +434,9 @@ int get_scene(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU*
   return PT_OK;
 }
 
-// -------------------------------------------------------------- bindings ---
-const Uniform* U(Pass* p, const char* name, int type) {
-  auto it = p->uni.find(name);
-  if (it == p->uni.end()) return nullptr;
-  return it->second.type == type ? &it->second : nullptr;
-}
 float uf(Pass* p, const char* n, float def) {
   const Uniform* u = U(p, n, 1);
   return u ? u->f[0] : def;
-}
-int ui(Pass* p, const char* n, int def) {
-  auto it = p->uni.find(n);
-  if (it == p->uni.end()) return def;
-  if (it->second.type == 2 || it->second.type == 4) return it->second.i;
-  if (it->second.type == 3) return (int)it->second.u;
-  return def;
 }
 uint32_t uu(Pass* p, const char* n, uint32_t def) {
   auto it = p->uni.find(n);
@@ -425,12 +450,6 @@ uint32_t uu(Pass* p, const char* n, uint32_t def) {
 Texture* bound_sampler(Pass* p, const char* name) {
   auto it = p->tex.find(name);
   return it != p->tex.end() ? tex_of(it->second) : nullptr;
-}
-Texture* sampler(Pass* p, const char* name, uint32_t* handle = nullptr) {
-  auto it = p->tex.find(name);
-  uint32_t h = it != p->tex.end() ? it->second : g.unit0;
-  if (handle) *handle = h;
-  return tex_of(h);
 }
 
 int plane_of(Texture* t, Pass* p, Plane* out, const char* what) {
@@ -452,25 +471,6 @@ int att_plane(Pass* p, int k, Plane* out) {
   if (rc != PT_OK) return rc;
   tex_written(t);  // (a draw into it by any pass)
   return PT_OK;
-}
-
-// pt_set_band holds a partition of W x H frames: a band or stored rows that are not the whole frame
-bool band_partition(int W, int H) {
-  return g.band_h > 0 && W == g.band_w && H == g.band_h &&
-         (g.band_y0 != 0 || g.band_y1 != H || g.band_row0 != 0 || g.band_rows != H);
-}
-
-void rows_of(Pass* p, int* y0, int* y1) {
-  if (p->y_begin >= 0) {
-    *y0 = p->y_begin;
-    *y1 = p->y_end;
-  } else if (g.band_h > 0 && p->W == g.band_w && p->H == g.band_h) {
-    *y0 = g.band_y0;
-    *y1 = g.band_y1;
-  } else {
-    *y0 = 0;
-    *y1 = p->H;
-  }
 }
 
 // sobol (path_tracing.frag:480-495): a per-frame uniform value
@@ -819,56 +819,6 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
   return PT_OK;
 }
 
-// The key of what the primary stage of the draw `k` of pass p reads (static_key.h; k complete but for leaf_bins,
-// which is scratch): the view, the rows and tiles, the walk settings as the draw uses them, the scene and the trees
-// bound from it, the plane the stage writes and the tile order it sorts. Not in it: frameCounter (the stage does not
-// read it) and the G-buffer hint planes (the bound only prunes the walk; DESIGN.md "The primary's bound as one float").
-ptk::PrimaryKey primary_key(const Pass* p, const PTParams& k, const SceneGPU* sg, int pair_cap) {
-  using namespace ptk;
-  PrimaryKey q{};
-  for (int i = 0; i < 3; ++i) q.w[kPkEye0 + i] = key_bits(k.eye[i]);
-  for (int i = 0; i < 16; ++i) q.w[kPkCamRot0 + i] = key_bits(k.camRot[i]);
-  q.w[kPkW] = key_bits(k.W);
-  q.w[kPkH] = key_bits(k.H);
-  q.w[kPkY0] = key_bits(k.y0);
-  q.w[kPkY1] = key_bits(k.y1);
-  q.w[kPkBandW] = key_bits(g.band_w);
-  q.w[kPkBandH] = key_bits(g.band_h);
-  q.w[kPkBandY0] = key_bits(g.band_y0);
-  q.w[kPkBandY1] = key_bits(g.band_y1);
-  q.w[kPkBandRow0] = key_bits(g.band_row0);
-  q.w[kPkBandRows] = key_bits(g.band_rows);
-  q.w[kPkTileStride] = key_bits(k.tile_stride);
-  q.w[kPkTileOffset] = key_bits(k.tile_offset);
-  q.w[kPkAspectCorrected] = key_bits(k.aspect_corrected);
-  q.w[kPkPrune] = key_bits(k.prune);
-  q.w[kPkClosestTree] = key_bits(k.closest_tree);
-  q.w[kPkPrimaryRaster] = key_bits(k.primary_raster);
-  q.w[kPkScene] = key_bits((const void*)sg);
-  q.w[kPkTriVer] = sg->tri_ver;
-  q.w[kPkNodeVer] = sg->node_ver;
-  q.w[kPkNtris] = key_bits(sg->ntris);
-  q.w[kPkTriGeom] = key_bits((const void*)k.scene.tri_geom);
-  q.w[kPkBvh] = key_bits((const void*)k.scene.bvh);
-  q.w[kPkRootRef] = key_bits(k.scene.root_ref);
-  q.w[kPkBvhAny] = key_bits((const void*)k.scene.bvh_any);
-  q.w[kPkRootAny] = key_bits(k.scene.root_any);
-  q.w[kPkBvh4] = key_bits((const void*)k.scene.bvh4);
-  q.w[kPkRoot4] = key_bits(k.scene.root4);
-  q.w[kPkRoot4c] = key_bits(k.scene.root4c);
-  q.w[kPkLeaves] = key_bits((const void*)k.scene.leaves);
-  q.w[kPkNleaves] = key_bits(k.scene.nleaves);
-  q.w[kPkTriLeaf] = key_bits((const void*)k.scene.tri_leaf);
-  q.w[kPkStackNeed] = key_bits(k.stack_need);
-  q.w[kPkSpill] = key_bits((const void*)k.wf.spill);
-  q.w[kPkPairCap] = key_bits(pair_cap);
-  q.w[kPkPlane] = key_bits((const void*)k.wf.hit0);
-  q.w[kPkPlaneGen] = p->wf.gen;
-  q.w[kPkTileCost] = key_bits((const void*)k.tiles.cost);
-  q.w[kPkTilePerm] = key_bits((const void*)k.tiles.perm_next);
-  return q;
-}
-
 // The wavefront-side fields of a path-tracing pass's PTParams: its wavefront state `st` (its own, or its frame's
 // share of a batch's), counters, budgets, refill, cost-ordered tiles and the primary rasteriser's bins.
 // key / reuse (a draw of one pass: both, or neither): the primary-hit cache's key of this draw, and whether it may skip
@@ -912,202 +862,6 @@ int pt_wf_setup(Pass* p, PTParams& k, SceneGPU* sg, const WFState& st, ptk::Prim
     }
     if (pr) TRY(bins_for(p->bins, tri ? sg->ntris : sg->nleaves, k.W, k.y0, k.y1, pair_cap, &k.leaf_bins));
     return PT_OK;
-}
-
-// after the launch of a draw that pt_wf_setup gave a key: the cache's state and counts
-void primary_cache_note(Pass* p, const ptk::PrimaryKey& key, bool reused, bool ok) {
-  if (reused) {
-    if (ok) p->pcache.reuses++;
-    return;  // (a failed launch wrote nothing into hit0)
-  }
-  p->busy_valid = false;  // the busy-tile list is that of the stage before this one
-  p->pcache.valid = ok;
-  if (ok) {
-    p->pcache.key = key;
-    p->pcache.runs++;
-  }
-}
-
-// The bounce-0 point-light verdict cache of a one-sample wavefront draw (DESIGN.md "Static view, part 2"), after
-// pt_wf_setup: the cache's key of this draw (the primary key and what the bounce-0 shadow ray reads beyond it) and the
-// draw's mode, into k.point_cache. The draw's caller notes the outcome (ptk::point_cache_note).
-// *forgets: the draw uses the cache after forgetting the lights of *forget (the mask may be 0: a colour-only update).
-ptk::LightsKey point_cache_mode_for(Pass* p, PTParams& k, const ptk::PrimaryKey& pkey, bool stage_reused,
-                                    const DrawReads& reads, bool* forgets, uint32_t* forget) {
-  using namespace ptk;
-  LightsKey q{};
-  memcpy(q.w + kLkPrimary0, pkey.w, sizeof(pkey.w));
-  q.w[kLkLightHandle] = reads.light_handle;
-  q.w[kLkLightDev] = key_bits((const void*)k.scene.lights);
-  q.w[kLkLightVer] = reads.light_ver;
-  q.w[kLkPointLightSize] = key_bits(k.pointLightSize);
-  q.w[kLkNlightsBuf] = key_bits(k.scene.nlights_buf);
-  q.w[kLkPointBins] = key_bits(k.point_bins);
-  q.w[kLkPointBinsDev] = key_bits((const void*)(k.point_bins ? k.pbins.hdr : nullptr));
-  q.w[kLkPlane] = key_bits((const void*)k.wf.pcache);
-  // (the counters of shadow_point_rays must stay what they are when statistics are asked for; launch_wavefront
-  // engages the cache only where its shades are folded, `shade_fold && max_depth > 0`: a draw of no bounce launches
-  // no shade at all, so it must not count as the draw that reset the plane)
-  const bool fold = k.shade_fold && k.max_depth > 0;
-  const bool bypass = ui(p, "point_cache", 1) == 0 || p->stats || p->row_cost || k.pointLightSize < 1 ||
-                      k.pointLightSize > kPcLights || k.wf.spill || !fold;
-  // a lights buffer that pt_lights_update moved on forgets the moved lights' bits instead of resetting every word
-  // (lights_key.h); a texture without stamps (never updated) has no lights to name: it resets as ever
-  *forget = 0;
-  bool fg = false;
-  k.point_cache = point_cache_mode_lights(p->lcache, q, stage_reused, bypass, &fg);
-  if (fg && !reads.light_stamps) {
-    k.point_cache = kPcReset;
-    fg = false;
-  }
-  *forgets = fg;
-  if (fg) *forget = lights_moved_mask(reads.light_stamps, std::min(reads.light_count, (int)kPcLights),
-                                      p->lcache.key.w[kLkLightVer]);
-  return q;
-}
-
-// The static background (DESIGN.md "Static view, part 3"), after a one-sample wavefront draw of the whole frame without
-// accumulation: the colour attachment's miss texels are the content of the draw's MissKey (static_key.h), whichever
-// slot's plane this is; the texture also remembers the draw's primary content and whose hit0 holds its primary hits,
-// for the quiet-tile flags. Any other path-tracing draw leaves the stamp att_plane made: fresh.
-ptk::MissKey miss_key_of(const PTParams& k, const ptk::PrimaryKey& key, const DrawReads& reads);
-void bg_note_colour(Pass* p, const PTParams& k, const ptk::PrimaryKey& key, const DrawReads& reads) {
-  using namespace ptk;
-  Texture* ct = tex_of(p->att[0]);
-  if (!ct || k.accumulate || k.y0 != 0 || k.y1 != k.H || k.tile_stride != 1 || band_partition(k.W, k.H) ||
-      ct->row0 != 0 || ct->rows != k.H || !k.wf.hit0)
-    return;
-  const PrimaryKey pc = primary_content(key);
-  const MissKey m = miss_key_of(k, key, reads);
-  ct->bg = BgStamp{g.bg_miss.of(m.w, kMkWords, &g.bg_serial), kBgWhole};
-  ct->bg_prim = g.bg_prim.of(pc.w, kPkWords, &g.bg_serial);
-  ct->bg_pass = p;
-  ct->bg_pass_gen = p->wf.gen;
-}
-ptk::MissKey miss_key_of(const PTParams& k, const ptk::PrimaryKey& key, const DrawReads& reads) {
-  using namespace ptk;
-  const PrimaryKey pc = primary_content(key);
-  MissKey m{};
-  memcpy(m.w + kMkPrimary0, pc.w, sizeof(pc.w));
-  m.w[kMkHdrHandle] = reads.hdr_handle;
-  m.w[kMkHdrDev] = key_bits((const void*)k.hdr.p);
-  m.w[kMkHdrVer] = reads.hdr_ver;
-  m.w[kMkHdrW] = key_bits(k.hdr.W);
-  m.w[kMkHdrH] = key_bits(k.hdr.H);
-  m.w[kMkCacheHandle] = reads.cache_handle;
-  m.w[kMkCacheDev] = key_bits((const void*)k.cache.p);
-  m.w[kMkCacheVer] = reads.cache_ver;
-  m.w[kMkMerged] = k.hdr_pdf.p != nullptr;
-  m.w[kMkClamp] = key_bits(k.clamp_threshold);
-  m.w[kMkAccumulate] = key_bits(k.accumulate);
-  m.w[kMkMaxDepth] = key_bits(k.max_depth);
-  m.w[kMkShadeFold] = k.shade_fold;
-  m.w[kMkSpp] = 1;
-  return m;
-}
-
-// PTSVGF_STATIC_REUSE=0 in the environment forces every reuse_static off (A/B)
-bool reuse_static_env_off() {
-  static const bool env_off = [] {
-    const char* e = getenv("PTSVGF_STATIC_REUSE");
-    return e && atoi(e) == 0;
-  }();
-  return env_off;
-}
-
-// The bounce-0 shade's keep mode (DESIGN.md "Static view, part 4") of a one-sample wavefront draw.
-// What the three attachments say before the draw: read before pt_params, whose att_plane renews all of it.
-struct FirstHitBefore {
-  ptk::BgStamp colour;
-  uint64_t emission = 0, albedo = 0;
-};
-FirstHitBefore first_hit_before(Pass* p) {
-  FirstHitBefore b;
-  Texture* t[3] = {nullptr, nullptr, nullptr};
-  for (size_t i = 0; i < 3 && i < p->att.size(); ++i) t[i] = tex_of(p->att[i]);
-  if (t[0]) b.colour = t[0]->bg;
-  if (t[1]) b.emission = t[1]->first_hit;
-  if (t[2]) b.albedo = t[2]->first_hit;
-  return b;
-}
-// The pass's last draw was none that could keep: a sampled or batched draw, or the megakernel's.
-void first_hit_off(Pass* p, int reason) {
-  p->fh_mode = ptk::kFhOff;
-  p->fh_reason = reason;
-}
-// After pt_wf_setup: the draw's mode, and for a draw that is not bypassed the content id of its FirstHitKey in *first.
-// A kept draw gets k.busy, the pass's busy-tile list, built here on the draw's stream when the primary stage ran since
-// it was last built; in the verdict cache's reset mode the words of the pixels the kept draw does not visit are
-// cleared here instead (a fresh word is 0).
-int first_hit_mode_for(Pass* p, PTParams& k, const SceneGPU* sg, const ptk::PrimaryKey& key, bool stage_reused,
-                       const DrawReads& reads, const FirstHitBefore& before, uint64_t* first) {
-  using namespace ptk;
-  *first = 0;
-  uint32_t bypass = 0;
-  auto by = [&](bool c, int r) { if (c) bypass |= 1u << r; };
-  bool whole = k.y0 == 0 && k.y1 == k.H && !band_partition(k.W, k.H);
-  for (int i = 0; i < 3; ++i) {
-    const Texture* t = tex_of(p->att[i]);
-    whole = whole && t && t->row0 == 0 && t->rows == k.H;
-  }
-  by(ui(p, "reuse_static", 0) == 0, kFhrUniform);
-  by(reuse_static_env_off(), kFhrEnv);
-  by(p->stats || p->row_cost, kFhrStats);
-  by(k.tile_stride != 1, kFhrTiles);
-  by(!whole, kFhrRows);
-  by(k.wf.spill != nullptr, kFhrDeep);
-  by(!k.shade_fold, kFhrUnfolded);
-  by(k.max_depth <= 0, kFhrDepth0);
-  by(k.accumulate != 0, kFhrAccumulate);
-  uint64_t miss = 0;
-  if (!bypass) {
-    const MissKey m = miss_key_of(k, key, reads);
-    miss = g.bg_miss.of(m.w, kMkWords, &g.bg_serial);
-    const PrimaryKey pc = primary_content(key);
-    FirstHitKey f{};
-    memcpy(f.w + kFkPrimary0, pc.w, sizeof(pc.w));
-    f.w[kFkTriShade] = key_bits((const void*)k.scene.tri_shade);
-    f.w[kFkTriShadeVer] = sg->tri_ver;
-    uint32_t mh = 0;
-    const Texture* ma = sampler(p, "material_array", &mh);
-    if (k.scene.texarr && ma) {
-      f.w[kFkMatHandle] = mh;
-      f.w[kFkMatDev] = key_bits((const void*)k.scene.texarr);
-      f.w[kFkMatVer] = ma->version;
-      f.w[kFkMatW] = key_bits(k.scene.tex_w);
-      f.w[kFkMatH] = key_bits(k.scene.tex_h);
-      f.w[kFkMatLayers] = key_bits(k.scene.tex_layers);
-    }
-    *first = g.bg_first.of(f.w, kFkWords, &g.bg_serial);
-  }
-  p->fh_mode = first_hit_mode(bypass, stage_reused, before.colour, before.emission, before.albedo, miss, *first,
-                              &p->fh_reason);
-  if (p->fh_mode != kFhKeep) return PT_OK;
-  const int ntiles = wf_subset_tiles(k.W, k.H, 1, 0);
-  if (p->busy_n != ntiles) {
-    if (p->busy) (void)hipFree(p->busy);
-    p->busy = nullptr;
-    p->busy_n = 0;
-    p->busy_valid = false;
-    HIPCHK(hipMalloc((void**)&p->busy, busy_tiles_ints(ntiles) * sizeof(int)));
-    p->busy_n = ntiles;
-  }
-  if (!p->busy_valid) {
-    const int rc = launch_busy_tiles(k, p->busy, g.stream);
-    if (rc) return hip_err((hipError_t)rc, "busy-tile list");
-    p->busy_valid = true;
-  }
-  if (k.point_cache == kPcReset) HIPCHK(hipMemsetAsync(k.wf.pcache, 0, p->wf.n * sizeof(uint16_t), g.stream));
-  k.busy = p->busy;
-  return PT_OK;
-}
-// after the launch of a draw first_hit_mode_for gave a mode: a draw that was not bypassed has left emission and albedo
-// holding the content `first` (bg_note_colour stamps the colour); a failed one leaves what att_plane left: nothing
-void first_hit_note(Pass* p, uint64_t first, bool ok) {
-  if (!ok || p->fh_mode == ptk::kFhOff) return;
-  if (Texture* t = tex_of(p->att[1])) t->first_hit = first;
-  if (Texture* t = tex_of(p->att[2])) t->first_hit = first;
-  if (p->fh_mode == ptk::kFhKeep) p->fh_kept++;
 }
 
 // The side stream and events of path-tracing draws issued on `s` (uniform trace_fork = 1), created on first use: one
@@ -1192,8 +946,8 @@ int draw_pathtrace_spp(Pass* p, PTParams& k, SceneGPU* sg, int n) {
   int rc;
   const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
   if (rc) return rc;
-  p->lcache.valid = false;  // (the samples would share one verdict word: the cache is bypassed)
-  p->lcache_last_mode = 0;
+  // (the samples would share one verdict word: the cache is bypassed; sample 0's stage still serves the primary cache)
+  static_view_off(p, ptk::kFhrSpp, true);
   rc = launch_pathtrace_wavefront_spp(ks, rs, g.stream, fk, &ad, reuse);
   primary_cache_note(p, key, reuse, rc == 0);
   if (!rc && k.tiles.cost) p->order.ordered = true;
@@ -1211,11 +965,11 @@ int draw_pathtrace(Pass* p) {
   PTParams k;
   SceneGPU* sg = nullptr;
   DrawReads reads;
-  const FirstHitBefore before = first_hit_before(p);  // (pt_params' att_plane makes the attachments' stamps fresh)
+  StaticView sv;
+  sv.before(p);  // (pt_params' att_plane makes the attachments' stamps fresh)
   TRY(pt_params(p, k, sg, reads));
   int rc;
   if (spp > 1) {
-    first_hit_off(p, ptk::kFhrSpp);
     TRY(draw_pathtrace_spp(p, k, sg, spp));
     return note_reads(reads);
   }
@@ -1224,33 +978,19 @@ int draw_pathtrace(Pass* p) {
     if (k.stack_need >= kStack)
       return err(PT_ERR_ARG, "the megakernel (pt_kernel=1) walks a 32-entry LDS stack; this BVH is deeper: use the "
                              "wavefront path tracer (pt_kernel=0, the default)");
-    p->pcache.valid = false;  // (it sorts the pass's tile order by its own costs)
-    p->lcache.valid = false;
-    p->lcache_last_mode = 0;
-    first_hit_off(p, ptk::kFhrMegakernel);
+    static_view_off(p, ptk::kFhrMegakernel, false);  // (it sorts the pass's tile order by its own costs)
     rc = launch_pathtrace(k, g.stream);
   } else {                            // 0: wavefront (kernels_wavefront.hip), production
     TRY(wf_alloc(p->wf, k.W, std::max(0, k.y1 - k.y0)));
     if (wf_spill(p->wf, k.stack_need) != PT_OK) return err(PT_ERR_HIP, "spill stack allocation failed");
-    ptk::PrimaryKey key;
-    bool reuse = false;
-    TRY(pt_wf_setup(p, k, sg, p->wf.st, &key, &reuse));
+    TRY(pt_wf_setup(p, k, sg, p->wf.st, &sv.key, &sv.reuse));
     const ptk::WfFork* fk = wf_fork(p, g.stream, &rc);
     if (rc) return rc;
-    bool forgets = false;
-    uint32_t forget = 0;
-    const ptk::LightsKey lkey = point_cache_mode_for(p, k, key, reuse, reads, &forgets, &forget);
-    uint64_t first = 0;
-    TRY(first_hit_mode_for(p, k, sg, key, reuse, reads, before, &first));
-    rc = forget ? ptk::launch_point_cache_forget(k.wf.pcache, p->wf.n, forget, g.stream) : 0;
-    if (!rc) rc = launch_pathtrace_wavefront(k, g.stream, fk, reuse);
-    primary_cache_note(p, key, reuse, rc == 0);
-    first_hit_note(p, first, rc == 0);
-    ptk::point_cache_note_lights(p->lcache, lkey, k.point_cache, forgets, rc == 0);
-    p->lcache_last_mode = k.point_cache;
-    p->lcache_last_forgot = forget;
+    TRY(sv.setup(p, k, sg, reads));
+    rc = sv.forget ? ptk::launch_point_cache_forget(k.wf.pcache, p->wf.n, sv.forget, g.stream) : 0;
+    if (!rc) rc = launch_pathtrace_wavefront(k, g.stream, fk, sv.reuse);
+    sv.finish(p, k, reads, rc);
     if (!rc && k.tiles.cost) p->order.ordered = true;
-    if (!rc) bg_note_colour(p, k, key, reads);
   }
   if (rc) return hip_err((hipError_t)rc, "pathtrace launch");
   return note_reads(reads);
@@ -1295,11 +1035,7 @@ int draw_pathtrace_batch(Pass** ps, int n) {
   if (wf_spill(h->wf, k[0].stack_need) != PT_OK) return err(PT_ERR_HIP, "spill stack allocation failed");
   // A batch always runs the stage, into the head pass's planes, and sorts every pass's tile order: no pass keeps a key
   // that claims a plane or an order this draw changed. Each counts as a draw that ran the stage.
-  for (int b = 0; b < n; ++b) {
-    ps[b]->pcache.valid = ps[b]->lcache.valid = false;
-    ps[b]->lcache_last_mode = 0;
-    first_hit_off(ps[b], ptk::kFhrBatch);
-  }
+  for (int b = 0; b < n; ++b) static_view_off(ps[b], ptk::kFhrBatch, false);
   for (int b = 0; b < n; ++b) TRY(pt_wf_setup(ps[b], k[b], sg, h->wf.stb[b]));
   // the batched shadow launches read frame 0's point-light bins for every frame: frames that do not share them (other
   // lights, another pointLightSize) all walk
@@ -1349,76 +1085,6 @@ static int gbuf_flags(Pass* p, Texture* fwt, GBufParams& k) {
   }
   return PT_OK;
 }
-
-// The key of a draw of the rasterize pass p over the triangles of src (static_key.h), read from the state as it is
-// now: before a draw it is compared with the key taken after the pass's last completed draw. Returns false when an
-// attachment is missing (the draw then reports it).
-bool gbuf_key(Pass* p, const Pass* src, ptk::GbufKey* out) {
-  using namespace ptk;
-  GbufKey q{};
-  if (p->att.size() < 4) return false;
-  int y0, y1;
-  rows_of(p, &y0, &y1);
-  q.w[kGkW] = key_bits(p->W);
-  q.w[kGkH] = key_bits(p->H);
-  q.w[kGkY0] = key_bits(y0);
-  q.w[kGkY1] = key_bits(y1);
-  q.w[kGkBandW] = key_bits(g.band_w);
-  q.w[kGkBandH] = key_bits(g.band_h);
-  q.w[kGkBandY0] = key_bits(g.band_y0);
-  q.w[kGkBandY1] = key_bits(g.band_y1);
-  q.w[kGkBandRow0] = key_bits(g.band_row0);
-  q.w[kGkBandRows] = key_bits(g.band_rows);
-  for (int i = 0; i < 4; ++i) {
-    const Texture* t = tex_of(p->att[i]);
-    if (!t) return false;
-    q.w[kGkAtt0 + 4 * i] = p->att[i];
-    q.w[kGkAtt0 + 4 * i + 1] = key_bits((const void*)t->dev);
-    q.w[kGkAtt0 + 4 * i + 2] = t->version;
-    q.w[kGkAtt0 + 4 * i + 3] = t->raster_stamp;
-  }
-  const Texture *wt = tex_of(p->att[0]), *fwt = tex_of(p->att[3]);
-  q.w[kGkFwAux] = key_bits((const void*)fwt->aux);
-  q.w[kGkFwAuxValid] = fwt->aux_valid;
-  q.w[kGkBoundAux] = key_bits((const void*)wt->aux);
-  q.w[kGkBoundAuxValid] = wt->aux_valid;
-  for (int i = 0; i < 3; ++i) q.w[kGkAuxEye0 + i] = key_bits(wt->aux_eye[i]);
-  if (const Uniform* be = U(p, "bound_eye", 5)) {
-    q.w[kGkBoundEyeSet] = 1;
-    for (int i = 0; i < 3; ++i) q.w[kGkBoundEye0 + i] = key_bits(be->f[i]);
-  }
-  const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // (draw_raster's defaults)
-  const Uniform *uv = U(p, "view", 6), *up = U(p, "projection", 6), *upv = U(p, "pre_viewproj", 6);
-  for (int i = 0; i < 16; ++i) {
-    q.w[kGkView0 + i] = key_bits(uv ? uv->f[i] : I[i]);
-    q.w[kGkProj0 + i] = key_bits(up ? up->f[i] : I[i]);
-    q.w[kGkPreViewProj0 + i] = key_bits(upv ? upv->f[i] : I[i]);
-  }
-  const RasterScene& rs = src->raster;
-  const bool motion = rs.disp && rs.ntris > 0 && ui(p, "object_motion", 1) != 0;
-  q.w[kGkDisp] = key_bits((const void*)(motion ? rs.disp : nullptr));
-  q.w[kGkMode] = key_bits(ui(p, "gbuffer_mode", 1));
-  q.w[kGkPairCap] = key_bits(ui(p, "raster_pair_cap", 0));
-  q.w[kGkTileFlags] = key_bits(ui(p, "atrous_tile_flags", 1));
-  q.w[kGkTfRows0] = key_bits(ui(p, "atrous_rows_begin", -1));
-  q.w[kGkTfRows1] = key_bits(ui(p, "atrous_rows_end", -1));
-  q.w[kGkTflags] = key_bits((const void*)fwt->tflags);
-  q.w[kGkTflagsCap] = fwt->tflags_cap;
-  q.w[kGkTflagsVer] = fwt->tflags_ver;
-  q.w[kGkTflagsY0] = key_bits(fwt->tflags_y0);
-  q.w[kGkTflagsY1] = key_bits(fwt->tflags_y1);
-  q.w[kGkSource] = p->raster_src;
-  q.w[kGkSceneVer] = rs.version;
-  *out = q;
-  return true;
-}
-
-// reuse_static (int uniform of a rasterize pass, default 0): the caller states that nothing outside the library writes
-// this pass's attachments between its draws. PTSVGF_STATIC_REUSE=0 in the environment forces it off (A/B).
-bool reuse_static_on(Pass* p) {
-  return !reuse_static_env_off() && ui(p, "reuse_static", 0) != 0;
-}
-
 
 int draw_raster(Pass* p) {
   Pass* src = p->raster_src ? pass_of(p->raster_src) : p;
@@ -1528,132 +1194,6 @@ int draw_raster(Pass* p) {
   return PT_OK;
 }
 
-// ---- the static background of the SVGF chain (DESIGN.md "Static view, part 3"; static_key.h has the rules)
-// static_background (int uniform of a reproject, variance or a-trous pass, default 0): the caller states that nothing
-// outside the library writes the pass's textures. PTSVGF_STATIC_BACKGROUND=0 in the environment forces it off (A/B).
-bool bg_env_off() {
-  static const bool off = [] {
-    const char* e = getenv("PTSVGF_STATIC_BACKGROUND");
-    return e && atoi(e) == 0;
-  }();
-  return off;
-}
-bool bg_whole(const Texture* t, int H) { return t && t->row0 == 0 && t->rows == H; }
-QuietSet* bg_set_of(uint64_t id) {
-  if (id)
-    for (QuietSet& q : g.bg_sets)
-      if (q.id == id) return &q;
-  return nullptr;
-}
-// What bypasses every SVGF draw alike: the switch, the environment, a row subset or band.
-int bg_bypass(Pass* p, int y0, int y1) {
-  if (ui(p, "static_background", 0) == 0) return PT_BG_R_UNIFORM;
-  if (bg_env_off()) return PT_BG_R_ENV;
-  if (y0 != 0 || y1 != p->H || band_partition(p->W, p->H)) return PT_BG_R_ROWS;
-  return PT_BG_R_NONE;
-}
-// Builds set `id` for the colour plane ct and the depth-fwidth attachment ft of a W x H frame, on the draw's stream:
-// from ft's compact plane and the primary plane of the pass that wrote ct, if it still holds that draw's hits.
-int bg_build_set(uint64_t id, const Texture* ct, const Texture* ft, int W, int H, bool* built) {
-  *built = false;
-  Pass* pp = nullptr;
-  for (auto& kv : g.passes)
-    if (kv.second.get() == ct->bg_pass) pp = kv.second.get();
-  if (!pp || pp->wf.gen != ct->bg_pass_gen || !pp->pcache.valid || !pp->wf.st.hit0 || !ft->aux || !ft->aux_valid)
-    return PT_OK;
-  const ptk::PrimaryKey pc = ptk::primary_content(pp->pcache.key);
-  if (g.bg_prim.of(pc.w, ptk::kPkWords, &g.bg_serial) != ct->bg_prim) return PT_OK;
-  QuietSet& q = g.bg_sets[g.bg_next];
-  g.bg_next = (g.bg_next + 1) % kQuietSets;
-  // the oldest set's allocation is taken again: draws issued on this stream have read it by the time the build runs;
-  // draws on other streams are waited for (a set goes out of use kQuietSets views later, so this is rare)
-  if (q.flags && (q.mixed || q.last_stream != g.stream)) HIPCHK(hipDeviceSynchronize());
-  q.id = 0;
-  const size_t off16 = ptk::atrous_flag_bytes(W, 0, H), n16 = (size_t)((W + 15) / 16) * ((H + 15) / 16);
-  const size_t offc = (off16 + n16 + 3) / 4 * 4, need = offc + 6 * sizeof(uint32_t);
-  if (q.cap < need) {
-    if (q.flags) (void)hipFree(q.flags);
-    q.flags = nullptr;
-    q.cap = 0;
-    HIPCHK(hipMalloc((void**)&q.flags, need));
-    q.cap = need;
-  }
-  const int rc = ptk::launch_quiet_flags(ft->aux, ft->row0, pp->wf.st.hit0, W, H, q.flags, q.flags + off16,
-                                         (uint32_t*)(q.flags + offc), g.stream);
-  if (rc) return hip_err((hipError_t)rc, "quiet-tile flags");
-  q.id = id;
-  q.gbuf = ft->bg_gbuf;
-  q.W = W;
-  q.H = H;
-  q.off16 = off16;
-  q.off_counts = offc;
-  q.last_stream = g.stream;
-  q.mixed = false;
-  *built = true;
-  return PT_OK;
-}
-// One SVGF draw's decision. Before the draw's att_plane calls: begin() reads the stamps as the draw finds them; after
-// the launch: finish() stamps the outputs and records the mode.
-struct BgDraw {
-  int reason = PT_BG_R_NONE;
-  uint64_t set = 0;
-  QuietSet* qs = nullptr;
-  bool skip = false;
-  int npairs = 0;
-  Texture* out[2] = {nullptr, nullptr};
-  ptk::BgStamp in[2], was[2];
-  bool mod[2] = {false, false};
-  int in_off = 0;  // an input was written by a bypassed draw of the chain: its reason
-  void pair(const Texture* i, Texture* o, bool modulated) {
-    if (i && i->bg_off && !in_off) in_off = i->bg_off;
-    in[npairs] = i ? i->bg : ptk::BgStamp{};
-    was[npairs] = o ? o->bg : ptk::BgStamp{};
-    out[npairs] = o;
-    mod[npairs++] = modulated;
-  }
-  // the set is known (0: none): may the draw skip its tiles?
-  void decide() {
-    qs = bg_set_of(set);
-    if (!qs) set = 0;
-    if (!reason && in_off) reason = in_off;  // the chain was bypassed above this draw
-    if (reason) return;
-    if (!set) {
-      reason = PT_BG_R_NO_SET;
-      return;
-    }
-    skip = true;
-    for (int i = 0; i < npairs; ++i) skip = skip && ptk::bg_pair_quiet(in[i], was[i], set, mod[i]);
-    if (!skip) reason = PT_BG_R_STAMPS;
-  }
-  void finish(Pass* p, int shape, bool ok) {
-    const bool off = reason >= PT_BG_R_UNIFORM && reason <= PT_BG_R_NO_PLANE;
-    for (int i = 0; i < npairs; ++i)
-      if (out[i]) {
-        out[i]->bg = ptk::bg_copy(in[i], ok && !off ? set : 0, mod[i], &g.bg_serial);
-        out[i]->bg_off = off ? reason : 0;
-      }
-    if (qs && skip) {
-      qs->mixed = qs->mixed || qs->last_stream != g.stream;
-      qs->last_stream = g.stream;
-    }
-    p->bg_mode = off ? PT_BG_OFF : skip ? PT_BG_SKIP : PT_BG_ARMED;
-    p->bg_reason = reason;
-    p->bg_set = off ? 0 : set;
-    p->bg_shape = shape;
-  }
-};
-// The set of a variance or a-trous draw: the one its input's stamp holds for, provided it was built for the G-buffer
-// content of this draw's depth-fwidth attachment and the frame's size.
-uint64_t bg_set_from_input(const Texture* in, const Texture* ft, int W, int H) {
-  const QuietSet* q = in && in->bg.id ? bg_set_of(in->bg.scope) : nullptr;
-  return q && ft->bg_gbuf && q->gbuf == ft->bg_gbuf && q->W == W && q->H == H ? q->id : 0;
-}
-// gNormalAndLinearZ and gNormalDepthFwidth are attachments of one G-buffer draw, and the compact plane is there: the
-// kernels' background tests (nd.w == 1, the compact plane's sign) then agree with the flags' content
-bool bg_one_gbuffer(const Texture* nd, const Texture* ft) {
-  return nd && ft && ft->aux && ft->aux_valid && ft->raster_stamp != 0 && nd->raster_stamp == ft->raster_stamp;
-}
-
 int draw_svgf(Pass* p, int kind) {
   int y0, y1;
   rows_of(p, &y0, &y1);
@@ -1690,12 +1230,12 @@ int draw_svgf(Pass* p, int kind) {
     // that meets the pair; every other case forgets the pair, so no set outlives a bypass
     {
       const Texture *ct = sampler(p, "gColor"), *ft = sampler(p, "gNormalDepthFwidth");
-      if (!bg.reason && k.sm.p) bg.reason = PT_BG_R_SAMPLE_MOMENTS;
-      if (!bg.reason && !(bg_whole(ct, p->H) && bg_whole(ft, p->H) && bg_whole(bg.out[0], p->H) &&
-                          bg_whole(bg.out[1], p->H) && bg_whole(sampler(p, "gPrevMoments_HistoryLength"), p->H)))
-        bg.reason = PT_BG_R_ROWS;
-      if (!bg.reason && !bg_one_gbuffer(sampler(p, "gNormalAndLinearZ"), ft)) bg.reason = PT_BG_R_NO_PLANE;
-      if (!bg.reason && !(ct->bg_prim && ft->bg_gbuf)) bg.reason = PT_BG_R_NO_CONTENT;
+      bg.need(!k.sm.p, PT_BG_R_SAMPLE_MOMENTS);
+      bg.need(bg_whole(ct, p->H) && bg_whole(ft, p->H) && bg_whole(bg.out[0], p->H) && bg_whole(bg.out[1], p->H) &&
+                  bg_whole(sampler(p, "gPrevMoments_HistoryLength"), p->H),
+              PT_BG_R_ROWS);
+      bg.need(bg_one_gbuffer(sampler(p, "gNormalAndLinearZ"), ft), PT_BG_R_NO_PLANE);
+      bg.need(ct->bg_prim && ft->bg_gbuf, PT_BG_R_NO_CONTENT);
       bool build = false;
       // (a pass with the switch off takes no part: it leaves the choice to the passes that have it on)
       if (bg.reason != PT_BG_R_UNIFORM && bg.reason != PT_BG_R_ENV)
@@ -1730,10 +1270,9 @@ int draw_svgf(Pass* p, int kind) {
     if (Texture* sm = bound_sampler(p, "gSampleMoments")) TRY(plane_of(sm, p, &k.sm, "gSampleMoments"));
     {
       const Texture *it = sampler(p, "gIllumination"), *ft = sampler(p, "gNormalDepthFwidth");
-      if (!bg.reason && k.sm.p) bg.reason = PT_BG_R_SAMPLE_MOMENTS;
-      if (!bg.reason && !(bg_whole(it, p->H) && bg_whole(ft, p->H) && bg_whole(bg.out[0], p->H)))
-        bg.reason = PT_BG_R_ROWS;
-      if (!bg.reason && !bg_one_gbuffer(sampler(p, "gNormalAndLinearZ"), ft)) bg.reason = PT_BG_R_NO_PLANE;
+      bg.need(!k.sm.p, PT_BG_R_SAMPLE_MOMENTS);
+      bg.need(bg_whole(it, p->H) && bg_whole(ft, p->H) && bg_whole(bg.out[0], p->H), PT_BG_R_ROWS);
+      bg.need(bg_one_gbuffer(sampler(p, "gNormalAndLinearZ"), ft), PT_BG_R_NO_PLANE);
       if (!bg.reason) bg.set = bg_set_from_input(it, ft, k.W, k.H);
       bg.decide();
       if (bg.skip) k.busy16 = bg.qs->flags + bg.qs->off16;
@@ -1795,13 +1334,12 @@ int draw_svgf(Pass* p, int kind) {
       // production variant, a step of 1 .. 16, the compact plane), and only over whole-frame planes, which is also what
       // makes launch_atrous_fast choose it (same_geometry)
       const Texture *it = sampler(p, "gIllumination"), *ft = sampler(p, "gNormalDepthFwidth");
-      if (!bg.reason && !(bg_whole(it, p->H) && bg_whole(ft, p->H) && bg_whole(bg.out[0], p->H) &&
-                          (bg.npairs < 2 || bg_whole(bg.out[1], p->H)) &&
-                          bg_whole(sampler(p, "gNormalAndLinearZ"), p->H)))
-        bg.reason = PT_BG_R_ROWS;
-      if (!bg.reason && !k.fwidth.aux) bg.reason = PT_BG_R_NO_PLANE;
-      if (!bg.reason && !k.tile_any) bg.reason = PT_BG_R_KERNEL;
-      if (!bg.reason && !bg_one_gbuffer(sampler(p, "gNormalAndLinearZ"), ft)) bg.reason = PT_BG_R_NO_PLANE;
+      bg.need(bg_whole(it, p->H) && bg_whole(ft, p->H) && bg_whole(bg.out[0], p->H) &&
+                  (bg.npairs < 2 || bg_whole(bg.out[1], p->H)) && bg_whole(sampler(p, "gNormalAndLinearZ"), p->H),
+              PT_BG_R_ROWS);
+      bg.need(k.fwidth.aux, PT_BG_R_NO_PLANE);
+      bg.need(k.tile_any, PT_BG_R_KERNEL);
+      bg.need(bg_one_gbuffer(sampler(p, "gNormalAndLinearZ"), ft), PT_BG_R_NO_PLANE);
       if (!bg.reason) bg.set = bg_set_from_input(it, ft, k.W, k.H);
       bg.decide();
       if (bg.skip) k.busy = bg.qs->flags + ptk::atrous_flag_offset(si, k.W, 0, k.H);
@@ -2223,355 +1761,6 @@ int pt_debug_point_bins_overlap(const float* px, const float* py, int n, float f
   if (bw * bh <= 2) e.n = 0;  // (as pb_bin: a box of at most two cells keeps both)
   for (int cy = cy0; cy <= cy1; ++cy)
     for (int cx = cx0; cx <= cx1; ++cx) kept[(cy - cy0) * bw + (cx - cx0)] = ptk::pb_cell_kept(e, fw, cx, cy, R) ? 1 : 0;
-  return PT_OK;
-}
-
-int pt_debug_stage_counts(uint32_t pass, uint64_t* runs, uint64_t* reuses) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  const int kind = g.programs[p->program];
-  if (kind != PK_PATHTRACE && kind != PK_RASTER)
-    return err(PT_ERR_ARG, "pt_debug_stage_counts: a path-tracing or a rasterize pass");
-  if (runs) *runs = kind == PK_PATHTRACE ? p->pcache.runs : p->gcache.runs;
-  if (reuses) *reuses = kind == PK_PATHTRACE ? p->pcache.reuses : p->gcache.reuses;
-  return PT_OK;
-}
-
-int pt_debug_static_key_words(int kind) {
-  if (kind != 0 && kind != 1) return err(PT_ERR_ARG, "pt_debug_static_key_words: kind 0 (primary) or 1 (G-buffer)");
-  return kind == 0 ? (int)ptk::kPkWords : (int)ptk::kGkWords;
-}
-
-static int static_key_args(const char* who, int kind, const uint64_t* a, const uint64_t* b, int words,
-                           const void* out) {
-  if (kind != 0 && kind != 1) return err(PT_ERR_ARG, std::string(who) + ": kind 0 (primary) or 1 (G-buffer)");
-  if (!a || !b || !out) return err(PT_ERR_ARG, std::string(who) + ": null argument");
-  if (words != (kind == 0 ? (int)ptk::kPkWords : (int)ptk::kGkWords))
-    return err(PT_ERR_ARG, std::string(who) + ": not this kind's word count");
-  return PT_OK;
-}
-
-int pt_debug_static_key_diff(int kind, const uint64_t* a, const uint64_t* b, int words, int* field) {
-  TRY(static_key_args("pt_debug_static_key_diff", kind, a, b, words, field));
-  if (kind == 0) {
-    ptk::PrimaryKey ka, kb;
-    memcpy(ka.w, a, sizeof(ka.w));
-    memcpy(kb.w, b, sizeof(kb.w));
-    *field = ptk::primary_key_diff(ka, kb);
-  } else {
-    ptk::GbufKey ka, kb;
-    memcpy(ka.w, a, sizeof(ka.w));
-    memcpy(kb.w, b, sizeof(kb.w));
-    *field = ptk::gbuf_key_diff(ka, kb);
-  }
-  return PT_OK;
-}
-
-int pt_debug_static_key_hit(int kind, const uint64_t* last, int last_valid, const uint64_t* now, int words, int enabled,
-                            int* hit) {
-  TRY(static_key_args("pt_debug_static_key_hit", kind, last, now, words, hit));
-  if (kind == 0) {
-    ptk::PrimaryCache c;
-    ptk::PrimaryKey k;
-    memcpy(c.key.w, last, sizeof(c.key.w));
-    memcpy(k.w, now, sizeof(k.w));
-    c.valid = last_valid != 0;
-    *hit = ptk::primary_cache_hit(c, k, !enabled) ? 1 : 0;
-  } else {
-    ptk::GbufCache c;
-    ptk::GbufKey k;
-    memcpy(c.key.w, last, sizeof(c.key.w));
-    memcpy(k.w, now, sizeof(k.w));
-    c.valid = last_valid != 0;
-    *hit = ptk::gbuf_cache_hit(c, k, enabled != 0) ? 1 : 0;
-  }
-  return PT_OK;
-}
-
-// ---- the static background of the SVGF chain (DESIGN.md "Static view, part 3")
-int pt_debug_bg_counts(uint32_t pass, int* mode, int* reason, uint64_t* skipped, uint64_t* total) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (mode) *mode = p->bg_mode;
-  if (reason) *reason = p->bg_reason;
-  if (skipped) *skipped = 0;
-  if (total) *total = 0;
-  if (p->bg_mode == PT_BG_OFF) return PT_OK;
-  const int S = 1 << p->bg_shape, nx = ptk::atrous_tile_nx(S), tj = ptk::atrous_tile_tj(S);
-  const uint64_t n = p->bg_shape == 5 ? (uint64_t)((p->W + 15) / 16) * ((p->H + 15) / 16)
-                                      : (uint64_t)((p->W + 64 * nx - 1) / (64 * nx)) * ((p->H + S * tj - 1) / (S * tj)) * S;
-  if (total) *total = n;
-  const QuietSet* q = bg_set_of(p->bg_set);
-  if (p->bg_mode != PT_BG_SKIP || !q || !skipped) return PT_OK;
-  uint32_t busy[6];
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(busy, q->flags + q->off_counts, sizeof(busy), hipMemcpyDeviceToHost));
-  *skipped = n - busy[p->bg_shape];
-  return PT_OK;
-}
-
-int pt_debug_bg_stamp(uint32_t tex, uint64_t* id, uint64_t* scope) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  const Texture* t = tex_of(tex);
-  if (!t) return err(PT_ERR_INVALID_HANDLE, "invalid texture");
-  if (id) *id = t->bg.id;
-  if (scope) *scope = t->bg.scope;
-  return PT_OK;
-}
-
-int pt_debug_bg_poke_hit0(uint32_t pass, int x, int y, int tri, float t) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (g.programs[p->program] != PK_PATHTRACE || !p->wf.st.hit0)
-    return err(PT_ERR_STATE, "pt_debug_bg_poke_hit0: a path-tracing pass that has drawn with the wavefront path tracer");
-  if (x < 0 || x >= p->W || y < 0 || (size_t)y * p->W + x >= p->wf.n)
-    return err(PT_ERR_ARG, "pt_debug_bg_poke_hit0: pixel outside the rows the pass drew");
-  int2 v;
-  v.x = tri;
-  memcpy(&v.y, &t, sizeof(t));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(p->wf.st.hit0 + (size_t)y * p->W + x, &v, sizeof(v), hipMemcpyHostToDevice));
-  // the plane is no longer what the stage wrote: the busy-tile list and the first-hit records were derived from that
-  p->busy_valid = false;
-  for (size_t i = 1; i < 3 && i < p->att.size(); ++i)
-    if (Texture* at = tex_of(p->att[i])) at->first_hit = 0;
-  return PT_OK;
-}
-
-// ---- the bounce-0 shade's keep mode (DESIGN.md "Static view, part 4")
-int pt_debug_firsthit_last(uint32_t pass, int* mode, int* reason, uint64_t* kept) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (g.programs[p->program] != PK_PATHTRACE) return err(PT_ERR_ARG, "pt_debug_firsthit_last: a path-tracing pass");
-  if (mode) *mode = p->fh_mode;
-  if (reason) *reason = p->fh_reason;
-  if (kept) *kept = p->fh_kept;
-  return PT_OK;
-}
-
-int pt_debug_firsthit_busy(uint32_t pass, int* busy, int* tiles) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (g.programs[p->program] != PK_PATHTRACE) return err(PT_ERR_ARG, "pt_debug_firsthit_busy: a path-tracing pass");
-  if (!busy || !tiles) return err(PT_ERR_ARG, "pt_debug_firsthit_busy: null argument");
-  *busy = -1;
-  *tiles = ptk::wf_subset_tiles(p->W, p->H, 1, 0);
-  if (!p->busy || !p->busy_valid) return PT_OK;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(busy, p->busy, sizeof(int), hipMemcpyDeviceToHost));
-  return PT_OK;
-}
-
-int pt_debug_firsthit_record(uint32_t tex, uint64_t* id) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  const Texture* t = tex_of(tex);
-  if (!t) return err(PT_ERR_INVALID_HANDLE, "invalid texture");
-  if (!id) return err(PT_ERR_ARG, "pt_debug_firsthit_record: null argument");
-  *id = t->first_hit;
-  return PT_OK;
-}
-
-int pt_debug_firsthit_key_words(void) { return (int)ptk::kFkWords; }
-
-int pt_debug_firsthit_key_diff(const uint64_t* a, const uint64_t* b, int words, int* field) {
-  if (!a || !b || !field) return err(PT_ERR_ARG, "pt_debug_firsthit_key_diff: null argument");
-  if (words != (int)ptk::kFkWords) return err(PT_ERR_ARG, "pt_debug_firsthit_key_diff: not the key's word count");
-  ptk::FirstHitKey ka, kb;
-  memcpy(ka.w, a, sizeof(ka.w));
-  memcpy(kb.w, b, sizeof(kb.w));
-  *field = ptk::first_hit_key_diff(ka, kb);
-  return PT_OK;
-}
-
-int pt_debug_firsthit_key_id(const uint64_t* key, int words, uint64_t* id) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  if (!key || !id) return err(PT_ERR_ARG, "pt_debug_firsthit_key_id: null argument");
-  if (words != (int)ptk::kFkWords) return err(PT_ERR_ARG, "pt_debug_firsthit_key_id: not the key's word count");
-  *id = g.bg_first.of(key, words, &g.bg_serial);
-  return PT_OK;
-}
-
-int pt_debug_firsthit_decide(uint32_t bypass, int stage_reused, uint64_t colour_id, uint64_t colour_scope,
-                             uint64_t emission, uint64_t albedo, uint64_t miss, uint64_t first, int* mode, int* reason) {
-  if (!mode || !reason) return err(PT_ERR_ARG, "pt_debug_firsthit_decide: null argument");
-  *mode = ptk::first_hit_mode(bypass, stage_reused != 0, ptk::BgStamp{colour_id, colour_scope}, emission, albedo, miss,
-                              first, reason);
-  return PT_OK;
-}
-
-int pt_debug_bg_fresh(uint64_t* serial, uint64_t* id, uint64_t* scope) {
-  if (!serial || !id || !scope) return err(PT_ERR_ARG, "pt_debug_bg_fresh: null argument");
-  const ptk::BgStamp s = ptk::bg_fresh(serial);
-  *id = s.id;
-  *scope = s.scope;
-  return PT_OK;
-}
-
-int pt_debug_bg_copy(uint64_t in_id, uint64_t in_scope, uint64_t set, int modulated, uint64_t* serial, uint64_t* id,
-                     uint64_t* scope) {
-  if (!serial || !id || !scope) return err(PT_ERR_ARG, "pt_debug_bg_copy: null argument");
-  const ptk::BgStamp s = ptk::bg_copy(ptk::BgStamp{in_id, in_scope}, set, modulated != 0, serial);
-  *id = s.id;
-  *scope = s.scope;
-  return PT_OK;
-}
-
-int pt_debug_bg_pair_quiet(uint64_t in_id, uint64_t in_scope, uint64_t out_id, uint64_t out_scope, uint64_t set,
-                           int modulated, int* quiet) {
-  if (!quiet) return err(PT_ERR_ARG, "pt_debug_bg_pair_quiet: null argument");
-  *quiet = ptk::bg_pair_quiet(ptk::BgStamp{in_id, in_scope}, ptk::BgStamp{out_id, out_scope}, set, modulated != 0) ? 1 : 0;
-  return PT_OK;
-}
-
-int pt_debug_bg_quiet_set(uint64_t* state, uint64_t prim, uint64_t gbuf, uint64_t* serial, uint64_t* set, int* build) {
-  if (!state || !serial || !set || !build) return err(PT_ERR_ARG, "pt_debug_bg_quiet_set: null argument");
-  ptk::QuietChoice c;
-  c.prim = state[0];
-  c.gbuf = state[1];
-  c.set = state[2];
-  bool b = false;
-  *set = ptk::quiet_set_for(c, prim, gbuf, serial, &b);
-  *build = b ? 1 : 0;
-  state[0] = c.prim;
-  state[1] = c.gbuf;
-  state[2] = c.set;
-  return PT_OK;
-}
-
-int pt_debug_bg_miss_key_words(void) { return (int)ptk::kMkWords; }
-
-int pt_debug_bg_miss_key_diff(const uint64_t* a, const uint64_t* b, int words, int* field) {
-  if (!a || !b || !field) return err(PT_ERR_ARG, "pt_debug_bg_miss_key_diff: null argument");
-  if (words != (int)ptk::kMkWords) return err(PT_ERR_ARG, "pt_debug_bg_miss_key_diff: not the key's word count");
-  ptk::MissKey ka, kb;
-  memcpy(ka.w, a, sizeof(ka.w));
-  memcpy(kb.w, b, sizeof(kb.w));
-  *field = ptk::miss_key_diff(ka, kb);
-  return PT_OK;
-}
-
-int pt_debug_bg_miss_key_id(const uint64_t* key, int words, uint64_t* id) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  if (!key || !id) return err(PT_ERR_ARG, "pt_debug_bg_miss_key_id: null argument");
-  if (words != (int)ptk::kMkWords) return err(PT_ERR_ARG, "pt_debug_bg_miss_key_id: not the key's word count");
-  *id = g.bg_miss.of(key, words, &g.bg_serial);
-  return PT_OK;
-}
-
-int pt_debug_bg_key_content(int kind, const uint64_t* key, int words, uint64_t source, uint64_t* out) {
-  TRY(static_key_args("pt_debug_bg_key_content", kind, key, key, words, out));
-  if (kind == 0) {
-    ptk::PrimaryKey k;
-    memcpy(k.w, key, sizeof(k.w));
-    k = ptk::primary_content(k);
-    memcpy(out, k.w, sizeof(k.w));
-  } else {
-    ptk::GbufKey k;
-    memcpy(k.w, key, sizeof(k.w));
-    k = ptk::gbuf_content(k, source);
-    memcpy(out, k.w, sizeof(k.w));
-  }
-  return PT_OK;
-}
-
-// ---- the bounce-0 point-light verdict cache (DESIGN.md "Static view, part 2")
-static int point_cache_pass(const char* who, uint32_t pass, Pass** out) {
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (g.programs[p->program] != PK_PATHTRACE) return err(PT_ERR_ARG, std::string(who) + ": a path-tracing pass");
-  if (!p->wf.base) return err(PT_ERR_STATE, std::string(who) + ": the pass has not drawn with the wavefront path tracer");
-  *out = p;
-  return PT_OK;
-}
-
-int pt_debug_point_cache_counts(uint32_t pass, uint64_t* served, uint64_t* queued) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  Pass* p;
-  TRY(point_cache_pass("pt_debug_point_cache_counts", pass, &p));
-  HIPCHK(hipDeviceSynchronize());
-  int c[ptk::kWfCtr];  // bounce 0's counters of frame 0
-  HIPCHK(hipMemcpy(c, p->wf.st.counters, sizeof(c), hipMemcpyDeviceToHost));
-  uint64_t q = 0;
-  for (int i = 0; i < 8 * ptk::kPointBins; ++i) q += (uint64_t)c[ptk::kCtrPoint + i];
-  uint64_t sv = 0;
-  for (int i = 0; i < 8; ++i) sv += (uint64_t)c[ptk::kCtrPcServed + i];
-  if (served) *served = sv;
-  if (queued) *queued = q;
-  return PT_OK;
-}
-
-int pt_debug_point_cache_read(uint32_t pass, uint16_t* words, size_t n) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  Pass* p;
-  TRY(point_cache_pass("pt_debug_point_cache_read", pass, &p));
-  if (!words || n != p->wf.n) return err(PT_ERR_ARG, "pt_debug_point_cache_read: one word per pixel of the pass's rows");
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(words, p->wf.st.pcache, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-  return PT_OK;
-}
-
-int pt_debug_point_cache_write(uint32_t pass, const uint16_t* words, size_t n) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  Pass* p;
-  TRY(point_cache_pass("pt_debug_point_cache_write", pass, &p));
-  if (!words || n != p->wf.n) return err(PT_ERR_ARG, "pt_debug_point_cache_write: one word per pixel of the pass's rows");
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(p->wf.st.pcache, words, n * sizeof(uint16_t), hipMemcpyHostToDevice));
-  return PT_OK;
-}
-
-int pt_debug_point_cache_mode(uint32_t pass, int* mode, int* valid) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  Pass* p = pass_of(pass);
-  if (!p) return err(PT_ERR_INVALID_HANDLE, "invalid pass");
-  if (g.programs[p->program] != PK_PATHTRACE) return err(PT_ERR_ARG, "pt_debug_point_cache_mode: a path-tracing pass");
-  if (mode) *mode = p->lcache_last_mode;
-  if (valid) *valid = p->lcache.valid ? 1 : 0;
-  return PT_OK;
-}
-
-int pt_debug_point_cache_word(int op, uint32_t word, int arg, uint32_t* out) {
-  if (!out) return err(PT_ERR_ARG, "pt_debug_point_cache_word: null argument");
-  if ((op == 0 || op == 2) && (arg < 0 || arg >= ptk::kPcLights))
-    return err(PT_ERR_ARG, "pt_debug_point_cache_word: a light index in 0 .. 3");
-  switch (op) {
-    case 0: *out = (uint32_t)ptk::pc_lookup(word, arg); break;
-    case 1: *out = (uint32_t)ptk::pc_pending(word); break;
-    case 2: *out = ptk::pc_mark_pending(word, arg); break;
-    case 3: *out = ptk::pc_resolve(word, arg != 0); break;
-    case 5: *out = ptk::pc_forget(word, (uint32_t)arg); break;  // (4 stays no op: it has always been refused)
-    default: return err(PT_ERR_ARG, "pt_debug_point_cache_word: op 0 (look-up) .. 3 (resolve), 5 (forget)");
-  }
-  return PT_OK;
-}
-
-int pt_debug_point_cache_key_words(void) { return (int)ptk::kLkWords; }
-
-int pt_debug_point_cache_key_diff(const uint64_t* a, const uint64_t* b, int words, int* field) {
-  if (!a || !b || !field) return err(PT_ERR_ARG, "pt_debug_point_cache_key_diff: null argument");
-  if (words != (int)ptk::kLkWords) return err(PT_ERR_ARG, "pt_debug_point_cache_key_diff: not the key's word count");
-  ptk::LightsKey ka, kb;
-  memcpy(ka.w, a, sizeof(ka.w));
-  memcpy(kb.w, b, sizeof(kb.w));
-  *field = ptk::lights_key_diff(ka, kb);
-  return PT_OK;
-}
-
-int pt_debug_point_cache_key_mode(const uint64_t* last, int last_valid, const uint64_t* now, int words, int stage_reused,
-                                  int enabled, int* mode) {
-  if (!last || !now || !mode) return err(PT_ERR_ARG, "pt_debug_point_cache_key_mode: null argument");
-  if (words != (int)ptk::kLkWords) return err(PT_ERR_ARG, "pt_debug_point_cache_key_mode: not the key's word count");
-  ptk::PointCache c;
-  ptk::LightsKey k;
-  memcpy(c.key.w, last, sizeof(c.key.w));
-  memcpy(k.w, now, sizeof(k.w));
-  c.valid = last_valid != 0;
-  *mode = ptk::point_cache_mode(c, k, stage_reused != 0, !enabled);
   return PT_OK;
 }
 

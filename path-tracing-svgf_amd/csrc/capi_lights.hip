@@ -1,6 +1,7 @@
 // capi_lights.hip — point lights that move (DESIGN.md "Moving point lights"): pt_lights_update and the diagnostics of
-// include/ptsvgf_debug_lights.h. The per-light consequences are drawn where the draws are issued (capi.hip:
-// point_bins_for, point_cache_mode_for) from the position stamps kept here; the rules themselves are lights_key.h's.
+// include/ptsvgf_debug_lights.h. The per-light consequences are drawn where the draws are issued (capi.hip's
+// point_bins_for, capi_static.hip's point_cache_mode_for) from the position stamps kept here; the rules themselves are
+// lights_key.h's.
 #include "../../include/ptsvgf_debug_lights.h"
 #include "capi_state.h"
 
@@ -94,12 +95,10 @@ int pt_debug_lights_key_mode(const uint64_t* last, int last_valid, const uint64_
   if (!last || !now || !mode || !forget) return err(PT_ERR_ARG, "pt_debug_lights_key_mode: null argument");
   if (words != (int)ptk::kLkWords) return err(PT_ERR_ARG, "pt_debug_lights_key_mode: not the key's word count");
   ptk::PointCache c;
-  ptk::LightsKey k;
-  memcpy(c.key.w, last, sizeof(c.key.w));
-  memcpy(k.w, now, sizeof(k.w));
+  c.key = ptk::key_from<ptk::LightsKey>(last);
   c.valid = last_valid != 0;
   bool f = false;
-  *mode = ptk::point_cache_mode_lights(c, k, stage_reused != 0, !enabled, &f);
+  *mode = ptk::point_cache_mode_lights(c, ptk::key_from<ptk::LightsKey>(now), stage_reused != 0, !enabled, &f);
   *forget = f ? 1 : 0;
   return PT_OK;
 }

@@ -1,6 +1,7 @@
 // capi_state.h — the library state behind include/ptsvgf.h, shared by the translation units that implement it:
-// capi.hip (init, textures, passes, draws, the scene cache; it defines the state and the helpers declared here) and
-// capi_geometry.hip (geometry that moves: builds, refits, raster binds, poses). Internal: nothing here is part of the ABI.
+// capi.hip (init, textures, passes, draws, the scene cache; it defines the state and the helpers declared here),
+// capi_geometry.hip (geometry that moves: builds, refits, raster binds, poses), capi_lights.hip (point lights that
+// move) and capi_static.hip (the static view: keys, caches, quiet-tile sets). Internal: nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -454,6 +455,58 @@ inline void tex_written(Texture* t) {
 }
 int ensure_init();
 int refresh_host(Texture* t);
+// a pass's bindings: a uniform of `type` (null: not set as one), an int uniform or `def`, a sampler by name (texture
+// unit 0 when unbound), the rows its draws cover; whether pt_set_band holds a partition of W x H frames
+const Uniform* U(Pass* p, const char* name, int type);
+int ui(Pass* p, const char* n, int def);
+Texture* sampler(Pass* p, const char* name, uint32_t* handle = nullptr);
+void rows_of(Pass* p, int* y0, int* y1);
+bool band_partition(int W, int H);
+
+// ---- defined in capi_static.hip: the static view (DESIGN.md "Static view"), as the draws of capi.hip use it
+ptk::PrimaryKey primary_key(const Pass* p, const ptk::PTParams& k, const SceneGPU* sg, int pair_cap);
+bool gbuf_key(Pass* p, const Pass* src, ptk::GbufKey* out);
+bool reuse_static_on(Pass* p);
+void primary_cache_note(Pass* p, const ptk::PrimaryKey& key, bool reused, bool ok);
+// One one-sample wavefront draw's use of the primary-hit cache, the verdict cache and the keep mode, in three steps.
+struct StaticView {
+  ptk::BgStamp colour;  // before(): what the attachments say as the draw finds them
+  uint64_t emission = 0, albedo = 0;
+  ptk::PrimaryKey key;  // pt_wf_setup: the draw's key, and whether it reads the cached primary hit
+  bool reuse = false, forgets = false;
+  ptk::LightsKey lkey;  // setup(): the verdict cache's key; `forgets`: its plane first forgets the lights of `forget`
+  uint32_t forget = 0;
+  uint64_t first = 0;   // setup(): the content id of the draw's FirstHitKey
+  void before(Pass* p);  // before pt_params, whose att_plane renews the attachments' stamps
+  // after pt_wf_setup: the verdict cache's mode into k.point_cache, the keep mode and with it k.busy
+  int setup(Pass* p, ptk::PTParams& k, const SceneGPU* sg, const DrawReads& reads);
+  void finish(Pass* p, const ptk::PTParams& k, const DrawReads& reads, int rc);  // after the launch (rc 0: it succeeded)
+};
+// A path-tracing draw that uses none of it (sampled, batched, the megakernel's): the verdict cache is stale, the keep
+// mode off for `reason` (a FirstHitReason), and the primary-hit cache stale too unless the draw serves it
+void static_view_off(Pass* p, int reason, bool keep_primary);
+// One SVGF draw's decision. Before the draw's att_plane calls pair() reads the stamps as the draw finds them; need()
+// states what the draw requires, decide() whether it may skip its tiles; finish() stamps the outputs after the launch.
+struct BgDraw {
+  int reason = 0;  // PT_BG_R_NONE
+  uint64_t set = 0;
+  QuietSet* qs = nullptr;
+  bool skip = false;
+  int npairs = 0;
+  Texture* out[2] = {nullptr, nullptr};
+  ptk::BgStamp in[2], was[2];
+  bool mod[2] = {false, false};
+  int in_off = 0;  // an input was written by a bypassed draw of the chain: its reason
+  void pair(const Texture* i, Texture* o, bool modulated);
+  void need(bool cond, int r) { if (!reason && !cond) reason = r; }  // the first unmet condition is the reason
+  void decide();
+  void finish(Pass* p, int shape, bool ok);
+};
+int bg_bypass(Pass* p, int y0, int y1);
+bool bg_whole(const Texture* t, int H);
+bool bg_one_gbuffer(const Texture* nd, const Texture* ft);
+uint64_t bg_set_from_input(const Texture* in, const Texture* ft, int W, int H);
+int bg_build_set(uint64_t id, const Texture* ct, const Texture* ft, int W, int H, bool* built);
 
 // defined in capi_geometry.hip: what pt_shutdown and the destroy calls release of a texture, a pass, a pose
 void free_trees(Texture* t);

@@ -70,11 +70,7 @@ inline int light_bins_step(LightBinsState& s, uint64_t stamp, int settle) {
 // is the same whoever decides the ray, so the bins fields may change with the lights. Anything else: point_cache_mode.
 inline bool lights_key_forgettable(const LightsKey& last, const LightsKey& now) {
   if (!now.w[kLkLightHandle] || now.w[kLkLightVer] <= last.w[kLkLightVer]) return false;
-  for (int i = 0; i < kLkWords; ++i) {
-    if (i == kLkLightDev || i == kLkLightVer || i == kLkPointBins || i == kLkPointBinsDev) continue;
-    if (last.w[i] != now.w[i]) return false;
-  }
-  return true;
+  return key_diff(last, now, {kLkLightDev, kLkLightVer, kLkPointBins, kLkPointBinsDev}) < 0;
 }
 inline int point_cache_mode_lights(const PointCache& c, const LightsKey& now, bool stage_reused, bool bypass,
                                    bool* forget) {

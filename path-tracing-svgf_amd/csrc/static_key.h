@@ -1,14 +1,17 @@
 // static_key.h — the key of everything the path tracer's primary stage reads (DESIGN.md "Static view"). A pass keeps
 // the key of the last stage it ran; a draw whose key equals it reads the primary hit plane that stage wrote
 // (WFState::hit0) instead of running the stage again. Plain host C++ with no HIP type, so the CPU suite reaches the
-// compare through pt_debug_primary_key_diff.
+// compare through pt_debug_static_key_diff.
 //
 // A key is one 64-bit word per field: a pointer's address, an integer, or a float's bit pattern (so a NaN equals
 // itself, and -0 differs from +0, which costs one stage and is never wrong). The compare walks the words, so a field
-// cannot be left out of it; a new input of the stage is a new enumerator here and a line in capi.hip's primary_key().
+// cannot be left out of it (every kind of key below goes through the one loop, key_words_diff); a new input of the
+// stage is a new enumerator here and a line in capi_static.hip's primary_key().
 #pragma once
 #include <stdint.h>
 #include <string.h>
+
+#include <initializer_list>
 
 namespace ptk {
 
@@ -42,11 +45,34 @@ inline uint64_t key_bits(float v) {
 inline uint64_t key_bits(const void* p) { return (uint64_t)(uintptr_t)p; }
 inline uint64_t key_bits(int v) { return (uint64_t)(int64_t)v; }
 
-// the first field in which the keys differ, -1 when they are equal
-inline int primary_key_diff(const PrimaryKey& a, const PrimaryKey& b) {
-  for (int i = 0; i < kPkWords; ++i)
-    if (a.w[i] != b.w[i]) return i;
+// The compare of every kind of key: the first of the n words in which a and b differ, -1 when they are equal. The
+// fields of `skip` are not compared.
+inline int key_words_diff(const uint64_t* a, const uint64_t* b, int n, std::initializer_list<int> skip = {}) {
+  for (int i = 0; i < n; ++i) {
+    bool differs = a[i] != b[i];
+    for (int s : skip) differs = differs && s != i;
+    if (differs) return i;
+  }
   return -1;
+}
+// the first field in which two keys of one kind differ, -1 when they are equal
+template <class K>
+inline int key_diff(const K& a, const K& b, std::initializer_list<int> skip = {}) {
+  return key_words_diff(a.w, b.w, (int)(sizeof(a.w) / sizeof(a.w[0])), skip);
+}
+// a key from the words of one (the C ABI's form of a key)
+template <class K>
+inline K key_from(const uint64_t* w) {
+  K k;
+  memcpy(k.w, w, sizeof(k.w));
+  return k;
+}
+// a composite key (LightsKey, MissKey, FirstHitKey: their *Primary0 is word 0) with `head` in front, the rest 0
+template <class K>
+inline K key_headed(const PrimaryKey& head) {
+  K k{};
+  memcpy(k.w, head.w, sizeof(head.w));
+  return k;
 }
 
 // The primary-hit cache of a path-tracing pass: the key of the last stage that ran, whether hit0 still holds that
@@ -60,7 +86,7 @@ struct PrimaryCache {
 // May this draw skip the stage? `bypass`: trace statistics or a row-cost buffer are bound (the stage's counters must
 // stay what they are), or the uniform primary_cache is 0.
 inline bool primary_cache_hit(const PrimaryCache& c, const PrimaryKey& now, bool bypass) {
-  return !bypass && c.valid && primary_key_diff(c.key, now) < 0;
+  return !bypass && c.valid && key_diff(c.key, now) < 0;
 }
 
 // ------------------------------------------- the bounce-0 point-light verdicts ---
@@ -80,12 +106,6 @@ struct LightsKey {
   uint64_t w[kLkWords];
 };
 
-inline int lights_key_diff(const LightsKey& a, const LightsKey& b) {
-  for (int i = 0; i < kLkWords; ++i)
-    if (a.w[i] != b.w[i]) return i;
-  return -1;
-}
-
 // The verdict cache of a path-tracing pass: the key of the draw that reset the plane, and whether the plane still
 // holds verdicts of that key (false: stale).
 struct PointCache {
@@ -100,7 +120,7 @@ struct PointCache {
 // a later draw under the reset draw's key uses it. A moving camera therefore never touches the plane.
 inline int point_cache_mode(const PointCache& c, const LightsKey& now, bool stage_reused, bool bypass) {
   if (bypass || !stage_reused) return 0;
-  return c.valid && lights_key_diff(c.key, now) < 0 ? 2 : 1;
+  return c.valid && key_diff(c.key, now) < 0 ? 2 : 1;
 }
 // after the draw's launch (ok: it succeeded)
 inline void point_cache_note(PointCache& c, const LightsKey& now, int mode, bool ok) {
@@ -142,12 +162,6 @@ struct GbufKey {
   uint64_t w[kGkWords];
 };
 
-inline int gbuf_key_diff(const GbufKey& a, const GbufKey& b) {
-  for (int i = 0; i < kGkWords; ++i)
-    if (a.w[i] != b.w[i]) return i;
-  return -1;
-}
-
 struct GbufCache {
   GbufKey key{};
   bool valid = false;  // key is that of a completed draw
@@ -161,7 +175,7 @@ struct GbufCache {
 inline bool gbuf_cache_hit(const GbufCache& c, const GbufKey& now, bool enabled) {
   const bool planes = now.w[kGkFwAux] && now.w[kGkFwAuxValid] &&
                       (!now.w[kGkBoundEyeSet] || (now.w[kGkBoundAux] && now.w[kGkBoundAuxValid]));
-  return enabled && c.valid && planes && gbuf_key_diff(c.key, now) < 0;
+  return enabled && c.valid && planes && key_diff(c.key, now) < 0;
 }
 
 // ------------------------------------------------ the static background of the SVGF chain ---
@@ -209,11 +223,6 @@ enum MissKeyField {
 struct MissKey {
   uint64_t w[kMkWords];
 };
-inline int miss_key_diff(const MissKey& a, const MissKey& b) {
-  for (int i = 0; i < kMkWords; ++i)
-    if (a.w[i] != b.w[i]) return i;
-  return -1;
-}
 
 // A texture's background stamp: "on the tiles of `scope` this texture holds content `id`". An id names a content, not
 // a texture: the miss colour of a MissKey, or whatever some texture held when something other than an SVGF copy wrote
@@ -285,11 +294,6 @@ enum FirstHitKeyField {
 struct FirstHitKey {
   uint64_t w[kFkWords];
 };
-inline int first_hit_key_diff(const FirstHitKey& a, const FirstHitKey& b) {
-  for (int i = 0; i < kFkWords; ++i)
-    if (a.w[i] != b.w[i]) return i;
-  return -1;
-}
 
 // FirstHitMode / FirstHitReason: include/ptsvgf_debug_firsthit.h's PT_FH_* values.
 enum FirstHitMode { kFhOff = 0, kFhFull = 1, kFhKeep = 2 };
