@@ -980,7 +980,7 @@ int draw_pathtrace(Pass* p) {
                              "wavefront path tracer (pt_kernel=0, the default)");
     static_view_off(p, ptk::kFhrMegakernel, false);  // (it sorts the pass's tile order by its own costs)
     rc = launch_pathtrace(k, g.stream);
-  } else {                            // 0: wavefront (kernels_wavefront.hip), production
+  } else {                            // 0: wavefront (kernels_wavefront.hip, kernels_wf_*.hip), production
     TRY(wf_alloc(p->wf, k.W, std::max(0, k.y1 - k.y0)));
     if (wf_spill(p->wf, k.stack_need) != PT_OK) return err(PT_ERR_HIP, "spill stack allocation failed");
     TRY(pt_wf_setup(p, k, sg, p->wf.st, &sv.key, &sv.reuse));

@@ -1,6 +1,6 @@
 // kernels_pointbins.hip — the build of the point-light triangle bins (PointBinsDev, pt_device.h): for every point
 // light a cube map of direction cells around it, each cell listing the triangles a shadow ray arriving at the light
-// from that cell's directions can hit. wf_shadow_point_bins (kernels_wavefront.hip) then decides a point-light shadow
+// from that cell's directions can hit. wf_shadow_point_bins (kernels_wf_trace.hip) then decides a point-light shadow
 // ray by testing its cell's list instead of walking a tree. Built once per scene and light set, on the device.
 //
 // What a cell must hold (DESIGN.md "Point-light shadow rays by light-binned triangles"). A ray (S, d) toward light L, d = normalize(L - S) rounded, can

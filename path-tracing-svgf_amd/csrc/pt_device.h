@@ -30,7 +30,7 @@ namespace ptk {
 
 // PT_WIDE_SIGNED = 1 (default since round 5): the 4-wide walks pick each child's near / far planes by the ray's
 // direction signs (which float4 is loaded) instead of slab's 6 min / max per child (pt_shading.h wide_step): 99 -> 92
-// VALU per shadow node step in the ISA. Same bits. With the traversal kernels at 7 waves per SIMD (kernels_wavefront.hip
+// VALU per shadow node step in the ISA. Same bits. With the traversal kernels at 7 waves per SIMD (wf_common.h
 // PT_TRACE_WAVES_PER_EU), same box, two alternating repetitions (profiles/r05/wide_signed/): 4K 222.5 / 222.4 ->
 // 225.3 / 225.2 fps, surface view 73.9 / 74.0 -> 78.1 / 78.0 (at 8 waves it spills 40-44 B per lane: 223.0, 77.1;
 // at 6: 223.0, 76.6)
@@ -114,7 +114,7 @@ struct SceneDev {
   const int* tri_leaf;
 };
 
-// Wavefront path-tracer state (kernels_wavefront.hip): SoA per band pixel.
+// Wavefront path-tracer state (kernels_wavefront.hip and its stages, kernels_wf_*.hip): SoA per band pixel.
 struct WFState {
   float4 *ray_o, *ray_d;        // current ray (origin, direction)
   float4 *light, *red;          // radiance accumulator, path throughput ("reduction")
@@ -289,7 +289,7 @@ struct PTParams {
   int prune;            // closest-hit pruning (parity-safe margin)
   int closest_tree;     // closest-hit rays walk the SAH tree over the reference leaves (closest_hit, pt_shading.h)
   int stack_need;       // deepest interior level of the binary BVH (selects the LDS stack size)
-  int refill;           // > 0: percent of each bounce/shadow list traced by lane-refill waves (kernels_wavefront.hip)
+  int refill;           // > 0: percent of each bounce/shadow list traced by lane-refill waves (kernels_wf_trace.hip)
   int refill_waves;     // resident waves a refill launch is sized for (0: the whole chip, kResidentWaves)
   int refill_grid;      // most blocks of a refill launch (uniform refill_grid; 0: PTSVGF_REFILL_GRID / its default)
   int list_grid;        // most blocks of the list-driven shade / finish (uniform list_grid; 0: PTSVGF_LIST_BLOCKS)
@@ -321,10 +321,11 @@ struct PTParams {
   // hands it to the bounce-0 shade and to the launch that consumes bounce 0's verdicts; every other launch gets kPcOff.
   int point_cache;
   // The bounce-0 shade's keep mode (DESIGN.md "Static view, part 4"), read by the folded bounce-0 instantiations
-  // alone: non-null when the host has proven (capi.hip first_hit_mode_for) that `color` already holds this draw's miss
-  // texels and `emission` / `albedo` this draw's first-hit texels. A miss pixel then does nothing, launch_wavefront
-  // passes both first-hit planes null, and block b shades tile busy[1 + b] of the pass's busy-tile list (the tiles of
-  // the bounce-0 order that hold a primary hit, in that order; busy[0]: how many), blocks past its length return.
+  // alone: non-null when the host has proven (capi_static.hip first_hit_mode_for) that `color` already holds this
+  // draw's miss texels and `emission` / `albedo` this draw's first-hit texels. A miss pixel then does nothing,
+  // launch_wavefront passes both first-hit planes null, and block b shades tile busy[1 + b] of the pass's busy-tile
+  // list (the tiles of the bounce-0 order that hold a primary hit, in that order; busy[0]: how many), blocks past its
+  // length return.
   const int* busy;
 };
 // The busy-tile list of a whole-frame draw whose primary hit plane (wf.hit0) is complete: busy[0] = the number of
@@ -339,7 +340,7 @@ struct GBufParams {
   Plane world, normal_depth, motion, fwidth;
   float* fwidth_aux;    // compact depth-fwidth plane (rows of fwidth), may be null
   // compact primary-ray bound plane (rows of world), may be null: per pixel the float the path tracer's primary
-  // rasterisers prune with (raster_bound, kernels_wavefront.hip), for primary rays that start at bound_eye
+  // rasterisers prune with (raster_bound, kernels_wf_primary.hip), for primary rays that start at bound_eye
   float* bound_aux;
   float bound_eye[3];
   unsigned char* tflags;  // a-trous per-tile surface flags (atrous_mark_tiles) of rows [tf_y0, tf_y1), may be null

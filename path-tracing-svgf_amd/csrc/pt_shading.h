@@ -1,5 +1,5 @@
 // pt_shading.h — device-side restatement of shaders/path_tracing.frag shared by
-// the megakernel (kernels_pt.hip) and the wavefront kernels (kernels_wavefront.hip):
+// the megakernel (kernels_pt.hip) and the wavefront kernels (kernels_wf_*.hip):
 // scene decode, hitAABB/hitTriangle, BVH traversal (closest / any-hit), the
 // Disney BRDF, its pdf and sampling, and the HDR environment lookups.
 // Header-only, included by .hip translation units built with -ffp-contract=off.

@@ -504,7 +504,7 @@ class Renderer:
             p.set_uniform_int("pointLightSize", scene.lights.shape[0])
             p.set_uniform_int("aspect_corrected", int(self.aspect_corrected))
             p.set_uniform_int("prune", int(self._pt_prune))
-            # lane-refill traversal waves: +8 % frames/s with frames in flight, -6 % serial (kernels_wavefront.hip)
+            # lane-refill traversal waves: +8 % frames/s with frames in flight, -6 % serial (kernels_wf_trace.hip)
             # share of each bounce / shadow list traced by lane-refill waves (frames in flight only); with up to 12
             # chunk rounds per wave 75 / 85 / 90 / 95 % measured 183.1 / 184.3 / 183.7 / 183.9 fps at 4K and 57.2 / 58.7 /
             # 59.5 / 60.6 fps on the surface view, 1080p and 8 bands within noise (tools/refill_pct_sweep.sh)
@@ -619,7 +619,7 @@ class Renderer:
 
     def _path_trace(self, hint=None):
         """hint: this frame's G-buffer set (drawn before on the same stream); its world position and normal/depth
-        planes bound the primary rays' walk (a result-preserving hint with no GL counterpart, kernels_wavefront.hip
+        planes bound the primary rays' walk (a result-preserving hint with no GL counterpart, kernels_wf_primary.hip
         wf_primary). The reference driver binds none, as main.cpp."""
         cam, cfg = self.camera, self.cfg
         view = cam.cam_view_mat

@@ -1,7 +1,8 @@
 """Adaptive sample counts (pt_pass_set_sample_counts / pt_pass_set_sample_stats / pt_sample_counts_derive,
-Renderer(spp=N, adaptive=tau); kernels_wavefront.hip wf_shade_counted, wf_spp_resolve_adaptive, spp_counts_kernel)
-against their definition (tests/adaptive_ref.py over spp_ref.py's per-sample colours of the CPU oracle). 160 x 96,
-test_gpu_spp.py's frames and scenes; every comparison is bitwise (uint32 views; counts as integers)."""
+Renderer(spp=N, adaptive=tau); kernels_wf_shade.hip wf_shade_counted, kernels_spp.hip wf_spp_resolve_adaptive and
+spp_counts_kernel) against their definition (tests/adaptive_ref.py over spp_ref.py's per-sample colours of the CPU
+oracle). 160 x 96, test_gpu_spp.py's frames and scenes; every comparison is bitwise (uint32 views; counts as
+integers)."""
 import numpy as np
 import pytest
 

@@ -1,4 +1,4 @@
-"""Pooled adaptive sample counts (pt_sample_counts_pool, Renderer(adaptive_pool=W); kernels_wavefront.hip
+"""Pooled adaptive sample counts (pt_sample_counts_pool, Renderer(adaptive_pool=W); kernels_spp.hip
 spp_pool_kernel) against their definition (tests/adaptive_pool_ref.py): the kernel on synthetic planes, every refusal,
 the closed loop over the renderer's own planes, the unchanged un-pooled path and the CLI flags. Comparisons are
 bitwise (uint32 views; two NaNs count as equal whatever their payloads; counts as integers)."""

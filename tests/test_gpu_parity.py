@@ -226,7 +226,7 @@ def test_closest_tree_is_result_preserving(gpu, scene_name, request):
 
 @pytest.mark.parametrize("scene_name", ["scene_small", "scene_nan"])
 def test_cooperative_shadow_walk_is_result_preserving(gpu, scene_name, request):
-    """Shadow rays past the step budget are finished by the wave-cooperative walk (kernels_wavefront.hip
+    """Shadow rays past the step budget are finished by the wave-cooperative walk (kernels_wf_trace.hip
     wf_shadow_coop): budgets 4 (nearly every ray, including LDS-stack overflows), 16 and 128 give the serial walk's
     bits (budget 0), from the one-ray-per-lane kernel and from the lane-refill kernel (trace_refill 75)."""
     gl = gpu
@@ -248,7 +248,7 @@ def test_cooperative_shadow_walk_is_result_preserving(gpu, scene_name, request):
 
 @pytest.mark.parametrize("scene_name", ["scene_small", "scene_cornell", "scene_nan"])
 def test_cooperative_closest_walk_is_result_preserving(gpu, scene_name, request):
-    """Bounce rays past the visit budget are finished by the wave-cooperative closest-hit walk (kernels_wavefront.hip
+    """Bounce rays past the visit budget are finished by the wave-cooperative closest-hit walk (kernels_wf_trace.hip
     wf_closest_coop, from the lane-refill kernel): budgets 2 (nearly every ray), 16 and 64 give the serial walk's
     bits, ray counts and tie re-walks."""
     gl = gpu

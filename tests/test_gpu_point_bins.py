@@ -1,5 +1,5 @@
 """Point-light shadow rays by the lights' triangle bins (pass uniform point_bins = 1: kernels_pointbins.hip's build,
-kernels_wavefront.hip wf_shadow_point_bins) against the tree walk (point_bins = 0, which test_gpu_parity.py and
+kernels_wf_trace.hip wf_shadow_point_bins) against the tree walk (point_bins = 0, which test_gpu_parity.py and
 test_gpu_fullsize.py pin to the oracle): the same verdict for the same ray, so the path tracer's planes must be
 bit-identical over every pixel, and the counters that do not say which path decided a ray must be equal."""
 import dataclasses

@@ -1,4 +1,4 @@
-"""Primary rays by tile-binned triangles (primary_raster = 2: kernels_wavefront.hip pr_tri_setup / wf_primary_tri)
+"""Primary rays by tile-binned triangles (primary_raster = 2: kernels_wf_primary.hip pr_tri_setup / wf_primary_tri)
 against the per-pixel walk (primary_raster = 0, wf_primary, which test_gpu_parity.py and test_gpu_fullsize.py pin
 to the oracle): the same closest hit of the same ray, so the path tracer's planes must be bit-identical over
 every pixel."""
@@ -133,7 +133,7 @@ GRAZE_PIXEL = (30, 40)
 
 
 def _primary_ray(cam, x, y):
-    """Eye and direction of pixel (x, y)'s primary ray (kernels_wavefront.hip primary_dir, aspect-corrected)."""
+    """Eye and direction of pixel (x, y)'s primary ray (wf_common.h primary_dir, aspect-corrected)."""
     from ptsvgf.camera import rigid_inverse
 
     m = rigid_inverse(cam.cam_view_mat).astype(np.float64)

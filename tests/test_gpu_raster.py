@@ -116,7 +116,7 @@ def test_primary_raster_equals_walk_bench_scene_1080p(gpu, scene_bench):
     print(st)
     _same(got, want, "bench1080")
     # every subset's pair list overflows: wf_primary walks all 8 160 tiles from its fix-up grid of a few hundred
-    # blocks striding over them (kernels_wavefront.hip primary_fix_blocks)
+    # blocks striding over them (kernels_wf_primary.hip launch_primary_stage)
     over, _ = _pt(gpu, scene_bench, W, H, 1, MOVES, cap=4)
     _same(over, want, "bench1080/overflow")
 

@@ -1,5 +1,5 @@
 """SVGF from sample moments on the GPU (pt_pass_set_sample_moments, sampler gSampleMoments, Renderer(spp=N,
-sample_moments=True); kernels_wavefront.hip wf_spp_resolve_adaptive<.., MOMENTS>, kernels_svgf.hip reproject_kernel<SM>
+sample_moments=True); kernels_spp.hip wf_spp_resolve_adaptive<.., MOMENTS>, kernels_svgf.hip reproject_kernel<SM>
 and variance_kernel<SM>) against its definition: tests/sample_moments_ref.cpp over spp_ref.py's per-sample colours of
 the CPU oracle and adaptive_ref.py's counts. 40 x 24 frames (partial 16 x 16 tiles; the variance pass's 3-texel apron
 crosses block edges), the scenes of test_gpu_spp.py; every comparison of the resolve, the reproject and the variance

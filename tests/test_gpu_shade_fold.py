@@ -1,5 +1,5 @@
 """Paths that end in place (uniform shade_fold = 1: no wf_finalize, no wf_finish between two shades, the shade
-specialised on first / last bounce; kernels_wavefront.hip) against the separate launches (shade_fold = 0), and the
+specialised on first / last bounce; kernels_wf_shade.hip) against the separate launches (shade_fold = 0), and the
 primary rasterisers' compact bound plane (written by the G-buffer draw; uniform bound_plane = 1) against their
 two-plane read (bound_plane = 0): the same statements in the same order, so the path tracer's planes must be
 bit-identical over every pixel and every frame."""
@@ -150,7 +150,7 @@ def test_one_ray_per_lane_kernels(gpu, scene_small):
 
 # ----------------------------------------------------------------- bound plane ---
 def _host_bound(world, nd, eye):
-    """raster_bound's statements (kernels_wavefront.hip) in float32 on the read-back texels."""
+    """raster_bound's statements (kernels_wf_primary.hip) in float32 on the read-back texels."""
     f = np.float32
     e = np.asarray(eye, f)
     with np.errstate(all="ignore"):

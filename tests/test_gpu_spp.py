@@ -1,7 +1,7 @@
 """Several samples per pixel in one path-tracing draw (int uniform spp = N, Renderer(spp=N): kernels_wavefront.hip
-launch_wavefront's sample draw and wf_spp_resolve) against its definition (tests/spp_ref.py, over the CPU oracle),
-against N one-sample draws of the GPU itself, and through every switch and draw geometry that must keep the bits.
-160 x 96, the camera states of test_gpu_shade_fold.py and one still frame after them (a move restarts the frame
+launch_wavefront's sample draw, kernels_spp.hip wf_spp_resolve) against its definition (tests/spp_ref.py, over the CPU
+oracle), against N one-sample draws of the GPU itself, and through every switch and draw geometry that must keep the
+bits. 160 x 96, the camera states of test_gpu_shade_fold.py and one still frame after them (a move restarts the frame
 counter, so only a still frame has F > 0); comparisons on uint32 views."""
 import numpy as np
 import pytest

@@ -8,6 +8,8 @@ every function symbol whose name contains the pattern, in name order: equal for 
 kernel's code changes.
 
 usage: python tools/kernel_hash.py LIB [PATTERN]   (default pattern: atrous_tile_kernel)
+       python tools/kernel_hash.py --list LIB [PATTERN]   one line per device function (default: all): name, size,
+                                                           sha256 of its bytes; diff two builds' listings
 """
 from __future__ import annotations
 
@@ -93,5 +95,17 @@ def kernel_code_hash(path: str, pattern: str = "atrous_tile_kernel") -> str | No
     return h.hexdigest()
 
 
+def kernel_listing(path: str, pattern: str = "") -> list[tuple[str, int, str]]:
+    """(name, size, sha256 of the instruction bytes) of every matching function, in name order."""
+    with open(path, "rb") as f:
+        lib = f.read()
+    funcs = sorted((n, c) for co in code_objects(lib) for n, c in _functions(co) if pattern in n)
+    return [(n, len(c), hashlib.sha256(c).hexdigest()) for n, c in funcs]
+
+
 if __name__ == "__main__":
+    if sys.argv[1] == "--list":  # one line per device function: two builds can be diffed function by function
+        for name, size, digest in kernel_listing(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else ""):
+            print(name, size, digest)
+        sys.exit(0)
     print(kernel_code_hash(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "atrous_tile_kernel"))
