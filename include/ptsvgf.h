@@ -150,6 +150,22 @@ int pt_texbuffer_create(const void* host_data, size_t bytes, uint32_t fmt, uint3
  * forgets that light alone. A colour-only change invalidates nothing. Same bits as a fresh buffer with these lights.
  * PT_ERR_INVALID_HANDLE: not a texture buffer; PT_ERR_ARG: null data, or a range outside the buffer. */
 int pt_lights_update(uint32_t lights_tex, int first, int count, const float* pos_rgb6);
+/* Material edits (DESIGN.md "Material edits"): the Triangle_encoded records of objects first_obj .. first_obj +
+ * count - 1 in the triangle buffer tri_tex take new materials; material18 holds `count` materials of
+ * PTS_MATERIAL_FLOATS (18) floats in ptsvgf_scene.h's order, object first_obj + k takes the k-th. A record belongs
+ * to object o when its objIndex (float 42) compares == (float)o; records of no named object keep their bits. Draws
+ * issued after the call render, bit for bit, what a library given a triangle buffer with floats 18 .. 35 of those
+ * records replaced would render; draws already enqueued, on any stream, read the materials they were enqueued with.
+ * The call does not wait for the device and, after the first few, does not allocate. The buffer's version does not
+ * advance: walk trees, point-light bins, the primary-hit and verdict caches and a pt_bvh_build pair stay valid; on a
+ * standing view each pass's next draw writes its emission and albedo planes in full once. A buffer no draw has
+ * decoded yet is no error. pose (0: none): a pt_pose_create handle made from this buffer, whose rest list is patched
+ * too; without it the next pt_pose_apply / pt_pose_apply_skin copies the old materials back. pt_bvh_refit copies
+ * whatever its tri_in holds: a caller that keeps a rest buffer of its own edits that one as well.
+ * PT_ERR_ARG: null material18, count outside [1, 4096], first_obj < 0 or first_obj + count > 2^24, a pose of another
+ * triangle count, a buffer that is not whole 45-float records; PT_ERR_INVALID_HANDLE: tri_tex is not a texture
+ * buffer, or the pose is unknown. Every check runs before anything is launched or changed. */
+int pt_materials_update(uint32_t tri_tex, uint32_t pose, int first_obj, int count, const float* material18);
 /* GPU BVH builder for dynamic scenes. The reference builds once on the host
  * (buildBVHwithSAH, Utils/BVH.h:42-173, main.cpp:88-96) and encodes triangles and nodes (main.cpp:101-151);
  * this builds a Karras LBVH on the device from the DEVICE contents of tri_in (Triangle_encoded texels, e.g.

@@ -244,7 +244,8 @@ void free_scene(SceneGPU& sg) {
   if (sg.pbins.sb.any()) (void)hipDeviceSynchronize();  // its readers may run on any stream
   free_point_bins(sg.pbins);
   drop_borrowed(sg);
-  float4** bufs[6] = {&sg.geom, &sg.shade, &sg.bvh, &sg.bvh4, &sg.bvh_any, &sg.leaves};
+  free_shade(sg);
+  float4** bufs[5] = {&sg.geom, &sg.bvh, &sg.bvh4, &sg.bvh_any, &sg.leaves};
   for (auto b : bufs) {
     if (*b) (void)hipFree(*b);
     *b = nullptr;
@@ -338,11 +339,15 @@ int get_scene_lbvh(Texture* tris, Texture* nodes, SceneGPU& sg, SceneGPU** out) 
   sg.need4 = t->dev_info[4];
   sg.fine_eye_limit = INFINITY;  // no fine boxes
   if (sg.geom) (void)hipFree(sg.geom);
-  if (sg.shade) (void)hipFree(sg.shade);
-  sg.geom = sg.shade = nullptr;
+  sg.geom = nullptr;
+  free_shade(sg);
+  const size_t shade_bytes = std::max<size_t>(ntris, 1) * 9 * sizeof(float4);
   HIPCHK(hipMalloc((void**)&sg.geom, std::max<size_t>(ntris, 1) * 4 * sizeof(float4)));
-  HIPCHK(hipMalloc((void**)&sg.shade, std::max<size_t>(ntris, 1) * 9 * sizeof(float4)));
-  HIPCHK((hipError_t)ptk::decode_tris((const float*)tris->dev, (int)ntris, sg.geom, sg.shade, g.stream));
+  HIPCHK(hipMalloc(&sg.shade.buf, shade_bytes));
+  sg.shade.bytes = shade_bytes;
+  TRY(materials_order(g.stream));  // the texels as every pt_materials_update so far left them
+  HIPCHK((hipError_t)ptk::decode_tris((const float*)tris->dev, (int)ntris, sg.geom, (float4*)sg.shade.buf, g.stream));
+  HIPCHK(sg.shade.mark_built(g.stream));  // for a pt_materials_update that follows: draws do not wait for it
   if (const int rc = build_tri_leaf(sg, (int)ntris)) return rc;
   sg.root_ref = root;
   sg.ntris = (int)ntris;
@@ -423,7 +428,13 @@ int get_scene(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU*
   if ((rc = upload_leaves((const float*)nodes->host.data(), nnodes, sg)) != PT_OK) return rc;
   if ((rc = build_tri_leaf(sg, (int)ntris)) != PT_OK) return rc;
   if ((rc = upload_vec(geom, &sg.geom)) != PT_OK) return rc;
-  if ((rc = upload_vec(shade, &sg.shade)) != PT_OK) return rc;
+  free_shade(sg);
+  {
+    float4* sh = nullptr;
+    if ((rc = upload_vec(shade, &sh)) != PT_OK) return rc;
+    sg.shade.buf = sh;
+    sg.shade.bytes = shade.size() * sizeof(float4);
+  }
   if (bvh.empty()) bvh.push_back(Float4{0, 0, 0, 0});
   if ((rc = upload_vec(bvh, &sg.bvh)) != PT_OK) return rc;
   sg.root_ref = root;
@@ -688,7 +699,11 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
     return err(PT_ERR_MISSING_TEXTURE, "path_tracing needs the 'triangles' and 'nodes' texture buffers");
   TRY(get_scene(tt, th, nt, nh, &sg));
   k.scene.tri_geom = sg->geom;
-  k.scene.tri_shade = sg->shade;
+  k.scene.tri_shade = (const float4*)sg->shade.buf;
+  if (sg->shade_first) {  // pt_materials_update wrote it, on another stream; this version is read until noted
+    HIPCHK(sg->shade.wait_built(g.stream));
+    reads.shade = &sg->shade;
+  }
   k.scene.bvh = sg->bvh;
   k.scene.root_ref = sg->root_ref;
   k.stack_need = sg->stack_need;
@@ -904,6 +919,7 @@ int note_reads(const DrawReads& r) {
   if (r.pbins) HIPCHK(r.pbins->note_read(g.stream));
   if (r.hdr) HIPCHK(r.hdr->note_read(g.stream));
   if (r.lights) HIPCHK(r.lights->note_read(g.stream));
+  if (r.shade) HIPCHK(r.shade->note_read(g.stream));
   return PT_OK;
 }
 
@@ -1457,6 +1473,7 @@ int pt_shutdown(void) {
   for (auto& kv : g.passes) free_pass(kv.second.get());
   for (auto& kv : g.poses) free_pose(*kv.second);
   for (auto& kv : g.scenes) free_scene(kv.second);
+  free_materials();
   for (auto& kv : g.hdr_merged) free_hdr_merged(kv.second);
   g.hdr_merged.clear();
   for (QuietSet& q : g.bg_sets)
@@ -1497,7 +1514,10 @@ int pt_stream_release(void* s) {
   }
   // the stream's last reads of the merged environments and of the scenes' point-light bins: done before the entry goes
   for (auto& kv : g.hdr_merged) kv.second.sb.forget(st);
-  for (auto& kv : g.scenes) kv.second.pbins.sb.forget(st);
+  for (auto& kv : g.scenes) {
+    kv.second.pbins.sb.forget(st);
+    kv.second.shade.forget(st);
+  }
   for (auto& kv : g.textures)
     if (kv.second->lights) kv.second->lights->sb.forget(st);
   if (g.stream == st) g.stream = g.own;

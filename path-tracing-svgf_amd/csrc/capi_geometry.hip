@@ -263,6 +263,7 @@ int pose_apply_with(const char* who, Pose& ps, uint32_t tri_out, uint32_t node_o
     TRY(refit_pass(who, p));
     if (p->raster.ntris != ps.rtris) return err(PT_ERR_ARG, w + "the pose holds another raster triangle count");
   }
+  TRY(materials_order(g.stream));  // the rest list and tri_out as every pt_materials_update so far left them
   // displacement records: the pass's own are rewritten where they lie, else the pair a pose without motion set aside
   float4* disp = nullptr;
   if (p && motion) {
@@ -342,6 +343,7 @@ int pt_bvh_build(uint32_t tri_in, int leaf_n, int ploc_radius, uint32_t tri_out,
   const size_t nt = ti->bytes / (45 * sizeof(float));
   if (nt > (1u << 24)) return err(PT_ERR_ARG, "pt_bvh_build: more than 2^24 triangles (float-encoded indices)");
   const int n = (int)nt;
+  TRY(materials_order(g.stream));  // tri_in is read and tri_out replaced after every pt_materials_update so far
   float *tbuf = nullptr, *nbuf = nullptr;
   HIPCHK(hipMalloc(&tbuf, nt * 45 * sizeof(float)));
   if (hipMalloc(&nbuf, (size_t)2 * n * 12 * sizeof(float)) != hipSuccess) {
@@ -388,6 +390,7 @@ int pt_bvh_refit(uint32_t tri_in, uint32_t tri_out, uint32_t node_out, float* ou
     return err(PT_ERR_ARG, "pt_bvh_refit: tri_in must hold whole Triangle_encoded records (45 floats)");
   if (ti->bytes != to->bytes) return err(PT_ERR_ARG, "pt_bvh_refit: tri_in holds another triangle count than the build");
   LbvhRefit* rf = no->refit;
+  TRY(materials_order(g.stream));  // tri_in is read and tri_out overwritten after every pt_materials_update so far
   EventTimer timer(out_ms);
   timer.start(g.stream);
   // both buffers are written where they lie: no staging, no copy (the host mirrors turn lazy, refresh_host)
@@ -665,7 +668,8 @@ int pt_pose_create(uint32_t tri_rest, const float* raster_rest, size_t n_floats,
     if (e == hipSuccess) e = hipMalloc((void**)&ps->r_list[1], rbytes);
     if (e == hipSuccess) e = hipMalloc((void**)&ps->r_obj, (size_t)ps->rtris * sizeof(int));
   }
-  // on the library stream: tri_rest may have been written there
+  // on the library stream: tri_rest may have been written there (or, by pt_materials_update, on that call's stream)
+  if (e == hipSuccess && materials_order(g.stream) != PT_OK) e = hipErrorUnknown;
   if (e == hipSuccess) e = hipMemcpyAsync(ps->tri_rest, t->dev, t->bytes, hipMemcpyDeviceToDevice, g.stream);
   if (e == hipSuccess && ps->rtris) {
     e = hipMemcpyAsync(ps->r_rest, raster_rest, rbytes, hipMemcpyHostToDevice, g.stream);

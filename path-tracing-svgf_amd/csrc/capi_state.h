@@ -1,7 +1,8 @@
 // capi_state.h — the library state behind include/ptsvgf.h, shared by the translation units that implement it:
 // capi.hip (init, textures, passes, draws, the scene cache; it defines the state and the helpers declared here),
 // capi_geometry.hip (geometry that moves: builds, refits, raster binds, poses), capi_lights.hip (point lights that
-// move) and capi_static.hip (the static view: keys, caches, quiet-tile sets). Internal: nothing here is part of the ABI.
+// move), capi_materials.hip (materials edited in place) and capi_static.hip (the static view: keys, caches, quiet-tile
+// sets). Internal: nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -281,6 +282,7 @@ struct DrawReads {
   SharedBuf* hdr = nullptr;
   SharedBuf* pbins = nullptr;
   SharedBuf* lights = nullptr;  // the device version of an updated lights buffer (LightVersions)
+  SharedBuf* shade = nullptr;   // the device version of tri_shade records pt_materials_update wrote (SceneGPU::shade)
   const uint64_t* light_stamps = nullptr;  // its per-light position stamps (null: never updated, all 0)
   int light_count = 0;
   // the pointLights texture the draw bound (0: none): part of the verdict cache's key (static_key.h)
@@ -309,7 +311,16 @@ struct PointBinsGPU {
 struct SceneGPU {
   PointBinsGPU pbins;
   float4* geom = nullptr;
-  float4* shade = nullptr;
+  // the tri_shade records. pt_materials_update (capi_materials.hip, DESIGN.md "Material edits") writes a new device
+  // version per update, as LightVersions does for the lights: the buffer the decode made is read by draws that noted
+  // nothing, so the first update sets it aside (shade_first, freed with the scene or at the next decode); later
+  // versions are renewed, waited for (wait_built) and noted in DrawReads. shade.built after a device decode: that
+  // decode's event, which the first update's kernel waits for.
+  SharedBuf shade;
+  float4* shade_first = nullptr;
+  // bumped per update, never reset: with tri_ver in the first-hit key (a retired version taken again has the same
+  // pointer and other contents)
+  uint64_t shade_ver = 0;
   float4* bvh = nullptr;
   float4* bvh4 = nullptr;
   float4* bvh_any = nullptr;  // any-hit tree over the reference leaves (build_anyhit_tree)
@@ -515,6 +526,14 @@ void free_raster_refit(RasterScene& r);
 void free_pose(Pose& p);
 // defined in capi_lights.hip: the versions of an updated lights buffer, the current one (t->dev) included
 void free_lights(Texture* t);
+// defined in capi_materials.hip (DESIGN.md "Material edits"). free_shade: every version of a scene's tri_shade records
+// (the caller holds no draw in flight that reads them, or they are all the decode's: it synchronises when versions
+// exist). materials_order: work issued on s after this call runs after every pt_materials_update issued so far, whose
+// kernels patch the triangle texels and a pose's rest list in place on a stream of their own; called by whatever reads
+// or overwrites those on the device. free_materials: the update stream and its staging (pt_shutdown).
+void free_shade(SceneGPU& sg);
+int materials_order(hipStream_t s);
+void free_materials();
 
 // (T: the device type, or the host tree builder's Float4 for float4)
 template <class T, class D>

@@ -263,7 +263,9 @@ static int first_hit_mode_for(Pass* p, PTParams& k, const SceneGPU* sg, const Pr
     miss = g.bg_miss.of(m.w, kMkWords, &g.bg_serial);
     FirstHitKey f = key_headed<FirstHitKey>(primary_content(key));
     f.w[kFkTriShade] = key_bits((const void*)k.scene.tri_shade);
-    f.w[kFkTriShadeVer] = sg->tri_ver;
+    // the texture version the records were decoded at with the count of pt_materials_update calls since the library
+    // began (neither comes near 2^32): a retired version taken again has the same pointer and other contents
+    f.w[kFkTriShadeVer] = sg->tri_ver + (sg->shade_ver << 32);
     uint32_t mh = 0;
     const Texture* ma = sampler(p, "material_array", &mh);
     if (k.scene.texarr && ma) {

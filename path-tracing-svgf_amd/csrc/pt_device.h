@@ -729,5 +729,16 @@ int skin_tris_launch(const float* rest, int n, const uint16_t* bones, const floa
 int skin_raster_launch(const float* rest, int ntris, const uint16_t* bones, const float* weights, const float* table,
                        int n_bones, float* out, hipStream_t s);
 
+// Material edits (DESIGN.md "Material edits", tests/materials_ref.py): table holds kMaterialFloats per object for the
+// objects first .. first + count - 1 (first + count <= 2^24); a record belongs to object o when its objIndex compares
+// == (float)o. Records of no named object keep their bits.
+constexpr int kMaterialFloats = 18;
+// n tri_shade records (9 float4): new_shade = old_shade with the material floats (record floats 9 .. 26) replaced.
+// new_shade may be old_shade.
+int materials_shade_launch(const float4* old_shade, float4* new_shade, int n, const float* table, int first, int count,
+                           hipStream_t s);
+// n Triangle_encoded records (objIndex: float 42), floats 18 .. 35 replaced where they lie
+int materials_records_launch(float* records, int n, const float* table, int first, int count, hipStream_t s);
+
 }  // namespace ptk
 #endif

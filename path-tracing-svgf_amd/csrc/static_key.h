@@ -286,7 +286,7 @@ inline uint64_t quiet_set_for(QuietChoice& c, uint64_t prim, uint64_t gbuf, uint
 enum FirstHitKeyField {
   kFkPrimary0,                              // primary_content() of the draw's PrimaryKey
   kFkTriShade = kFkPrimary0 + kPkWords,     // SceneDev::tri_shade, and the version of the texture it was decoded from
-  kFkTriShadeVer,
+  kFkTriShadeVer,                           // with, in the high half, the scene's count of pt_materials_update calls
   kFkMatHandle, kFkMatDev, kFkMatVer,       // material_array: handle, device pointer, Texture::version
   kFkMatW, kFkMatH, kFkMatLayers,           // and its size
   kFkWords

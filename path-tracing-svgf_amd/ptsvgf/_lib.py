@@ -92,6 +92,7 @@ _PT_SIGS = [
     ("pt_texture2d_wrap", C.c_int, [_vp, C.c_int, C.c_int, _u32p]),
     ("pt_texbuffer_create", C.c_int, [_vp, C.c_size_t, _u32, _u32p]),
     ("pt_lights_update", C.c_int, [_u32, C.c_int, C.c_int, _fp]),
+    ("pt_materials_update", C.c_int, [_u32, _u32, C.c_int, C.c_int, _fp]),
     ("pt_bvh_build", C.c_int, [_u32, C.c_int, C.c_int, _u32, _u32, C.POINTER(C.c_int), _fp]),
     ("pt_bvh_refit", C.c_int, [_u32, _u32, _u32, _fp]),
     ("pt_texarray_create", C.c_int, [C.c_int, C.c_int, C.c_int, _u32p]),
@@ -164,6 +165,8 @@ _PT_SIGS = [
     ("pt_debug_lights_key_field", C.c_int, [C.c_int]),
     ("pt_debug_lights_state", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int,
                                         C.POINTER(C.c_int)]),
+    # include/ptsvgf_debug_materials.h
+    ("pt_debug_materials_state", C.c_int, [_u32, _u32, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # include/ptsvgf_debug_static.h
     ("pt_debug_point_cache_forgotten", C.c_int, [_u32, _u32p]),
     ("pt_debug_stage_counts", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

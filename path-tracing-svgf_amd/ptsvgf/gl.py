@@ -97,6 +97,22 @@ def lights_update(tex: int, first: int, lights) -> None:
     check(pt().pt_lights_update(tex, int(first), a.shape[0], fptr(a)))
 
 
+def materials_update(tri_tex: int, first_obj: int, materials, pose: int = 0) -> None:
+    """pt_materials_update: objects first_obj .. of the triangle buffer `tri_tex` take `materials` ((n, 18) float32 in
+    ptsvgf_scene.h's order; tests/materials_ref.py is the definition). `pose`: the pt_pose_create handle made from that
+    buffer, whose rest list is patched too. Draws already enqueued keep their materials; nothing waits for the device."""
+    a = np.ascontiguousarray(materials, dtype=np.float32).reshape(-1, 18)
+    check(pt().pt_materials_update(tri_tex, int(pose), int(first_obj), a.shape[0], fptr(a)))
+
+
+def materials_state(tri_tex: int, node_tex: int) -> dict:
+    """pt_debug_materials_state (include/ptsvgf_debug_materials.h) of the scene decoded from the two buffers:
+    {"shade_version", "device_versions", "staging_slots"}."""
+    ver, n, m = C.c_uint64(), C.c_int(), C.c_int()
+    check(pt().pt_debug_materials_state(tri_tex, node_tex, C.byref(ver), C.byref(n), C.byref(m)))
+    return {"shade_version": ver.value, "device_versions": n.value, "staging_slots": m.value}
+
+
 def lights_state(tex: int, nl: int = 4) -> dict:
     """pt_debug_lights_state (include/ptsvgf_debug_lights.h): {"version", "pos_stamps" (per light: the version at which
     its position last changed, 0 never), "device_versions" (device buffers the texture owns)}."""

@@ -6,6 +6,7 @@ written as PNG and, optionally, the selected plane's raw floats as PFM.
 
 --sway DEG bends the bench scene's plant on the device each frame (Renderer.set_skin / skin_objects).
 --light-orbit DEG turns point light 0 about the scene's vertical axis each frame (Renderer.set_lights).
+--hue-cycle DEG [--hue-object K] turns the hue of object K's baseColor each frame (Renderer.set_materials).
 """
 from __future__ import annotations
 
@@ -115,6 +116,9 @@ def main(argv=None) -> int:
                     help="bend the plant (object 2) by an 8-bone chain, the angle a sine over the frames of this amplitude")
     ap.add_argument("--light-orbit", type=float, default=0.0, metavar="DEG",
                     help="turn point light 0 about the scene's vertical axis by DEG per frame (moving light)")
+    ap.add_argument("--hue-cycle", type=float, default=0.0, metavar="DEG",
+                    help="turn the hue of one object's baseColor by DEG per frame (material edits in place)")
+    ap.add_argument("--hue-object", type=int, default=1, metavar="K", help="the object --hue-cycle recolours")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
 
@@ -131,7 +135,17 @@ def main(argv=None) -> int:
         r.set_view(a.view)
         sway = _sway_setup(r, scene) if a.sway is not None else None
         light_at = _light_orbit_setup(scene) if a.light_orbit else None
+        hue0 = None
+        if a.hue_cycle:
+            from .materials import hue_turned, object_material
+
+            try:
+                hue0 = object_material(scene.tri_enc, a.hue_object)  # each hue is turned from the first material
+            except ValueError as e:
+                raise SystemExit(f"--hue-cycle: {e}")
         for f in range(a.frames):
+            if hue0 is not None:
+                r.set_materials({a.hue_object: hue_turned(hue0, a.hue_cycle * (f + 1))})
             if light_at is not None:
                 r.set_lights(light_at(a.light_orbit * (f + 1)), first=0)
             if a.orbit:

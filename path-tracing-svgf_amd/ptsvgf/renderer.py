@@ -801,6 +801,39 @@ class Renderer:
         new[first:first + a.shape[0]] = a
         self.scene.lights = new
 
+    def set_materials(self, materials: dict) -> None:
+        """Material edits (pt_materials_update): `materials` is {obj_index: 18 floats in ptsvgf_scene.h's order}; the
+        triangles of those objects take them from the next frame() on. The frames in flight are not flushed and keep
+        the materials they were issued with; only an open path-tracing batch is issued first. Nothing that reads
+        geometry alone is rebuilt or forgotten (trees, point-light bins, the static view's primary hit and verdicts);
+        on a standing view each slot's next frame writes its emission and albedo planes in full once. The renderer's
+        pose (pose_objects / skin_objects) and the rest pose rebuild_bvh received follow, and so does scene.tri_enc.
+        Contiguous object ranges go in one call each. Same bits as a renderer built on these materials."""
+        from .materials import apply_materials
+
+        table = {}
+        for o, m in materials.items():
+            m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+            if int(o) != o or int(o) < 0 or m.size != 18:
+                raise ValueError(f"set_materials: object {o!r} needs an index >= 0 and 18 floats")
+            table[int(o)] = m
+        if not table:
+            return
+        self._issue_batch()
+        objs = sorted(table)
+        runs, start = [], 0
+        for i in range(1, len(objs) + 1):
+            if i == len(objs) or objs[i] != objs[i - 1] + 1 or i - start == 4096:
+                runs.append(objs[start:i])
+                start = i
+        pose = self._pose or 0
+        for run in runs:
+            block = np.stack([table[o] for o in run])
+            gl.materials_update(self.trianglesTextureBuffer, run[0], block, pose)
+            self.scene.tri_enc = apply_materials(self.scene.tri_enc, run[0], block)
+            if self._pose_rest is not None:  # a pose created later starts from these rows
+                self._pose_rest = (apply_materials(self._pose_rest[0], run[0], block),) + tuple(self._pose_rest[1:])
+
     def _issue_batch(self) -> None:
         """Draw the open batch's path tracers on the stream of its last frame, after all its G-buffers."""
         if not self._batch:
