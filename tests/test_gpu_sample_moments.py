@@ -256,6 +256,7 @@ class Chain:
         self.prev2 = None
 
     def check(self, fr, sm, tag, rows=None):
+        H, W = fr["color"].shape[:2]  # (the frame's own size: tests/test_gpu_material_zoo.py draws another)
         cfg, z = self.cfg, np.zeros((H, W, 4), f32)
         p = self.prev
         ri, rm = self.ref.reproject(fr["velocity"], fr["color"], fr["albedo"], fr["emission"],

@@ -56,6 +56,16 @@ class Restatement:
     POINT_PDF = 2.0           # calculatePointLight :890 (2 PI / n)
     HDR_HALF = 2              # hdrPdf :829 (hdrResolution^2 / 2, integer)
     GGX_CC = 0.25             # clearcoat smithG alpha :659
+    LUM = (0.3, 0.6, 0.1)     # Cdlum's weights :631
+    CTINT_FALLBACK = 1.0      # Ctint where Cdlum <= 0 :632
+    CSPEC0 = 0.08             # Cspec0 = mix(0.08 Cspec, Cdlin, metallic) :634
+    FD90_BASE = 0.5           # Fd90 = 0.5 + 2 LdotH^2 roughness :638
+    SS_SCALE = 1.25           # ss = 1.25 (Fss (1 / (NdotL + NdotV) - 0.5) + 0.5) :646
+    SS_OFF = 0.5              # ... the 0.5 taken from 1 / (NdotL + NdotV)
+    SS_ADD = 0.5              # ... the 0.5 added
+    GLOSS_LO = 0.1            # GTR1's alpha = mix(0.1, 0.001, clearcoatGloss) :657
+    GLOSS_HI = 0.001
+    CC_F0 = 0.04              # Fr = mix(0.04, 1, FH) :658
 
     def __init__(self, scene, cull_group: int = 0):
         """cull_group > 0: closest() tests only the triangles of the groups (cull_group consecutive triangles in a
@@ -132,11 +142,12 @@ class Restatement:
             with np.errstate(divide="ignore", invalid="ignore"):
                 t = (NP1[None, :] - s @ Nf.T) / dN                           # (dot(N,p1) - dot(S,N)) / dot(d,N): sign-free
             ok &= t >= 0.0005
-            P = s[:, None, :] + dd[:, None, :] * t[..., None]
             Nn = np.where(inside[..., None], -Nf[None], Nf[None])
-            c1 = _dot(_cross(p2 - p1, P - p1), Nn)
-            c2 = _dot(_cross(p3 - p2, P - p2), Nn)
-            c3 = _dot(_cross(p1 - p3, P - p3), Nn)
+            with np.errstate(invalid="ignore"):  # t = inf for a ray in a triangle's plane (dot(d, N) = 0), which `ok`
+                P = s[:, None, :] + dd[:, None, :] * t[..., None]            # has rejected: 0 * inf and inf - inf here
+                c1 = _dot(_cross(p2 - p1, P - p1), Nn)
+                c2 = _dot(_cross(p3 - p2, P - p2), Nn)
+                c3 = _dot(_cross(p1 - p3, P - p3), Nn)
             hit = ok & (((c1 > 0) & (c2 > 0) & (c3 > 0)) | ((c1 < 0) & (c2 < 0) & (c3 < 0)))
             th = np.where(hit, t, np.inf)
             k = np.argmin(th, 1)
@@ -217,7 +228,8 @@ class Restatement:
     @staticmethod
     def smith_ggx(NdotV, alphaG):                                            # :547-551
         a, b = alphaG * alphaG, NdotV * NdotV
-        return 1.0 / (NdotV + np.sqrt(a + b - a * b))
+        with np.errstate(divide="ignore"):  # NdotV = 0 at roughness 0: the shader divides by 0 there too
+            return 1.0 / (NdotV + np.sqrt(a + b - a * b))
 
     @staticmethod
     def schlick(u):                                                          # :524-528
@@ -232,26 +244,26 @@ class Restatement:
         NdotL, NdotV = _dot(N, L), _dot(N, V)
         H = _norm(L + V)
         NdotH, LdotH = _dot(N, H), _dot(L, H)
-        Cdlum = 0.3 * base[:, 0] + 0.6 * base[:, 1] + 0.1 * base[:, 2]
+        Cdlum = self.LUM[0] * base[:, 0] + self.LUM[1] * base[:, 1] + self.LUM[2] * base[:, 2]
         with np.errstate(divide="ignore", invalid="ignore"):
-            Ctint = np.where((Cdlum > 0)[:, None], base / Cdlum[:, None], 1.0)
+            Ctint = np.where((Cdlum > 0)[:, None], base / Cdlum[:, None], self.CTINT_FALLBACK)
         Cspec = specular[:, None] * _mix(1.0, Ctint, specularTint[:, None])
-        Cspec0 = _mix(0.08 * Cspec, base, metallic[:, None])
+        Cspec0 = _mix(self.CSPEC0 * Cspec, base, metallic[:, None])
         Csheen = _mix(1.0, Ctint, sheenTint[:, None])
-        Fd90 = 0.5 + 2.0 * LdotH * LdotH * roughness
+        Fd90 = self.FD90_BASE + 2.0 * LdotH * LdotH * roughness
         FL, FV = self.schlick(NdotL), self.schlick(NdotV)
         Fd = _mix(1.0, Fd90, FL) * _mix(1.0, Fd90, FV)
         Fss90 = LdotH * LdotH * roughness
         Fss = _mix(1.0, Fss90, FL) * _mix(1.0, Fss90, FV)
         with np.errstate(divide="ignore", invalid="ignore"):
-            ss = 1.25 * (Fss * (1.0 / (NdotL + NdotV) - 0.5) + 0.5)
+            ss = self.SS_SCALE * (Fss * (1.0 / (NdotL + NdotV) - self.SS_OFF) + self.SS_ADD)
         alpha = np.maximum(0.001, roughness * roughness)
         Ds = self.gtr2(NdotH, alpha)
         FH = self.schlick(LdotH)
         Fs = _mix(Cspec0, 1.0, FH[:, None])
         Gs = self.smith_ggx(NdotL, roughness) * self.smith_ggx(NdotV, roughness)
-        Dr = self.gtr1(NdotH, _mix(0.1, 0.001, clearcoatGloss))
-        Fr = _mix(0.04, 1.0, FH)
+        Dr = self.gtr1(NdotH, _mix(self.GLOSS_LO, self.GLOSS_HI, clearcoatGloss))
+        Fr = _mix(self.CC_F0, 1.0, FH)
         Gr = self.smith_ggx(NdotL, self.GGX_CC) * self.smith_ggx(NdotV, self.GGX_CC)
         Fsheen = (FH * sheen)[:, None] * Csheen
         diffuse = (1.0 / self.PI) * _mix(Fd, ss, subsurface)[:, None] * base + Fsheen
@@ -271,7 +283,7 @@ class Restatement:
         NdotH, LdotH = _dot(N, H), _dot(L, H)
         alpha = np.maximum(0.001, prm[:, 4] ** 2)
         Ds = self.gtr2(NdotH, alpha)
-        Dr = self.gtr1(NdotH, _mix(0.1, 0.001, prm[:, 9]))
+        Dr = self.gtr1(NdotH, _mix(self.GLOSS_LO, self.GLOSS_HI, prm[:, 9]))
         pd, ps, pc = self.lobe_probs(prm)
         with np.errstate(divide="ignore", invalid="ignore"):
             pdf = pd * (NdotL / self.PI) + ps * (Ds * NdotH / (4.0 * LdotH)) + pc * (Dr * NdotH / (4.0 * LdotH))
@@ -300,7 +312,7 @@ class Restatement:
             return I - 2.0 * _dot(Hh, I)[:, None] * Hh                     # reflect(-V, H)
         a2 = np.maximum(0.001, prm[:, 4] ** 2)
         Ls = gtr_h(np.sqrt((1.0 - xi2) / (1.0 + (a2 * a2 - 1.0) * xi2)))    # SampleGTR2 :713-730
-        a1 = _mix(0.1, 0.001, prm[:, 9])
+        a1 = _mix(self.GLOSS_LO, self.GLOSS_HI, prm[:, 9])
         Lc = gtr_h(np.sqrt((1.0 - (a1 * a1) ** (1.0 - xi2)) / (1.0 - a1 * a1)))  # SampleGTR1 :733-750
         return np.where((xi3 <= pd)[:, None], Ld, np.where((xi3 <= pd + ps)[:, None], Ls, Lc))
 
