@@ -1,5 +1,5 @@
 // capi_lights.hip — point lights that move (DESIGN.md "Moving point lights"): pt_lights_update and the diagnostics of
-// include/ptsvgf_debug_lights.h. The per-light consequences are drawn where the draws are issued (capi.hip's
+// include/ptsvgf_debug_lights.h. The per-light consequences are drawn where the draws are issued (capi_draw_pt.hip's
 // point_bins_for, capi_static.hip's point_cache_mode_for) from the position stamps kept here; the rules themselves are
 // lights_key.h's.
 #include "../../include/ptsvgf_debug_lights.h"

@@ -1,8 +1,9 @@
 // capi_state.h — the library state behind include/ptsvgf.h, shared by the translation units that implement it:
-// capi.hip (init, textures, passes, draws, the scene cache; it defines the state and the helpers declared here),
-// capi_geometry.hip (geometry that moves: builds, refits, raster binds, poses), capi_lights.hip (point lights that
-// move), capi_materials.hip (materials edited in place) and capi_static.hip (the static view: keys, caches, quiet-tile
-// sets). Internal: nothing here is part of the ABI.
+// capi.hip (init, textures, passes, uniforms, streams; it defines the state and the helpers declared here),
+// capi_draw_pt.hip (the path tracer's draws, the scene cache, the point-light bins), capi_draw_svgf.hip (the G-buffer
+// draw and the SVGF chain's, one function per pass kind), capi_geometry.hip (geometry that moves: builds, refits,
+// raster binds, poses), capi_lights.hip (point lights that move), capi_materials.hip (materials edited in place) and
+// capi_static.hip (the static view: keys, caches, quiet-tile sets). Internal: nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -466,15 +467,40 @@ inline void tex_written(Texture* t) {
 }
 int ensure_init();
 int refresh_host(Texture* t);
-// a pass's bindings: a uniform of `type` (null: not set as one), an int uniform or `def`, a sampler by name (texture
-// unit 0 when unbound), the rows its draws cover; whether pt_set_band holds a partition of W x H frames
+// a pass's bindings: a uniform of `type` (null: not set as one), an int / float / uint uniform or `def`, a sampler by
+// name (texture unit 0 when unbound; bound_sampler: null when unbound), the rows its draws cover; whether pt_set_band
+// holds a partition of W x H frames
 const Uniform* U(Pass* p, const char* name, int type);
 int ui(Pass* p, const char* n, int def);
+float uf(Pass* p, const char* n, float def);
+uint32_t uu(Pass* p, const char* n, uint32_t def);
 Texture* sampler(Pass* p, const char* name, uint32_t* handle = nullptr);
+Texture* bound_sampler(Pass* p, const char* name);
 void rows_of(Pass* p, int* y0, int* y1);
 bool band_partition(int W, int H);
+// the plane of a 2-D texture of the pass's size (`what` names it in the error text); of the pass's k-th colour
+// attachment, which the draw is about to write (tex_written)
+int plane_of(Texture* t, Pass* p, ptk::Plane* out, const char* what);
+int att_plane(Pass* p, int k, ptk::Plane* out);
+// drops a merged environment; forgets the trees a GPU-built scene borrowed from its node texture
+void free_hdr_merged(HdrMerged& m);
+void drop_borrowed(SceneGPU& sg);
 
-// ---- defined in capi_static.hip: the static view (DESIGN.md "Static view"), as the draws of capi.hip use it
+// ---- defined in capi_draw_pt.hip: the path tracer's draws (pt_pass_draw, pt_pass_draw_batch), and the tile
+// rasterisers' scratch and the cost-ordered tile dispatch, which the G-buffer draw uses too
+int draw_pathtrace(Pass* p);
+int draw_pathtrace_batch(Pass** ps, int n);
+int bins_for(RasterBins& b, int n, int W, int y0, int y1, int cap, ptk::Bins* out);
+int tile_order_begin(Pass* p, int ntiles, ptk::TileSched* out);
+int tile_order_finish(Pass* p, const ptk::TileSched& t);
+
+// ---- defined in capi_draw_svgf.hip: the G-buffer draw and the SVGF chain's draws (pt_pass_draw); the a-trous tile
+// flags of a G-buffer draw or adoption (pt_raster_pass_adopt)
+int draw_raster(Pass* p);
+int draw_svgf(Pass* p, int kind);
+int gbuf_flags(Pass* p, Texture* fwt, ptk::GBufParams& k);
+
+// ---- defined in capi_static.hip: the static view (DESIGN.md "Static view"), as the draws use it
 ptk::PrimaryKey primary_key(const Pass* p, const ptk::PTParams& k, const SceneGPU* sg, int pair_cap);
 bool gbuf_key(Pass* p, const Pass* src, ptk::GbufKey* out);
 bool reuse_static_on(Pass* p);

@@ -2,7 +2,7 @@
 // of static_key.h's keys, what a path-tracing draw does with the primary-hit cache, the verdict cache and the keep
 // mode (StaticView), the static background's quiet-tile sets and per-draw decision (BgDraw), and the diagnostics of
 // include/ptsvgf_debug_static.h, _background.h and _firsthit.h. Host code only, over the library state of
-// capi_state.h; the draws that use it are capi.hip's.
+// capi_state.h; the draws that use it are those of capi_draw_pt.hip and capi_draw_svgf.hip.
 #include "../../include/ptsvgf_debug_background.h"
 #include "../../include/ptsvgf_debug_firsthit.h"
 #include "../../include/ptsvgf_debug_static.h"

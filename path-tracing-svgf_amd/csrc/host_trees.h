@@ -1,4 +1,4 @@
-// host_trees.h — the host tree builder (host_trees.cpp): the packed trees the C ABI layer (capi.hip, capi_geometry.hip) uploads, built
+// host_trees.h — the host tree builder (host_trees.cpp): the packed trees the C ABI layer (capi_draw_pt.hip, capi_geometry.hip) uploads, built
 // from the encoded reference tree or from raster triangles. Plain C++ over std::vector: no HIP header, no library
 // state. Every function that can fail returns a PT_* code (include/ptsvgf.h) and, when `msg` is not null, its message.
 #pragma once

@@ -5,7 +5,7 @@
 // whose triangles move every frame cannot afford that (a recursive sort per node). This builder produces the SAME
 // buffer formats on the device — triangles in leaf order (Triangle_encoded, 15 RGB32F texels each) and
 // BVHNode_encoded nodes with the dummy node 0 and the root at node 1 — so every consumer of the reference's buffers
-// (the path tracer, the host decode in capi.hip, the CPU oracle) takes them unchanged. It is a different tree than
+// (the path tracer, the host decode in capi_draw_pt.hip, the CPU oracle) takes them unchanged. It is a different tree than
 // the SAH builder's (no GPU builder can reproduce a host sort-and-sweep bit for bit); rendering over it is checked
 // against the oracle walking the same buffers (tests/test_gpu_bvh.py).
 //
@@ -251,7 +251,7 @@ __global__ void __launch_bounds__(256) lbvh_reorder(const float* __restrict__ tr
   out[f] = tri[(size_t)(k[p] & mask) * kTriFloats + q];
 }
 
-// Triangle_encoded texels -> the path tracer's tri_geom / tri_shade records (capi.hip get_scene's host decode,
+// Triangle_encoded texels -> the path tracer's tri_geom / tri_shade records (capi_draw_pt.hip get_scene's host decode,
 // same built-ins, so the same bits): the device decode of GPU-built scenes, whose triangles never leave the device.
 __global__ void __launch_bounds__(256) decode_tris_kernel(const float* __restrict__ te, int n, float4* __restrict__ geom,
                                                            float4* __restrict__ shade) {
@@ -496,7 +496,7 @@ __global__ void __launch_bounds__(256) raster_disp_kernel(const float4* __restri
 // ---------------------------------------------------------------------------------------------------------------
 // Walk trees of a built tree (lbvh_trees_launch): the packed binary tree, the leaf list and the 4-wide tree the
 // traversal kernels read, derived from the BVHNode_encoded texels without a trip through the host. Their content is
-// defined by capi.hip's pack_bvh, upload_leaves and pack_wide (greedy collapse, no keep / direct nodes); every
+// defined by pack_bvh and pack_wide (host_trees.cpp) and upload_leaves (capi_draw_pt.hip) (greedy collapse, no keep / direct nodes); every
 // float32 operation below is spelled as those evaluate it (-ffp-contract=off).
 //   trees_local   per node: parent links; per interior node the child list of the 4-wide node it would root (local:
 //                 at most two nodes are opened, so only nodes up to three levels below are read)
@@ -520,7 +520,7 @@ __device__ __forceinline__ NodeTex node_tex(const float* __restrict__ nodes, int
 __device__ __forceinline__ bool node_ok(int i, int nn) { return i >= 1 && i < nn; }
 __device__ __forceinline__ int leaf_ref_of(const NodeTex& t) { return -(t.first * 16 + t.n) - 1; }
 
-// capi.hip sah_area: extents clamped as std::max(d, 0.0f) evaluates ((d < 0) ? 0 : d, so NaN stays NaN)
+// host_trees.cpp sah_area: extents clamped as std::max(d, 0.0f) evaluates ((d < 0) ? 0 : d, so NaN stays NaN)
 __device__ __forceinline__ float tex_area(const float* __restrict__ nodes, int i) {
   const float* f = nodes + (size_t)i * kNodeFloats;
   float dx = f[9] - f[6], dy = f[10] - f[7], dz = f[11] - f[8];

@@ -376,7 +376,7 @@ int launch_point_bins_build(const SceneDev& sc, int nl, int R, int tight, void* 
 // restricted to that light (its info record, cell counts, headers and entry section; the scatter buffer is shared and
 // the stream orders its users). The scene's magnitude (pb_extent) is a function of the triangles, which have not
 // changed, and stays. The other lights' sections are not touched. The caller orders this after every draw that reads
-// the bins (capi.hip point_bins_for).
+// the bins (capi_draw_pt.hip point_bins_for).
 int launch_point_bins_rebuild_light(const SceneDev& sc, int nl, int R, int tight, void* base, int l, hipStream_t s) {
   if (nl < 1 || nl > kPointBins || R < 1 || R > kPointBinsMaxR || !base || !sc.lights || !sc.tri_leaf || l < 0 ||
       l >= nl)

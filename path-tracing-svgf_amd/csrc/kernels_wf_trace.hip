@@ -894,7 +894,7 @@ void launch_closest(const WfDraw& d, int i, hipStream_t s) {
 
 void launch_shadow(const WfDraw& d, int i, hipStream_t s) {
   const PTParams& p = d.ps[0];
-  // point-light shadow rays by the lights' triangle bins (every frame of a batch agrees: capi.hip); deep trees keep
+  // point-light shadow rays by the lights' triangle bins (every frame of a batch agrees: capi_draw_pt.hip); deep trees keep
   // the walk
   const bool pbins = d.stack != WfStack::kDeep && p.point_bins;
   // its grid: a wave per 64 point-light rays (at most one per pixel), at most the resident waves (8 per SIMD), each

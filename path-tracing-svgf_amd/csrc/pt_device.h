@@ -1,5 +1,5 @@
 // pt_device.h — parameter blocks and HBM layouts shared by the C-ABI layer
-// (capi.hip) and the kernels. Everything here is plain data; no torch types.
+// (capi.hip, capi_draw_*.hip) and the kernels. Everything here is plain data; no torch types.
 //
 // HBM layout (DESIGN.md "Data layout"):
 //  * frame planes: RGBA32F (float4) row-major, one plane per GL texture, holding
@@ -256,7 +256,7 @@ struct Bins {
 // found to hit (a cell's entries ascend by it; truncating a float >= 0 rounds it down); the box (x0 | x1 << 4 |
 // y0 << 8 | y1 << 12, in 1 / 16 of the cell) holds every direction of the cell from which such a ray can arrive.
 // info: kPointBinsInfo ints per light: [0] != 0: the light has no usable bins (a non-finite position, or the entries
-// overflowed `cap`: its rays walk; 2: the light moved and its lists are pending, capi.hip point_bins_for), [1] entries, [2..4] float bits of the light position the bins were built around,
+// overflowed `cap`: its rays walk; 2: the light moved and its lists are pending, capi_draw_pt.hip point_bins_for), [1] entries, [2..4] float bits of the light position the bins were built around,
 // [5] float bits of Mtot, the coordinate magnitude of the scene plus the light's, [6] the catch-all list's entries,
 // [7] the (triangle, face) boxes of the light's last build that went to pb_bin_large (kernels_pointbins.hip).
 constexpr int kPointBinsInfo = 8;
@@ -274,7 +274,7 @@ struct PTParams {
   Plane color, emission, albedo, last;  // outputs (+ lastFrame input)
   SceneDev scene;
   Tex hdr, cache;
-  // hdrMap's radiance (.xyz) and hdrCache's pdf (.z) of each texel in one float4 (capi.hip hdr_merged), when both
+  // hdrMap's radiance (.xyz) and hdrCache's pdf (.z) of each texel in one float4 (capi_draw_pt.hip pt_params, hdr_merged), when both
   // textures have one size: the NEE's hdr_color + hdr_pdf at one direction then read one texture (null: two)
   Tex hdr_pdf;
   int hdrResolution;
@@ -314,7 +314,7 @@ struct PTParams {
   int primary_raster;
   const int* pr_fix;
   // point_bins != 0: the point-light shadow rays of the lights with usable bins are decided by wf_shadow_point_bins
-  // over `pbins`; the shadow walks take the HDR rays and the other lights' (uniform point_bins; capi.hip point_bins_for)
+  // over `pbins`; the shadow walks take the HDR rays and the other lights' (uniform point_bins; capi_draw_pt.hip point_bins_for)
   int point_bins;
   PointBinsDev pbins;
   // the bounce-0 point-light verdict cache's mode for this launch (PointCacheMode, point_cache.h). launch_wavefront

@@ -559,7 +559,7 @@ __device__ __forceinline__ bool wide_step(const float4* __restrict__ tree, int& 
   int nh = 0;
 #if PT_WIDE_SIGNED
   // For a ray whose inv components are all finite (the kernels hand the others to the cooperative walk) and a box
-  // with lo <= hi (a tree with a NaN coordinate in a child box is not walked 4-wide: capi.hip), the near plane of an
+  // with lo <= hi (a tree with a NaN coordinate in a child box is not walked 4-wide: capi_draw_pt.hip pt_params), the near plane of an
   // axis is the lo plane when inv >= 0 (+0 included) and the hi plane otherwise: (b - o) * inv rounds monotonically
   // in b, so slab's min(fx, nx) IS that plane's value and its max(fx, nx) the other's — the same floats, picked by
   // which float4 is loaded instead of by 6 min / max per child. hitAABB's d > 0 is t1 >= t0 && t1 > 0 (d is t0 when

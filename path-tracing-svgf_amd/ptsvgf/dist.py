@@ -328,7 +328,7 @@ def allreduce_motion(m: float, dist, group=None) -> float:
 def camera_moved(cam, pre_viewproj) -> bool:
     """True unless this frame's projection * view equals the previous frame's pre_viewproj bit for bit. The G-buffer
     kernel forms both clip positions of a surface point with the same float arithmetic from those two matrices
-    (kernels_pt.hip: motion = now - prev, capi.hip builds projection * view as camera.mat_mul does), so a camera that
+    (kernels_pt.hip: motion = now - prev, capi_draw_svgf.hip builds projection * view as camera.mat_mul does), so a camera that
     did not move gives motion exactly 0 at every pixel."""
     import numpy as np
 

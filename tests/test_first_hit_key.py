@@ -114,7 +114,7 @@ def test_what_is_not_proven_draws_in_full():
 
 
 class Slot:
-    """One path-tracing pass with its three attachments, as capi.hip's draw_pathtrace treats them."""
+    """One path-tracing pass with its three attachments, as capi_draw_pt.hip's draw_pathtrace treats them."""
 
     def __init__(self):
         self.colour, self.emission, self.albedo = (0, 0), 0, 0

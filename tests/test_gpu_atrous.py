@@ -123,6 +123,17 @@ def test_tile_kernel_equals_step_kernel(gpu, step, size):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (v, kw)
 
 
+@pytest.mark.parametrize("step", [1, 4])
+def test_unknown_variant_runs_the_tile_kernel(gpu, step):
+    """An atrous_variant that names no kernel (neither 0, 1 nor 2) runs the LDS-tiled kernel without tile flags: the
+    step kernel's bits. 48 x 33 (the window of _planes that holds its phiIllumination == 0 block) is no multiple of
+    the 16-pixel tile in either direction, so edge tiles are live."""
+    illum, nd, fw = (np.ascontiguousarray(a[40:73, 100:148]) for a in _planes(seed=7))
+    a = _run(gpu, illum, nd, fw, step, 3)
+    b = _run(gpu, illum, nd, fw, step, 2)
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
 def test_tile_kernel_aux_flag_on_rendered_planes(gpu, scene_small):
     """On real G-buffer planes the tile kernel reads the compact depth-fwidth plane, whose sign bit carries the
     zCenter == 1 flag: same bits as the step kernel reading the full texels, every step, 1080p-like aspect."""
