@@ -212,6 +212,43 @@ int pt_texture_device_ptr(uint32_t tex, void** out_ptr);
 int pt_texture_info(uint32_t tex, int* width, int* height, int* row0);
 int pt_texture_destroy(uint32_t tex);
 
+/* ---- ray queries (no GL counterpart) ----------------------------------------- */
+/* Closest hit, occlusion and picking for the caller's own rays over the scene in (tri_tex, node_tex): the scene the
+ * path-tracing draws of these buffers walk, decoded by the first query or draw and current after pt_bvh_build,
+ * pt_bvh_refit, pt_pose_apply and pt_pose_apply_skin (DESIGN.md "Ray queries"; tests/ray_query_ref.py restates the
+ * definition).
+ * A ray is 8 floats on the device, 16-byte aligned: floats 0-2 the origin S, float 3 ignored, floats 4-6 the
+ * direction d, used as given and never normalised (as hitBVH uses ray.direction), float 7 tmax, which only
+ * pt_rays_occluded reads. A hit is 32 bytes: {float t; int32 tri; int32 obj; int32 inside; float P[3]; float zero;}.
+ *
+ * pt_rays_closest: hit i is what hitBVH (path_tracing.frag:372-424) returns for ray i, bit for bit: the least t and,
+ * when several triangles attain it, the one the reference's depth-first order meets first. t: hitTriangle's distance;
+ * tri: the record's index in tri_tex as the buffer lies now (for a pt_bvh_build pair: in tri_out, leaf order); obj:
+ * (int)objIndex of that record (float 42), -1 when that float is not finite or lies outside +-2^24; inside:
+ * hitTriangle's isInside; P = S + d * t in float32, one rounding per operation. A miss: t = 114514 (the reference's
+ * INF), tri = obj = -1, inside = 0, P = 0. The last float is 0.
+ * pt_rays_occluded: byte i is 1 iff ray i's closest hit exists and its t < tmax (in units of t, not of length; a
+ * tmax of +inf asks for any hit), else 0.
+ * pt_rays_primary: the ray records of the pixels (x, y) given as n int32 pairs in device_xy (8-byte aligned), or with
+ * device_xy NULL and n = width * height of every pixel, row-major, row 0 at the bottom: S = eye3, d the path-tracing
+ * pass's primary direction for cameraRotate16 (column-major) and aspect_corrected, bit for bit, tmax = +inf, float 3
+ * = 0. A pixel outside the frame yields d = 0, a ray that misses everything.
+ *
+ * All three are asynchronous on the library's current stream, like draws. n == 0 returns PT_OK and launches nothing.
+ * Every check runs before anything is launched: PT_ERR_INVALID_HANDLE: tri_tex or node_tex is not a texture buffer;
+ * PT_ERR_ARG: a null pointer with n > 0, n < 0 or n > 2^28, a record pointer that is not 16-byte aligned, width or
+ * height < 1, a NULL device_xy with n != width * height; and the scene errors a draw reports for these buffers
+ * (PT_ERR_FORMAT for a tree deeper than the reference's stack[256]). A query over a tree deeper than the LDS stack
+ * grows a scratch buffer before its launch and keeps it until pt_shutdown. A query touches no pass: primary-hit and
+ * verdict caches, static-view keys and tile orders stay as they are. A pt_materials_update issued after a query does
+ * not disturb it. As for draws, the caller has no query in flight on buffers it hands to pt_bvh_build, pt_bvh_refit,
+ * pt_pose_apply or pt_pose_apply_skin. The walks prune with the draws' margins, which are sized for directions of
+ * about unit length. */
+int pt_rays_closest(uint32_t tri_tex, uint32_t node_tex, const void* device_rays, int64_t n, void* device_hits);
+int pt_rays_occluded(uint32_t tri_tex, uint32_t node_tex, const void* device_rays, int64_t n, void* device_u8);
+int pt_rays_primary(const float* eye3, const float* cameraRotate16, int width, int height, int aspect_corrected,
+                    const int32_t* device_xy, int64_t n, void* device_rays_out);
+
 /* ---- passes (RenderPass / Rasterize_RenderPass) ---------------------------- */
 int pt_pass_create(uint32_t program, int width, int height, uint32_t* out_pass);
 int pt_pass_add_color_attachment(uint32_t pass, uint32_t tex);

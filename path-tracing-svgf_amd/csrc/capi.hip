@@ -310,6 +310,7 @@ int pt_shutdown(void) {
   for (auto& kv : g.poses) free_pose(*kv.second);
   for (auto& kv : g.scenes) free_scene(kv.second);
   free_materials();
+  free_rays();
   for (auto& kv : g.hdr_merged) free_hdr_merged(kv.second);
   g.hdr_merged.clear();
   for (QuietSet& q : g.bg_sets)

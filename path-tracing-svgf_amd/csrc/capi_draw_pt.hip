@@ -278,6 +278,10 @@ int get_scene(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU*
 
 namespace ptapi {
 
+int scene_of(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU** out) {
+  return get_scene(tris, th, nodes, nh, out);
+}
+
 // Cost-ordered dispatch (TileSched): the launch records per-tile costs into o.cost and
 // runs in the order the previous launch's costs gave (once one exists for this tile
 // count); tile_order_finish then sorts the new costs for the next launch.

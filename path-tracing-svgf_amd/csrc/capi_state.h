@@ -2,8 +2,9 @@
 // capi.hip (init, textures, passes, uniforms, streams; it defines the state and the helpers declared here),
 // capi_draw_pt.hip (the path tracer's draws, the scene cache, the point-light bins), capi_draw_svgf.hip (the G-buffer
 // draw and the SVGF chain's, one function per pass kind), capi_geometry.hip (geometry that moves: builds, refits,
-// raster binds, poses), capi_lights.hip (point lights that move), capi_materials.hip (materials edited in place) and
-// capi_static.hip (the static view: keys, caches, quiet-tile sets). Internal: nothing here is part of the ABI.
+// raster binds, poses), capi_lights.hip (point lights that move), capi_materials.hip (materials edited in place),
+// capi_rays.hip (ray queries) and capi_static.hip (the static view: keys, caches, quiet-tile sets). Internal: nothing
+// here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -560,6 +561,11 @@ void free_lights(Texture* t);
 void free_shade(SceneGPU& sg);
 int materials_order(hipStream_t s);
 void free_materials();
+// defined in capi_rays.hip: the ray queries' spill scratch (pt_shutdown)
+void free_rays();
+// defined in capi_draw_pt.hip: the decoded scene of a (triangles, nodes) pair of texture buffers, as the path-tracing
+// draws get it (decoded on first use and again when either buffer's version moved on); the scene errors are the draws'
+int scene_of(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU** out);
 
 // (T: the device type, or the host tree builder's Float4 for float4)
 template <class T, class D>

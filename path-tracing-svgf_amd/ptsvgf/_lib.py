@@ -93,6 +93,9 @@ _PT_SIGS = [
     ("pt_texbuffer_create", C.c_int, [_vp, C.c_size_t, _u32, _u32p]),
     ("pt_lights_update", C.c_int, [_u32, C.c_int, C.c_int, _fp]),
     ("pt_materials_update", C.c_int, [_u32, _u32, C.c_int, C.c_int, _fp]),
+    ("pt_rays_closest", C.c_int, [_u32, _u32, _vp, C.c_int64, _vp]),
+    ("pt_rays_occluded", C.c_int, [_u32, _u32, _vp, C.c_int64, _vp]),
+    ("pt_rays_primary", C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp]),
     ("pt_bvh_build", C.c_int, [_u32, C.c_int, C.c_int, _u32, _u32, C.POINTER(C.c_int), _fp]),
     ("pt_bvh_refit", C.c_int, [_u32, _u32, _u32, _fp]),
     ("pt_texarray_create", C.c_int, [C.c_int, C.c_int, C.c_int, _u32p]),
@@ -167,6 +170,10 @@ _PT_SIGS = [
                                         C.POINTER(C.c_int)]),
     # include/ptsvgf_debug_materials.h
     ("pt_debug_materials_state", C.c_int, [_u32, _u32, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    # include/ptsvgf_debug_rays.h
+    ("pt_debug_rays_variant", C.c_int, [C.c_int]),
+    ("pt_debug_rays_state", C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_size_t)]),
     # include/ptsvgf_debug_static.h
     ("pt_debug_point_cache_forgotten", C.c_int, [_u32, _u32p]),
     ("pt_debug_stage_counts", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

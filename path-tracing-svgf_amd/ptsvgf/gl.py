@@ -105,6 +105,118 @@ def materials_update(tri_tex: int, first_obj: int, materials, pose: int = 0) -> 
     check(pt().pt_materials_update(tri_tex, int(pose), int(first_obj), a.shape[0], fptr(a)))
 
 
+# A hit record of pt_rays_closest (32 bytes; the last float, always 0, has no field)
+HIT_DTYPE = np.dtype({"names": ["t", "tri", "obj", "inside", "P"], "formats": ["<f4", "<i4", "<i4", "<i4", ("<f4", (3,))],
+                      "offsets": [0, 4, 8, 12, 16], "itemsize": 32})
+
+
+def _is_tensor(a) -> bool:
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def _device_rays(rays):
+    """(device tensor (n, 8) float32, came from the host) of a ray list given as a numpy array or a torch tensor."""
+    import torch
+
+    if _is_tensor(rays):
+        if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 \
+                or not rays.is_contiguous():
+            raise ValueError("rays: a contiguous float32 (n, 8) device tensor")
+        return rays, False
+    a = np.ascontiguousarray(rays, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError(f"rays: float32 (n, 8), got {a.shape}")
+    t = torch.from_numpy(a).cuda()
+    torch.cuda.current_stream().synchronize()  # the upload, before the library's stream reads it
+    return t, True
+
+
+def rays_closest(tri_tex: int, node_tex: int, rays):
+    """pt_rays_closest: the closest hit of every ray (8 floats: origin, -, direction as given, tmax) over the scene in
+    (tri_tex, node_tex), as the reference's hitBVH returns it (tests/ray_query_ref.py). A numpy (n, 8) array is
+    uploaded, the call synchronises, and a structured array (HIT_DTYPE: t, tri, obj, inside, P) comes back. A torch
+    device tensor is read where it lies on the library's current stream and a float32 (n, 8) device tensor of the raw
+    records comes back without synchronising (floats 1-3 hold the int32 bits of tri, obj, inside)."""
+    import torch
+
+    t, host = _device_rays(rays)
+    n = t.shape[0]
+    out = torch.empty((n, 8), dtype=torch.float32, device=t.device)
+    check(pt().pt_rays_closest(tri_tex, node_tex, C.c_void_p(t.data_ptr() if n else None), n,
+                               C.c_void_p(out.data_ptr() if n else None)))
+    if not host:
+        return out
+    if n:
+        sync()
+    return out.cpu().numpy().view(HIT_DTYPE).reshape(n)
+
+
+def rays_occluded(tri_tex: int, node_tex: int, rays):
+    """pt_rays_occluded: per ray, whether its closest hit exists and lies at t < tmax (float 7; +inf: any hit). numpy
+    in, bool array out (synchronises); torch device tensor in, uint8 device tensor out (no synchronisation)."""
+    import torch
+
+    t, host = _device_rays(rays)
+    n = t.shape[0]
+    out = torch.empty((n,), dtype=torch.uint8, device=t.device)
+    check(pt().pt_rays_occluded(tri_tex, node_tex, C.c_void_p(t.data_ptr() if n else None), n,
+                                C.c_void_p(out.data_ptr() if n else None)))
+    if not host:
+        return out
+    if n:
+        sync()
+    return out.cpu().numpy().astype(bool)
+
+
+def rays_primary(eye, cameraRotate, width: int, height: int, aspect_corrected: bool, xy=None):
+    """pt_rays_primary: the path-tracing pass's primary rays as ray records. xy None: every pixel, row-major, row 0 at
+    the bottom; a numpy (n, 2) int array of (x, y): those pixels (one outside the frame raises PtError PT_ERR_ARG),
+    numpy (n, 8) float32 back after a synchronisation; a torch int32 (n, 2) device tensor: read where it lies on the
+    library's current stream (a pixel outside the frame yields the direction 0, a ray that misses), a device tensor
+    back without synchronising."""
+    import torch
+
+    from ._lib import PtError
+
+    e = np.ascontiguousarray(eye, dtype=np.float32).reshape(3)
+    m = np.ascontiguousarray(cameraRotate, dtype=np.float32).reshape(16)
+    host = not _is_tensor(xy)
+    if xy is None:
+        n, dxy = int(width) * int(height), None
+    elif host:
+        a = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        if a.size and (a.min() < 0 or (a[:, 0] >= width).any() or (a[:, 1] >= height).any()):
+            raise PtError(-6, "rays_primary: a pixel outside the frame")
+        n, dxy = a.shape[0], torch.from_numpy(a).cuda()
+        torch.cuda.current_stream().synchronize()
+    else:
+        if not xy.is_cuda or xy.dtype != torch.int32 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous():
+            raise ValueError("xy: a contiguous int32 (n, 2) device tensor")
+        n, dxy = xy.shape[0], xy
+    out = torch.empty((n, 8), dtype=torch.float32, device="cuda")
+    check(pt().pt_rays_primary(fptr(e), fptr(m), int(width), int(height), 1 if aspect_corrected else 0,
+                               C.c_void_p(dxy.data_ptr() if dxy is not None and n else None), n,
+                               C.c_void_p(out.data_ptr() if n else None)))
+    if not host:
+        return out
+    if n:
+        sync()
+    return out.cpu().numpy()
+
+
+def rays_variant(variant: int) -> None:
+    """pt_debug_rays_variant (include/ptsvgf_debug_rays.h): 0 one ray per lane, 1 lane refill, -1 the default."""
+    check(pt().pt_debug_rays_variant(int(variant)))
+
+
+def rays_state() -> dict:
+    """pt_debug_rays_state: {"stack_kind" (0 small, 1 full, 2 deep), "variant"} of the last query that launched,
+    {"scratch_allocs", "scratch_bytes"} of the deep trees' spill scratch."""
+    k, v, a, b = C.c_int(), C.c_int(), C.c_uint64(), C.c_size_t()
+    check(pt().pt_debug_rays_state(C.byref(k), C.byref(v), C.byref(a), C.byref(b)))
+    return {"stack_kind": k.value, "variant": v.value, "scratch_allocs": a.value, "scratch_bytes": b.value}
+
+
 def materials_state(tri_tex: int, node_tex: int) -> dict:
     """pt_debug_materials_state (include/ptsvgf_debug_materials.h) of the scene decoded from the two buffers:
     {"shade_version", "device_versions", "staging_slots"}."""

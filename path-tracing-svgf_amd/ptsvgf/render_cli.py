@@ -7,10 +7,13 @@ written as PNG and, optionally, the selected plane's raw floats as PFM.
 --sway DEG bends the bench scene's plant on the device each frame (Renderer.set_skin / skin_objects).
 --light-orbit DEG turns point light 0 about the scene's vertical axis each frame (Renderer.set_lights).
 --hue-cycle DEG [--hue-object K] turns the hue of object K's baseColor each frame (Renderer.set_materials).
+--pick X,Y (repeatable) prints, after the last frame, one JSON line {"pick": {...}} with what lies under pixel (X, Y)
+of the last frame's view (Y from the bottom row; Renderer.pick), or {"pick": null}.
 """
 from __future__ import annotations
 
 import argparse
+import json
 import struct
 import zlib
 
@@ -119,8 +122,19 @@ def main(argv=None) -> int:
     ap.add_argument("--hue-cycle", type=float, default=0.0, metavar="DEG",
                     help="turn the hue of one object's baseColor by DEG per frame (material edits in place)")
     ap.add_argument("--hue-object", type=int, default=1, metavar="K", help="the object --hue-cycle recolours")
+    ap.add_argument("--pick", action="append", default=[], metavar="X,Y",
+                    help="after the last frame print {\"pick\": ...} for the pixel (Y from the bottom row); repeatable")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    picks = []
+    for s in a.pick:
+        try:
+            x, y = (int(v) for v in s.split(","))
+        except ValueError:
+            ap.error(f"--pick {s!r}: expected X,Y")
+        if not (0 <= x < a.width and 0 <= y < a.height):
+            ap.error(f"--pick {s!r}: outside {a.width} x {a.height}")
+        picks.append((x, y))
 
     scene = build_scene(a.scene)
     if a.hdr:
@@ -157,6 +171,8 @@ def main(argv=None) -> int:
         write_png(a.png, gl.readback(r.planes()["output"]))
         if a.pfm:
             write_pfm(a.pfm, gl.readback(r._view_plane(r.frame_index - 1)))
+        for x, y in picks:
+            print(json.dumps({"pick": r.pick(x, y)}))
         r.close()
     finally:
         gl.shutdown()

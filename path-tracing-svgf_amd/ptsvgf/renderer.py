@@ -834,6 +834,39 @@ class Renderer:
             if self._pose_rest is not None:  # a pose created later starts from these rows
                 self._pose_rest = (apply_materials(self._pose_rest[0], run[0], block),) + tuple(self._pose_rest[1:])
 
+    # ------------------------------------------------------- ray queries ---
+    def cast_rays(self, rays):
+        """Closest hits of the caller's rays (gl.rays_closest) over the buffers the renderer draws now: after
+        rebuild_bvh / refit_bvh / pose_objects / skin_objects the built pair, so `tri` indexes its leaf order.
+        rays: (n, 8) float32 (origin, -, direction, tmax), numpy or a torch device tensor."""
+        return gl.rays_closest(self.trianglesTextureBuffer, self.nodesTextureBuffer, rays)
+
+    def occluded(self, rays):
+        """Per ray, whether anything lies before its tmax (gl.rays_occluded); a bool array for numpy rays."""
+        return gl.rays_occluded(self.trianglesTextureBuffer, self.nodesTextureBuffer, rays)
+
+    def pick(self, x: int, y: int):
+        """What lies under pixel (x, y) (y from the bottom row, as the textures count) for the renderer's current eye,
+        cameraRotate and aspect_corrected: {"obj", "tri", "t", "point", "inside"}, or None on a miss. Issued on the
+        library's own stream and waited for there alone: the frames in flight are not flushed and draw nothing anew."""
+        from ._lib import check, pt
+
+        cam = self.camera
+        if not (0 <= int(x) < self.W and 0 <= int(y) < self.H):
+            raise ValueError(f"pick: pixel ({x}, {y}) outside {self.W} x {self.H}")
+        check(pt().pt_use_own_stream())
+        try:
+            rays = gl.rays_primary(cam.cam_position, rigid_inverse(cam.cam_view_mat), self.W, self.H,
+                                   self.aspect_corrected, np.array([[int(x), int(y)]], np.int32))
+            h = self.cast_rays(rays)[0]
+        finally:
+            if self._lib_stream is not None:  # the draws' stream, as the last frame left it
+                _set_stream(self._lib_stream)
+        if h["tri"] < 0:
+            return None
+        return {"obj": int(h["obj"]), "tri": int(h["tri"]), "t": float(h["t"]),
+                "point": [float(v) for v in h["P"]], "inside": bool(h["inside"])}
+
     def _issue_batch(self) -> None:
         """Draw the open batch's path tracers on the stream of its last frame, after all its G-buffers."""
         if not self._batch:
