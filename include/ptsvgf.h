@@ -166,6 +166,27 @@ int pt_lights_update(uint32_t lights_tex, int first, int count, const float* pos
  * triangle count, a buffer that is not whole 45-float records; PT_ERR_INVALID_HANDLE: tri_tex is not a texture
  * buffer, or the pose is unknown. Every check runs before anything is launched or changed. */
 int pt_materials_update(uint32_t tri_tex, uint32_t pose, int first_obj, int count, const float* material18);
+/* Environment edits (DESIGN.md "Environment edits"): a new map of the same size for the 2-D textures a path-tracing
+ * pass binds as hdrMap and hdrCache, with its importance cache built on the device. rgb holds width * height texels
+ * of 3 floats in file scanline order, the layout pt_texture2d_upload(.., PT_RGB32F, ..) takes: a host pointer when
+ * on_device is 0, else a device pointer (4-byte aligned). Afterwards hdr_tex holds (R, G, B, 1) and cache_tex
+ * (x, y, pdf, 1) per texel, bit for bit what pt_texture2d_upload(hdr_tex, rgb) and pt_texture2d_upload(cache_tex,
+ * pts_hdr_cache(rgb)) leave, except that a NaN pdf may be another NaN. Draws already enqueued, on any stream, read the
+ * environment they were enqueued with (the merged plane of hdr_merge included); draws issued afterwards read the new
+ * one. The call does not wait for the device and, after the first few, does not allocate. Host data is consumed
+ * before the call returns. Device data is consumed in stream order on the library's current stream: work queued there
+ * before the call has produced it, work queued there afterwards may overwrite it. Both textures' versions advance and
+ * nothing else does: walk trees, point-light bins, the primary-hit and verdict caches and the G-buffer draw's key stay
+ * valid; on a standing view each pass redraws what depends on the miss colour once. pt_texture_readback sees the
+ * current version; pt_texture_device_ptr returns its plane, another pointer after every update, whose texels are
+ * complete once the device is idle (the builds run on a stream of their own; pt_texture_readback waits for every
+ * stream) — the library's draws wait for them themselves. A later
+ * pt_texture2d_upload keeps its contract (no draw in flight); pt_texture_destroy of either texture and pt_shutdown
+ * free the versions. PT_ERR_ARG: null rgb, hdr_tex == cache_tex, width or height outside [1, 8192], a size other
+ * than both textures' (a new size goes through pt_texture2d_upload); PT_ERR_INVALID_HANDLE: not a 2-D texture;
+ * PT_ERR_STATE: a wrapped texture, or one that stores a band of its rows. Every check runs before anything is
+ * launched or changed. */
+int pt_environment_update(uint32_t hdr_tex, uint32_t cache_tex, const void* rgb, int width, int height, int on_device);
 /* GPU BVH builder for dynamic scenes. The reference builds once on the host
  * (buildBVHwithSAH, Utils/BVH.h:42-173, main.cpp:88-96) and encodes triangles and nodes (main.cpp:101-151);
  * this builds a Karras LBVH on the device from the DEVICE contents of tri_in (Triangle_encoded texels, e.g.

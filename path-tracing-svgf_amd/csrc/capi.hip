@@ -300,6 +300,7 @@ int pt_shutdown(void) {
   for (auto& kv : g.textures) {
     Texture* t = kv.second.get();
     free_lights(t);
+    free_environment(t);
     if (t->owned && t->dev) (void)hipFree(t->dev);
     if (t->aux) (void)hipFree(t->aux);
     if (t->tflags) (void)hipFree(t->tflags);
@@ -357,6 +358,8 @@ int pt_stream_release(void* s) {
   }
   for (auto& kv : g.textures)
     if (kv.second->lights) kv.second->lights->sb.forget(st);
+  for (auto& kv : g.textures)
+    if (kv.second->env) kv.second->env->sb.forget(st);
   if (g.stream == st) g.stream = g.own;
   return PT_OK;
 }
@@ -514,6 +517,10 @@ int pt_texture2d_upload(uint32_t tex, int w, int h, uint32_t fmt, const float* d
   if (fmt != PT_RGB32F && fmt != PT_RGBA32F && fmt != PT_RGB && fmt != PT_RGBA)
     return err(PT_ERR_FORMAT, "upload format must be RGB32F or RGBA32F");
   int nch = (fmt == PT_RGB32F || fmt == PT_RGB) ? 3 : 4;
+  // a texture pt_environment_update wrote: a new size ends the pair's versions; else the copy below writes the
+  // current version's plane where it lies, after the build that wrote it
+  if (t->env && (w != t->W || h != t->H)) free_environment(t);
+  if (t->env && t->env->sb.buf) HIPCHK(t->env->sb.wait_built(g.stream));
   if (w != t->W || h != t->H) {  // glTexImage2D respecifies the image
     if (t->owned && t->dev) HIPCHK(hipFree(t->dev));
     if (!t->owned) return err(PT_ERR_ARG, "cannot resize a wrapped texture");
@@ -544,6 +551,7 @@ int pt_texture_upload_rgba(uint32_t tex, const float* data, size_t bytes) {
   Texture* t = tex_of(tex);
   if (!t || t->target != PT_TEXTURE_2D) return err(PT_ERR_INVALID_HANDLE, "invalid 2-D texture");
   if (!data || bytes != t->bytes) return err(PT_ERR_ARG, "upload size must equal the stored rows");
+  if (t->env && t->env->sb.buf) HIPCHK(t->env->sb.wait_built(g.stream));  // (as pt_texture2d_upload)
   HIPCHK(hipMemcpyAsync(t->dev, data, bytes, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
   tex_written(t);
@@ -688,6 +696,7 @@ int pt_texture_destroy(uint32_t tex) {
   if (it == g.textures.end()) return err(PT_ERR_INVALID_HANDLE, "invalid texture");
   (void)hipStreamSynchronize(g.stream);
   free_lights(it->second.get());  // every version of an updated lights buffer (dev is one of them)
+  free_environment(it->second.get());  // of an updated environment: both textures get their own buffers back
   if (it->second->owned && it->second->dev) (void)hipFree(it->second->dev);
   if (it->second->aux) (void)hipFree(it->second->aux);
   if (it->second->tflags) (void)hipFree(it->second->tflags);

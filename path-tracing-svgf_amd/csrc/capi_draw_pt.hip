@@ -560,9 +560,25 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
   reads.cache_ver = hc->version;
   k.cache = Tex{(const float4*)hc->dev, hc->W, hc->H};
   k.hdr_pdf = Tex{nullptr, 0, 0};
+  // pt_environment_update wrote them: the version's build runs on another stream, and is read until noted
+  EnvVersions* ev = hm->env;
+  if (ev && ev->sb.buf) {
+    HIPCHK(ev->sb.wait_built(g.stream));
+    reads.env[0] = &ev->sb;
+  }
+  if (hc->env && hc->env != ev && hc->env->sb.buf) {
+    HIPCHK(hc->env->sb.wait_built(g.stream));
+    reads.env[1] = &hc->env->sb;
+  }
+  // the pair as its last update left it (two whole 2-D textures of one size): the merged plane is the version's third
+  const bool env_pair = ev && ev == hc->env && ev->sb.buf && hm->dev == ev->sb.buf &&
+                        hc->dev == (const char*)ev->sb.buf + ev->plane() && ev->vh == hm->version &&
+                        ev->vc == hc->version;
   // A/B switch hdr_merge (default 1): the NEE's radiance and pdf fetches at one direction from one merged texture
-  if (ui(p, "hdr_merge", 1) && hm != hc && hm->W == hc->W && hm->H == hc->H && hm->target == PT_TEXTURE_2D &&
-      hc->target == PT_TEXTURE_2D && hm->rows == hm->H && hc->rows == hc->H) {
+  if (ui(p, "hdr_merge", 1) && env_pair) {
+    k.hdr_pdf = Tex{(const float4*)((const char*)ev->sb.buf + 2 * ev->plane()), hm->W, hm->H};
+  } else if (ui(p, "hdr_merge", 1) && hm != hc && hm->W == hc->W && hm->H == hc->H && hm->target == PT_TEXTURE_2D &&
+             hc->target == PT_TEXTURE_2D && hm->rows == hm->H && hc->rows == hc->H) {
     // Built on the draw's stream, read by the path tracers of every frame in flight on other streams (SharedBuf).
     // Staleness follows Texture::version, which uploads bump; a texture wrapped around external device memory
     // (pt_texture2d_wrap) is not tracked, so new contents there must be re-bound (a new handle) to be merged.
@@ -715,6 +731,8 @@ int note_reads(const DrawReads& r) {
   if (r.hdr) HIPCHK(r.hdr->note_read(g.stream));
   if (r.lights) HIPCHK(r.lights->note_read(g.stream));
   if (r.shade) HIPCHK(r.shade->note_read(g.stream));
+  for (SharedBuf* e : r.env)
+    if (e) HIPCHK(e->note_read(g.stream));
   return PT_OK;
 }
 

@@ -2,7 +2,8 @@
 // capi.hip (init, textures, passes, uniforms, streams; it defines the state and the helpers declared here),
 // capi_draw_pt.hip (the path tracer's draws, the scene cache, the point-light bins), capi_draw_svgf.hip (the G-buffer
 // draw and the SVGF chain's, one function per pass kind), capi_geometry.hip (geometry that moves: builds, refits,
-// raster binds, poses), capi_lights.hip (point lights that move), capi_materials.hip (materials edited in place),
+// raster binds, poses), capi_lights.hip (point lights that move), capi_environment.hip (the environment edited in place),
+// capi_materials.hip (materials edited in place),
 // capi_rays.hip (ray queries) and capi_static.hip (the static view: keys, caches, quiet-tile sets). Internal: nothing
 // here is part of the ABI.
 #pragma once
@@ -26,6 +27,7 @@
 namespace ptapi {
 
 struct LightVersions;
+struct EnvVersions;
 
 enum ProgKind { PK_PATHTRACE = 1, PK_REPROJECT, PK_VARIANCE, PK_ATROUS, PK_MODULATE, PK_BLIT, PK_SAVE, PK_OUTPUT, PK_TAA,
                 PK_RASTER };
@@ -79,6 +81,9 @@ struct Texture {
   bool host_stale = false;
   // a lights buffer pt_lights_update has written (capi_lights.hip; owned): dev is then lights->sb.buf
   LightVersions* lights = nullptr;
+  // an hdrMap or hdrCache texture pt_environment_update has written (capi_environment.hip): the pair's versions, held
+  // by both textures and owned by the hdrMap; dev is then a plane of env->sb.buf
+  EnvVersions* env = nullptr;
 };
 
 struct Uniform {
@@ -278,6 +283,25 @@ struct LightVersions {
   std::vector<uint64_t> pos_stamp;  // per light: the Texture::version at which its position last changed bitwise
 };
 
+// The device versions of an (hdrMap, hdrCache) pair that pt_environment_update changes (DESIGN.md "Environment edits").
+// One version is one buffer of three float4 planes of W x H texels: the hdr texels, the cache texels and the merged
+// plane (hdr.xyz, cache.z). An update takes a version nothing in flight reads (SharedBuf::renew), builds it on a
+// stream of its own and makes its first two planes the textures' dev. The buffers pt_texture2d_create made are read by
+// draws that noted nothing: the first update sets them aside (first_hdr, first_cache), freed with the versions.
+struct EnvVersions {
+  SharedBuf sb;
+  uint32_t hdr_handle = 0, cache_handle = 0;
+  int W = 0, H = 0;
+  void *first_hdr = nullptr, *first_cache = nullptr;
+  hipStream_t upload = nullptr;    // the builds' stream (non-blocking, created by the first update)
+  hipEvent_t src_done = nullptr;   // a device source: its expansion on the current stream, which the build waits for
+  std::map<void*, void*> staging;  // per device version: its pinned host slot of W x H RGB texels (host sources)
+  float* scratch = nullptr;        // lum / pdf and the conditional CDFs (W x H each), both marginals (W each), the total
+  // the textures' versions as the last update left them: while they stand, the version's merged plane is the pair's
+  uint64_t vh = 0, vc = 0;
+  size_t plane() const { return (size_t)W * H * sizeof(float4); }
+};
+
 // What the draw being issued reads of the shared buffers (pt_params, point_bins_for), noted on its stream after a
 // successful launch (note_reads). Local to the draw call, which holds g_mu throughout.
 struct DrawReads {
@@ -285,6 +309,7 @@ struct DrawReads {
   SharedBuf* pbins = nullptr;
   SharedBuf* lights = nullptr;  // the device version of an updated lights buffer (LightVersions)
   SharedBuf* shade = nullptr;   // the device version of tri_shade records pt_materials_update wrote (SceneGPU::shade)
+  SharedBuf* env[2] = {nullptr, nullptr};  // the versions of an updated hdrMap / hdrCache (EnvVersions; [1]: another pair's)
   const uint64_t* light_stamps = nullptr;  // its per-light position stamps (null: never updated, all 0)
   int light_count = 0;
   // the pointLights texture the draw bound (0: none): part of the verdict cache's key (static_key.h)
@@ -553,6 +578,10 @@ void free_raster_refit(RasterScene& r);
 void free_pose(Pose& p);
 // defined in capi_lights.hip: the versions of an updated lights buffer, the current one (t->dev) included
 void free_lights(Texture* t);
+// defined in capi_environment.hip: the versions of an updated (hdrMap, hdrCache) pair, given either texture. Both
+// textures are left with a buffer of their own that holds what they held (nothing in flight reads them afterwards:
+// it synchronises)
+void free_environment(Texture* t);
 // defined in capi_materials.hip (DESIGN.md "Material edits"). free_shade: every version of a scene's tri_shade records
 // (the caller holds no draw in flight that reads them, or they are all the decode's: it synchronises when versions
 // exist). materials_order: work issued on s after this call runs after every pt_materials_update issued so far, whose

@@ -530,6 +530,15 @@ void point_bins_sections(int ntris, int nl, int R, int tight, int l, size_t* hdr
 // The verdict cache forgets the lights of `mask` (pc_forget, point_cache.h) on the n words of `plane`
 // (kernels_lights.hip).
 int launch_point_cache_forget(uint16_t* plane, size_t n, uint32_t mask, hipStream_t s);
+// The environment's importance cache on the device (kernels_environment.hip, DESIGN.md "Environment edits").
+// environment_expand: n RGB texels (3 floats each) to (R, G, B, 1). environment_scratch_floats: the floats of scratch a
+// W x H build works in. launch_environment_cache: from the hdr texels, the cache texels (x, y, pdf, 1) of pts_hdr_cache
+// and the merged plane (hdr.xyz, pdf), bit for bit; 1 <= W, H <= kEnvMaxSide. Everything runs on s.
+constexpr int kEnvMaxSide = 8192;
+int launch_environment_expand(const float* rgb, float4* hdr, int n, hipStream_t s);
+size_t environment_scratch_floats(int W, int H);
+int launch_environment_cache(const float4* hdr, float4* cache, float4* merged, float* scratch, int W, int H,
+                             hipStream_t s);
 }  // namespace ptk
 
 namespace ptk {

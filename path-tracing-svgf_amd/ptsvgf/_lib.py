@@ -93,6 +93,7 @@ _PT_SIGS = [
     ("pt_texbuffer_create", C.c_int, [_vp, C.c_size_t, _u32, _u32p]),
     ("pt_lights_update", C.c_int, [_u32, C.c_int, C.c_int, _fp]),
     ("pt_materials_update", C.c_int, [_u32, _u32, C.c_int, C.c_int, _fp]),
+    ("pt_environment_update", C.c_int, [_u32, _u32, _vp, C.c_int, C.c_int, C.c_int]),
     ("pt_rays_closest", C.c_int, [_u32, _u32, _vp, C.c_int64, _vp]),
     ("pt_rays_occluded", C.c_int, [_u32, _u32, _vp, C.c_int64, _vp]),
     ("pt_rays_primary", C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp]),
@@ -168,6 +169,8 @@ _PT_SIGS = [
     ("pt_debug_lights_key_field", C.c_int, [C.c_int]),
     ("pt_debug_lights_state", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int,
                                         C.POINTER(C.c_int)]),
+    # include/ptsvgf_debug_environment.h
+    ("pt_debug_environment_state", C.c_int, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # include/ptsvgf_debug_materials.h
     ("pt_debug_materials_state", C.c_int, [_u32, _u32, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # include/ptsvgf_debug_rays.h

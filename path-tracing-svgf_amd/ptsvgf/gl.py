@@ -105,6 +105,35 @@ def materials_update(tri_tex: int, first_obj: int, materials, pose: int = 0) -> 
     check(pt().pt_materials_update(tri_tex, int(pose), int(first_obj), a.shape[0], fptr(a)))
 
 
+def environment_update(hdr_tex: int, cache_tex: int, rgb) -> None:
+    """pt_environment_update: a new map of the same size for the hdrMap / hdrCache pair, its importance cache built on
+    the device (tests/environment_ref.py is the definition). `rgb` is (h, w, 3) float32: a numpy array, or a contiguous
+    CUDA torch tensor, consumed in stream order on the library's current stream. Draws already enqueued keep the
+    environment they were enqueued with; nothing waits for the device."""
+    if _is_tensor(rgb):
+        if not rgb.is_cuda or str(rgb.dtype) != "torch.float32" or not rgb.is_contiguous() or rgb.dim() != 3:
+            raise ValueError("environment_update: a contiguous float32 CUDA tensor of shape (h, w, 3)")
+        h, w, ch = rgb.shape
+        ptr, dev = C.c_void_p(rgb.data_ptr()), 1
+    else:
+        a = np.ascontiguousarray(rgb, dtype=np.float32)
+        if a.ndim != 3:
+            raise ValueError("environment_update: an array of shape (h, w, 3)")
+        h, w, ch = a.shape
+        ptr, dev = a.ctypes.data_as(C.c_void_p), 0
+    if ch != 3:
+        raise ValueError("environment_update: 3 floats per texel")
+    check(pt().pt_environment_update(hdr_tex, cache_tex, ptr, int(w), int(h), dev))
+
+
+def environment_state(hdr_tex: int) -> dict:
+    """pt_debug_environment_state (include/ptsvgf_debug_environment.h): {"version", "device_versions",
+    "staging_slots"}."""
+    ver, n, m = C.c_uint64(), C.c_int(), C.c_int()
+    check(pt().pt_debug_environment_state(hdr_tex, C.byref(ver), C.byref(n), C.byref(m)))
+    return {"version": ver.value, "device_versions": n.value, "staging_slots": m.value}
+
+
 # A hit record of pt_rays_closest (32 bytes; the last float, always 0, has no field)
 HIT_DTYPE = np.dtype({"names": ["t", "tri", "obj", "inside", "P"], "formats": ["<f4", "<i4", "<i4", "<i4", ("<f4", (3,))],
                       "offsets": [0, 4, 8, 12, 16], "itemsize": 32})

@@ -7,6 +7,7 @@ written as PNG and, optionally, the selected plane's raw floats as PFM.
 --sway DEG bends the bench scene's plant on the device each frame (Renderer.set_skin / skin_objects).
 --light-orbit DEG turns point light 0 about the scene's vertical axis each frame (Renderer.set_lights).
 --hue-cycle DEG [--hue-object K] turns the hue of object K's baseColor each frame (Renderer.set_materials).
+--sky-turn DEG turns the environment map about the vertical axis by DEG per frame (Renderer.set_environment).
 --pick X,Y (repeatable) prints, after the last frame, one JSON line {"pick": {...}} with what lies under pixel (X, Y)
 of the last frame's view (Y from the bottom row; Renderer.pick), or {"pick": null}.
 """
@@ -66,6 +67,11 @@ def _sway_setup(r, scene, obj: int = 2):
     return lambda deg: skin.chain_bones(base, tip, SWAY_BONES, deg, (0.0, 0.0, 1.0))
 
 
+def sky_shift(f: int, deg: float, width: int) -> int:
+    """--sky-turn: the columns the original map is rolled by before frame f."""
+    return int(round(f * deg / 360.0 * width))
+
+
 def _light_orbit_setup(scene, light: int = 0):
     """--light-orbit: frame count -> the light's record turned by that many steps about the vertical (y) axis through
     the middle of the scene's bounds. Each position is turned from the first one, so the steps do not accumulate
@@ -121,6 +127,8 @@ def main(argv=None) -> int:
                     help="turn point light 0 about the scene's vertical axis by DEG per frame (moving light)")
     ap.add_argument("--hue-cycle", type=float, default=0.0, metavar="DEG",
                     help="turn the hue of one object's baseColor by DEG per frame (material edits in place)")
+    ap.add_argument("--sky-turn", type=float, default=0.0, metavar="DEG",
+                    help="turn the environment map by DEG per frame: its columns rolled from the original (environment edits)")
     ap.add_argument("--hue-object", type=int, default=1, metavar="K", help="the object --hue-cycle recolours")
     ap.add_argument("--pick", action="append", default=[], metavar="X,Y",
                     help="after the last frame print {\"pick\": ...} for the pixel (Y from the bottom row); repeatable")
@@ -157,7 +165,10 @@ def main(argv=None) -> int:
                 hue0 = object_material(scene.tri_enc, a.hue_object)  # each hue is turned from the first material
             except ValueError as e:
                 raise SystemExit(f"--hue-cycle: {e}")
+        sky0 = np.array(scene.hdr, np.float32, copy=True) if a.sky_turn else None  # each turn rolls the original
         for f in range(a.frames):
+            if sky0 is not None:
+                r.set_environment(np.roll(sky0, sky_shift(f, a.sky_turn, sky0.shape[1]), axis=1))
             if hue0 is not None:
                 r.set_materials({a.hue_object: hue_turned(hue0, a.hue_cycle * (f + 1))})
             if light_at is not None:

@@ -834,6 +834,35 @@ class Renderer:
             if self._pose_rest is not None:  # a pose created later starts from these rows
                 self._pose_rest = (apply_materials(self._pose_rest[0], run[0], block),) + tuple(self._pose_rest[1:])
 
+    def set_environment(self, hdr) -> None:
+        """Environment edits (pt_environment_update): `hdr`, an (h, w, 3) float32 numpy array or CUDA torch tensor of
+        the map's size, is the environment from the next frame() on; its importance cache is built on the device.
+        The frames in flight are not flushed and keep the environment they were issued with; only an open
+        path-tracing batch is issued first. A tensor is consumed in the order of torch's current stream: what that
+        stream has queued produced it, and it may be overwritten there right after the call. Trees, point-light bins
+        and the static view's primary hit and verdicts stay; on a standing view each slot redraws what depends on the
+        miss colour once. For a host array scene.hdr follows; scene.cache is dropped (nothing reads it after
+        construction). Same bits as a renderer built on (hdr, hdr_cache(hdr))."""
+        tensor = type(hdr).__module__.split(".")[0] == "torch"
+        if not tensor:
+            hdr = np.ascontiguousarray(hdr, dtype=np.float32)
+        if tuple(hdr.shape) != (self.scene.hdr.shape[0], self.hdrResolution, 3):
+            raise ValueError(f"set_environment: a map of shape {tuple(self.scene.hdr.shape)}, not {tuple(hdr.shape)}")
+        self._issue_batch()
+        if tensor:
+            import torch
+
+            _set_stream(torch.cuda.current_stream())
+            try:
+                gl.environment_update(self.hdrMap, self.hdrCache, hdr)
+            finally:
+                if self._lib_stream is not None:  # the draws' stream, as the last frame left it
+                    _set_stream(self._lib_stream)
+        else:
+            gl.environment_update(self.hdrMap, self.hdrCache, hdr)
+            self.scene.hdr = np.array(hdr, dtype=np.float32, copy=True)
+        self.scene.cache = None
+
     # ------------------------------------------------------- ray queries ---
     def cast_rays(self, rays):
         """Closest hits of the caller's rays (gl.rays_closest) over the buffers the renderer draws now: after
