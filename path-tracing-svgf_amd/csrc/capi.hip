@@ -194,6 +194,42 @@ void free_scene(SceneGPU& sg) {
   sg.tri_leaf_cap = 0;
 }
 
+// what a texture holds on the device (pt_texture_destroy, pt_shutdown: nothing in flight reads it)
+void free_texture(Texture* t) {
+  free_lights(t);       // every version of an updated lights buffer (dev is one of them)
+  free_environment(t);  // of an updated environment: both textures get their own buffers back
+  if (t->owned && t->dev) (void)hipFree(t->dev);
+  if (t->aux) (void)hipFree(t->aux);
+  if (t->tflags) (void)hipFree(t->tflags);
+  free_trees(t);  // (pt_texture_destroy drops the scenes that borrowed them)
+  free_refit(t);
+}
+
+// Every SharedBuf that lives: the merged environments, every scene's point-light bins and shade versions, every
+// texture's light and environment versions (a pair's twice: both textures hold it). Whatever keeps one adds it here.
+template <class F>
+void each_shared(F f) {
+  for (auto& kv : g.hdr_merged) f(kv.second.sb);
+  for (auto& kv : g.scenes) {
+    f(kv.second.pbins.sb);
+    f(kv.second.shade.sb);
+  }
+  for (auto& kv : g.textures) {
+    if (kv.second->lights) f(kv.second->lights->sb);
+    if (kv.second->env) f(kv.second->env->sb);
+  }
+}
+
+// the stored rows of a new w x h image of 2-D texture t: the band's under a pt_set_band of that size, else all
+void store_rows(Texture* t, int w, int h) {
+  const bool band = g.band_h > 0 && w == g.band_w && h == g.band_h;
+  t->W = w;
+  t->H = h;
+  t->row0 = band ? g.band_row0 : 0;
+  t->rows = band ? g.band_rows : h;
+  t->bytes = (size_t)w * t->rows * 16;
+}
+
 // what a pass holds on the device (pt_pass_destroy, pt_shutdown: nothing in flight reads it)
 void free_pass(Pass* p) {
   if (p->raster.geom) (void)hipFree(p->raster.geom);
@@ -297,16 +333,7 @@ int pt_shutdown(void) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   if (!g.init) return PT_OK;
   (void)hipDeviceSynchronize();
-  for (auto& kv : g.textures) {
-    Texture* t = kv.second.get();
-    free_lights(t);
-    free_environment(t);
-    if (t->owned && t->dev) (void)hipFree(t->dev);
-    if (t->aux) (void)hipFree(t->aux);
-    if (t->tflags) (void)hipFree(t->tflags);
-    free_trees(t);
-    free_refit(t);
-  }
+  for (auto& kv : g.textures) free_texture(kv.second.get());
   for (auto& kv : g.passes) free_pass(kv.second.get());
   for (auto& kv : g.poses) free_pose(*kv.second);
   for (auto& kv : g.scenes) free_scene(kv.second);
@@ -350,16 +377,8 @@ int pt_stream_release(void* s) {
     (void)hipStreamDestroy(it->second.side);
     g.forks.erase(it);
   }
-  // the stream's last reads of the merged environments and of the scenes' point-light bins: done before the entry goes
-  for (auto& kv : g.hdr_merged) kv.second.sb.forget(st);
-  for (auto& kv : g.scenes) {
-    kv.second.pbins.sb.forget(st);
-    kv.second.shade.forget(st);
-  }
-  for (auto& kv : g.textures)
-    if (kv.second->lights) kv.second->lights->sb.forget(st);
-  for (auto& kv : g.textures)
-    if (kv.second->env) kv.second->env->sb.forget(st);
+  // the stream's last reads of every shared buffer: done before the entry goes
+  each_shared([st](SharedBuf& sb) { sb.forget(st); });
   if (g.stream == st) g.stream = g.own;
   return PT_OK;
 }
@@ -474,16 +493,7 @@ int pt_texture2d_create(int w, int h, uint32_t* out) {
   TRY(ensure_init());
   if (w <= 0 || h <= 0 || !out) return err(PT_ERR_ARG, "pt_texture2d_create: bad size");
   auto t = std::make_unique<Texture>();
-  t->W = w;
-  t->H = h;
-  if (g.band_h > 0 && w == g.band_w && h == g.band_h) {
-    t->row0 = g.band_row0;
-    t->rows = g.band_rows;
-  } else {
-    t->row0 = 0;
-    t->rows = h;
-  }
-  t->bytes = (size_t)w * t->rows * 16;
+  store_rows(t.get(), w, h);
   HIPCHK(hipMalloc(&t->dev, t->bytes));
   HIPCHK(hipMemsetAsync(t->dev, 0, t->bytes, g.stream));  // GL leaves it undefined; the build zeroes
   return new_texture(std::move(t), out);
@@ -494,15 +504,7 @@ int pt_texture2d_wrap(void* ptr, int w, int h, uint32_t* out) {
   TRY(ensure_init());
   if (!ptr || w <= 0 || h <= 0 || !out) return err(PT_ERR_ARG, "pt_texture2d_wrap: bad argument");
   auto t = std::make_unique<Texture>();
-  t->W = w;
-  t->H = h;
-  if (g.band_h > 0 && w == g.band_w && h == g.band_h) {
-    t->row0 = g.band_row0;
-    t->rows = g.band_rows;
-  } else {
-    t->rows = h;
-  }
-  t->bytes = (size_t)w * t->rows * 16;
+  store_rows(t.get(), w, h);
   t->dev = ptr;
   t->owned = false;
   return new_texture(std::move(t), out);
@@ -526,9 +528,7 @@ int pt_texture2d_upload(uint32_t tex, int w, int h, uint32_t fmt, const float* d
     if (!t->owned) return err(PT_ERR_ARG, "cannot resize a wrapped texture");
     if (t->aux) (void)hipFree(t->aux);  // sized for the old image
     t->aux = nullptr;
-    t->W = w; t->H = h; t->row0 = 0; t->rows = h;
-    if (g.band_h > 0 && w == g.band_w && h == g.band_h) { t->row0 = g.band_row0; t->rows = g.band_rows; }
-    t->bytes = (size_t)w * t->rows * 16;
+    store_rows(t, w, h);
     HIPCHK(hipMalloc(&t->dev, t->bytes));
   }
   std::vector<float4> buf((size_t)w * t->rows);
@@ -695,13 +695,7 @@ int pt_texture_destroy(uint32_t tex) {
   auto it = g.textures.find(tex);
   if (it == g.textures.end()) return err(PT_ERR_INVALID_HANDLE, "invalid texture");
   (void)hipStreamSynchronize(g.stream);
-  free_lights(it->second.get());  // every version of an updated lights buffer (dev is one of them)
-  free_environment(it->second.get());  // of an updated environment: both textures get their own buffers back
-  if (it->second->owned && it->second->dev) (void)hipFree(it->second->dev);
-  if (it->second->aux) (void)hipFree(it->second->aux);
-  if (it->second->tflags) (void)hipFree(it->second->tflags);
-  free_trees(it->second.get());  // the scenes that borrowed them are dropped below
-  free_refit(it->second.get());
+  free_texture(it->second.get());  // (the scenes that borrowed its trees are dropped below)
   g.textures.erase(it);
   for (auto hm = g.hdr_merged.begin(); hm != g.hdr_merged.end();) {  // merged environments built from it
     if (hm->first.first == tex || hm->first.second == tex) {

@@ -172,11 +172,12 @@ int get_scene_lbvh(Texture* tris, Texture* nodes, SceneGPU& sg, SceneGPU** out) 
   free_shade(sg);
   const size_t shade_bytes = std::max<size_t>(ntris, 1) * 9 * sizeof(float4);
   HIPCHK(hipMalloc((void**)&sg.geom, std::max<size_t>(ntris, 1) * 4 * sizeof(float4)));
-  HIPCHK(hipMalloc(&sg.shade.buf, shade_bytes));
-  sg.shade.bytes = shade_bytes;
+  HIPCHK(hipMalloc(&sg.shade.sb.buf, shade_bytes));
+  sg.shade.sb.bytes = shade_bytes;
   TRY(materials_order(g.stream));  // the texels as every pt_materials_update so far left them
-  HIPCHK((hipError_t)ptk::decode_tris((const float*)tris->dev, (int)ntris, sg.geom, (float4*)sg.shade.buf, g.stream));
-  HIPCHK(sg.shade.mark_built(g.stream));  // for a pt_materials_update that follows: draws do not wait for it
+  HIPCHK((hipError_t)ptk::decode_tris((const float*)tris->dev, (int)ntris, sg.geom, (float4*)sg.shade.sb.buf,
+                                      g.stream));
+  HIPCHK(sg.shade.sb.mark_built(g.stream));  // for a pt_materials_update that follows: draws do not wait for it
   if (const int rc = build_tri_leaf(sg, (int)ntris)) return rc;
   sg.root_ref = root;
   sg.ntris = (int)ntris;
@@ -261,8 +262,8 @@ int get_scene(Texture* tris, uint32_t th, Texture* nodes, uint32_t nh, SceneGPU*
   {
     float4* sh = nullptr;
     if ((rc = upload_vec(shade, &sh)) != PT_OK) return rc;
-    sg.shade.buf = sh;
-    sg.shade.bytes = shade.size() * sizeof(float4);
+    sg.shade.sb.buf = sh;
+    sg.shade.sb.bytes = shade.size() * sizeof(float4);
   }
   if (bvh.empty()) bvh.push_back(Float4{0, 0, 0, 0});
   if ((rc = upload_vec(bvh, &sg.bvh)) != PT_OK) return rc;
@@ -446,7 +447,7 @@ int point_bins_for(Pass* p, SceneGPU* sg, Texture* lt, uint32_t lh, PTParams& k,
       fprintf(stderr, "ptsvgf point-light bins: %d lights, R = %d, %zu B allocated (headers %zu B per light)\n", nl, R,
               need, (size_t)(6 * R * R + 1) * sizeof(int2));
   }
-  HIPCHK(m.sb.wait_built(g.stream));
+  TRY(read_shared(reads, m.sb));
   // Moving lights (DESIGN.md "Moving point lights"), once per draw and light (lights_key.h light_bins_step): a light
   // that moved is marked (info[l][0] = 2: its rays walk) and, once it has stood for point_bins_settle draws, gets its
   // lists rebuilt, alone and in place. Both write what the draws in flight on other streams read, so this stream
@@ -470,7 +471,6 @@ int point_bins_for(Pass* p, SceneGPU* sg, Texture* lt, uint32_t lh, PTParams& k,
     m.light_dev = lt->dev;
     m.light_ver = lt->version;
   }
-  reads.pbins = &m.sb;
   k.point_bins = 1;
   k.pbins = m.dev;
   return PT_OK;
@@ -495,11 +495,9 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
     return err(PT_ERR_MISSING_TEXTURE, "path_tracing needs the 'triangles' and 'nodes' texture buffers");
   TRY(get_scene(tt, th, nt, nh, &sg));
   k.scene.tri_geom = sg->geom;
-  k.scene.tri_shade = (const float4*)sg->shade.buf;
-  if (sg->shade_first) {  // pt_materials_update wrote it, on another stream; this version is read until noted
-    HIPCHK(sg->shade.wait_built(g.stream));
-    reads.shade = &sg->shade;
-  }
+  k.scene.tri_shade = (const float4*)sg->shade.sb.buf;
+  // pt_materials_update wrote it, on another stream; this version is read until noted
+  if (sg->shade.edited()) TRY(read_shared(reads, sg->shade.sb));
   k.scene.bvh = sg->bvh;
   k.scene.root_ref = sg->root_ref;
   k.stack_need = sg->stack_need;
@@ -534,8 +532,7 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
     reads.light_handle = lh;
     reads.light_ver = lt->version;
     if (lt->lights) {  // pt_lights_update wrote it: this version's copy runs on another stream, and is read until noted
-      HIPCHK(lt->lights->sb.wait_built(g.stream));
-      reads.lights = &lt->lights->sb;
+      TRY(read_shared(reads, lt->lights->sb));
       reads.light_stamps = lt->lights->pos_stamp.data();
       reads.light_count = (int)lt->lights->pos_stamp.size();
     }
@@ -562,14 +559,8 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
   k.hdr_pdf = Tex{nullptr, 0, 0};
   // pt_environment_update wrote them: the version's build runs on another stream, and is read until noted
   EnvVersions* ev = hm->env;
-  if (ev && ev->sb.buf) {
-    HIPCHK(ev->sb.wait_built(g.stream));
-    reads.env[0] = &ev->sb;
-  }
-  if (hc->env && hc->env != ev && hc->env->sb.buf) {
-    HIPCHK(hc->env->sb.wait_built(g.stream));
-    reads.env[1] = &hc->env->sb;
-  }
+  if (ev && ev->sb.buf) TRY(read_shared(reads, ev->sb));
+  if (hc->env && hc->env != ev && hc->env->sb.buf) TRY(read_shared(reads, hc->env->sb));  // (another pair's)
   // the pair as its last update left it (two whole 2-D textures of one size): the merged plane is the version's third
   const bool env_pair = ev && ev == hc->env && ev->sb.buf && hm->dev == ev->sb.buf &&
                         hc->dev == (const char*)ev->sb.buf + ev->plane() && ev->vh == hm->version &&
@@ -602,8 +593,7 @@ int pt_params(Pass* p, PTParams& k, SceneGPU*& sg, DrawReads& reads) {
       m.vh = hm->version;
       m.vc = hc->version;
     }
-    HIPCHK(m.sb.wait_built(g.stream));
-    reads.hdr = &m.sb;
+    TRY(read_shared(reads, m.sb));
     k.hdr_pdf = Tex{(const float4*)m.sb.buf, m.W, m.H};
   }
   k.hdrResolution = ui(p, "hdrResolution", hm->W);
@@ -723,17 +713,6 @@ const ptk::WfFork* wf_fork(Pass* p, hipStream_t s, int* rc) {
     return nullptr;
   }
   return &(g.forks[s] = f);
-}
-
-// after a path-tracing draw's launch: its stream's use events on the shared buffers it read (SharedBuf::note_read)
-int note_reads(const DrawReads& r) {
-  if (r.pbins) HIPCHK(r.pbins->note_read(g.stream));
-  if (r.hdr) HIPCHK(r.hdr->note_read(g.stream));
-  if (r.lights) HIPCHK(r.lights->note_read(g.stream));
-  if (r.shade) HIPCHK(r.shade->note_read(g.stream));
-  for (SharedBuf* e : r.env)
-    if (e) HIPCHK(e->note_read(g.stream));
-  return PT_OK;
 }
 
 // Samples per pixel of a path-tracing pass's draw (int uniform spp, default 1): 1 .. kMaxBatch, checked before

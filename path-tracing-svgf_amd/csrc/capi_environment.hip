@@ -1,7 +1,7 @@
 // capi_environment.hip — the environment edited in place (DESIGN.md "Environment edits"): pt_environment_update and the
-// diagnostic of include/ptsvgf_debug_environment.h. The (hdrMap, hdrCache) pair gets device versions as the lights
-// buffer does (EnvVersions, capi_state.h); the importance cache is built on the device (kernels_environment.hip). The
-// draws wait for a version's build and note their reads where they bind the pair (capi_draw_pt.hip's pt_params).
+// diagnostic of include/ptsvgf_debug_environment.h. The (hdrMap, hdrCache) pair's device versions are a Versions with
+// a second set-aside buffer (EnvVersions, capi_state.h); the importance cache is built on the device
+// (kernels_environment.hip). The draws read a version where they bind the pair (capi_draw_pt.hip's pt_params).
 #include "../../include/ptsvgf_debug_environment.h"
 #include "capi_state.h"
 
@@ -14,7 +14,7 @@ void free_environment(Texture* t) {
   if (!v) return;
   (void)hipDeviceSynchronize();  // the builds' stream, and the versions' readers on any stream
   Texture* pair[2] = {tex_of(v->hdr_handle), tex_of(v->cache_handle)};
-  void* first[2] = {v->first_hdr, v->first_cache};
+  void* first[2] = {v->take_first(), v->first_cache};
   for (int i = 0; i < 2; ++i) {
     Texture* p = pair[i];
     if (!p || p->env != v) continue;
@@ -27,11 +27,9 @@ void free_environment(Texture* t) {
   }
   for (void* f : first)
     if (f) (void)hipFree(f);
-  v->sb.free();
-  for (auto& s : v->staging) (void)hipHostFree(s.second);
+  v->free();
   if (v->scratch) (void)hipFree(v->scratch);
   if (v->src_done) (void)hipEventDestroy(v->src_done);
-  if (v->upload) (void)hipStreamDestroy(v->upload);
   delete v;
 }
 
@@ -72,21 +70,15 @@ int pt_environment_update(uint32_t hdr_tex, uint32_t cache_tex, const void* rgb,
     HIPCHK(hipMalloc((void**)&nv->scratch, ptk::environment_scratch_floats(width, height) * sizeof(float)));
     v = th->env = tc->env = nv.release();  // (what it lacks still is had below, or by the next update)
   }
-  if (!v->upload) HIPCHK(hipStreamCreateWithFlags(&v->upload, hipStreamNonBlocking));
+  hipStream_t up = v->stream();
+  if (!up) return hip_err(hipGetLastError(), "pt_environment_update: the builds' stream");
   if (!v->src_done) HIPCHK(hipEventCreateWithFlags(&v->src_done, hipEventDisableTiming));
-  // a version nothing in flight reads. The first update sets the textures' own buffers aside: draws read them unnoted.
+  // a version nothing in flight reads; the first update sets both textures' own buffers aside
   const size_t plane = v->plane();
-  if (!v->first_hdr) {
-    void* nb = nullptr;
-    HIPCHK(hipMalloc(&nb, 3 * plane));
-    v->first_hdr = th->dev;
-    v->first_cache = tc->dev;
-    v->sb.buf = nb;
-    v->sb.bytes = 3 * plane;
-  } else {
-    const hipError_t e = v->sb.renew(3 * plane);
-    if (e != hipSuccess) return hip_err(e, "pt_environment_update: a new version of the environment");
-  }
+  const bool created = !v->edited();
+  if (const hipError_t e = v->next(th->dev, 3 * plane))
+    return hip_err(e, "pt_environment_update: a new version of the environment");
+  if (created) v->first_cache = tc->dev;
   float4* hdr = (float4*)v->sb.buf;
   float4* cache = (float4*)((char*)v->sb.buf + plane);
   float4* merged = (float4*)((char*)v->sb.buf + 2 * plane);
@@ -96,20 +88,20 @@ int pt_environment_update(uint32_t hdr_tex, uint32_t cache_tex, const void* rgb,
     rc = ptk::launch_environment_expand((const float*)rgb, hdr, n, g.stream);
     if (rc) return hip_err((hipError_t)rc, "pt_environment_update: expand");
     HIPCHK(hipEventRecord(v->src_done, g.stream));
-    HIPCHK(hipStreamWaitEvent(v->upload, v->src_done, 0));
+    HIPCHK(hipStreamWaitEvent(up, v->src_done, 0));
   } else {
-    void*& stage = v->staging[v->sb.buf];
     const size_t bytes = (size_t)n * 3 * sizeof(float);
-    if (!stage) HIPCHK(hipHostMalloc(&stage, bytes, hipHostMallocDefault));
+    void* stage = v->stage(bytes);  // W x H RGB texels
+    if (!stage) return hip_err(hipGetLastError(), "pt_environment_update: pinned staging");
     memcpy(stage, rgb, bytes);
     // the RGB texels pass through the version's cache plane, which the last kernel of the build overwrites
-    HIPCHK(hipMemcpyAsync(cache, stage, bytes, hipMemcpyHostToDevice, v->upload));
-    rc = ptk::launch_environment_expand((const float*)cache, hdr, n, v->upload);
+    HIPCHK(hipMemcpyAsync(cache, stage, bytes, hipMemcpyHostToDevice, up));
+    rc = ptk::launch_environment_expand((const float*)cache, hdr, n, up);
     if (rc) return hip_err((hipError_t)rc, "pt_environment_update: expand");
   }
-  rc = ptk::launch_environment_cache(hdr, cache, merged, v->scratch, width, height, v->upload);
+  rc = ptk::launch_environment_cache(hdr, cache, merged, v->scratch, width, height, up);
   if (rc) return hip_err((hipError_t)rc, "pt_environment_update: cache");
-  HIPCHK(v->sb.mark_built(v->upload));
+  HIPCHK(v->sb.mark_built(up));
   th->dev = hdr;
   tc->dev = cache;
   tex_written(th);
@@ -126,7 +118,7 @@ int pt_debug_environment_state(uint32_t hdr_tex, uint64_t* version, int* device_
   if (!t || t->target != PT_TEXTURE_2D) return err(PT_ERR_INVALID_HANDLE, "pt_debug_environment_state: not a 2-D texture");
   const EnvVersions* v = t->env;
   if (version) *version = t->version;
-  if (device_versions) *device_versions = (v && v->first_hdr) ? (int)v->sb.spare.size() + (v->sb.buf ? 1 : 0) + 1 : 1;
+  if (device_versions) *device_versions = (v && v->edited()) ? v->count() : 1;
   if (staging_slots) *staging_slots = v ? (int)v->staging.size() : 0;
   return PT_OK;
 }

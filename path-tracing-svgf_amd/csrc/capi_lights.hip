@@ -1,7 +1,7 @@
 // capi_lights.hip — point lights that move (DESIGN.md "Moving point lights"): pt_lights_update and the diagnostics of
-// include/ptsvgf_debug_lights.h. The per-light consequences are drawn where the draws are issued (capi_draw_pt.hip's
-// point_bins_for, capi_static.hip's point_cache_mode_for) from the position stamps kept here; the rules themselves are
-// lights_key.h's.
+// include/ptsvgf_debug_lights.h. The buffer's device versions are a Versions (capi_state.h). The per-light
+// consequences are drawn where the draws are issued (capi_draw_pt.hip's point_bins_for, capi_static.hip's
+// point_cache_mode_for) from the position stamps kept here; the rules themselves are lights_key.h's.
 #include "../../include/ptsvgf_debug_lights.h"
 #include "capi_state.h"
 
@@ -13,10 +13,7 @@ void free_lights(Texture* t) {
   LightVersions* v = t->lights;
   if (!v) return;
   (void)hipDeviceSynchronize();  // its readers may run on any stream
-  v->sb.free();                  // (the current version is t->dev)
-  if (v->first) (void)hipFree(v->first);
-  for (auto& s : v->staging) (void)hipHostFree(s.second);
-  if (v->upload) (void)hipStreamDestroy(v->upload);
+  v->free();                     // (the current version is t->dev)
   delete v;
   t->lights = nullptr;
   t->dev = nullptr;
@@ -43,22 +40,13 @@ int pt_lights_update(uint32_t lights_tex, int first, int count, const float* pos
     t->lights->pos_stamp.assign((size_t)nl, 0);
   }
   LightVersions& v = *t->lights;
-  if (!v.upload) HIPCHK(hipStreamCreateWithFlags(&v.upload, hipStreamNonBlocking));
-  // a version nothing in flight reads. The first update sets the creation's buffer aside: draws read it unnoted.
-  if (!v.first) {
-    v.first = t->dev;
-    void* nb = nullptr;
-    HIPCHK(hipMalloc(&nb, t->bytes));
-    v.sb.buf = nb;
-    v.sb.bytes = t->bytes;
-  } else {
-    const hipError_t e = v.sb.renew(t->bytes);
-    if (e != hipSuccess) {  // (renew retired the current version: the texture keeps pointing at it until one is had)
-      return hip_err(e, "pt_lights_update: a new version of the lights buffer");
-    }
-  }
-  void*& stage = v.staging[v.sb.buf];
-  if (!stage) HIPCHK(hipHostMalloc(&stage, t->bytes, hipHostMallocDefault));
+  hipStream_t up = v.stream();
+  if (!up) return hip_err(hipGetLastError(), "pt_lights_update: the copies' stream");
+  // a version nothing in flight reads (on failure the texture keeps pointing where it pointed)
+  if (const hipError_t e = v.next(t->dev, t->bytes))
+    return hip_err(e, "pt_lights_update: a new version of the lights buffer");
+  void* stage = v.stage(t->bytes);
+  if (!stage) return hip_err(hipGetLastError(), "pt_lights_update: pinned staging");
   const uint64_t ver = t->version + 1;
   for (int i = 0; i < count; ++i) {
     uint8_t* dst = t->host.data() + (size_t)(first + i) * lb;
@@ -69,8 +57,8 @@ int pt_lights_update(uint32_t lights_tex, int first, int count, const float* pos
   memcpy(stage, t->host.data(), t->bytes);
   // on a stream of its own, so that a draw waits for this copy (its event: pt_params) and not for whatever else the
   // stream that happened to be current has queued; no host wait anywhere
-  HIPCHK(hipMemcpyAsync(v.sb.buf, stage, t->bytes, hipMemcpyHostToDevice, v.upload));
-  HIPCHK(v.sb.mark_built(v.upload));
+  HIPCHK(hipMemcpyAsync(v.sb.buf, stage, t->bytes, hipMemcpyHostToDevice, up));
+  HIPCHK(v.sb.mark_built(up));
   t->dev = v.sb.buf;
   t->version = ver;
   return PT_OK;
@@ -123,8 +111,7 @@ int pt_debug_lights_state(uint32_t lights_tex, uint64_t* version, uint64_t* pos_
   const int nl = (int)(t->bytes / (6 * sizeof(float)));
   for (int l = 0; pos_stamps && l < cap; ++l)
     pos_stamps[l] = (t->lights && l < nl) ? t->lights->pos_stamp[(size_t)l] : 0;
-  if (device_versions)
-    *device_versions = t->lights ? (int)t->lights->sb.spare.size() + (t->lights->sb.buf ? 1 : 0) + 1 : 1;
+  if (device_versions) *device_versions = (t->lights && t->lights->edited()) ? t->lights->count() : 1;
   return PT_OK;
 }
 

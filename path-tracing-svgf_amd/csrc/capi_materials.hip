@@ -1,7 +1,8 @@
 // capi_materials.hip — materials edited in place (DESIGN.md "Material edits"): pt_materials_update and the
 // diagnostics of include/ptsvgf_debug_materials.h. The definition is tests/materials_ref.py's; the kernels are
-// kernels_materials.hip's. The versions of a scene's tri_shade records are handled as capi_lights.hip handles the
-// lights buffer's; the first-hit key takes the scene's shade version where the draws are issued (capi_static.hip).
+// kernels_materials.hip's. The versions of a scene's tri_shade records are a Versions (capi_state.h), written on the
+// one stream all updates share; the first-hit key takes the scene's shade version where the draws are issued
+// (capi_static.hip).
 #include "../../include/ptsvgf_debug_materials.h"
 #include "capi_state.h"
 #include "materials_host.h"
@@ -50,10 +51,8 @@ int take_slot(MatSlot** out) {
 }  // namespace
 
 void free_shade(SceneGPU& sg) {
-  if (sg.shade_first || !sg.shade.spare.empty()) (void)hipDeviceSynchronize();  // readers may run on any stream
+  if (sg.shade.edited() || !sg.shade.sb.spare.empty()) (void)hipDeviceSynchronize();  // readers may run on any stream
   sg.shade.free();
-  if (sg.shade_first) (void)hipFree(sg.shade_first);
-  sg.shade_first = nullptr;
 }
 
 int materials_order(hipStream_t s) {
@@ -114,36 +113,30 @@ int pt_materials_update(uint32_t tri_tex, uint32_t pose, int first_obj, int coun
   // A device decode of these texels that a draw queued (get_scene_lbvh) runs first: the texels are patched in place
   // below, and that draw reads the materials it was enqueued with. (Builds, refits and poses have synchronised.)
   for (auto& kv : g.scenes)
-    if (kv.first.first == tri_tex && kv.second.shade.built) HIPCHK(kv.second.shade.wait_built(up));
+    if (kv.first.first == tri_tex && kv.second.shade.sb.built) HIPCHK(kv.second.shade.sb.wait_built(up));
 
   // the decoded records of every scene that holds this buffer's current contents: a version nothing in flight reads
   for (auto& kv : g.scenes) {
     SceneGPU& sg = kv.second;
-    if (kv.first.first != tri_tex || !sg.geom || !sg.shade.buf || sg.tri_ver != t->version || sg.ntris != n) continue;
-    const size_t bytes = (size_t)n * 9 * sizeof(float4);
-    const float4* old = (const float4*)sg.shade.buf;
-    if (!sg.shade_first) {  // the decode's buffer: draws read it unnoted, so it is set aside for good
-      void* nb = nullptr;
-      HIPCHK(hipMalloc(&nb, bytes));
-      sg.shade_first = (float4*)sg.shade.buf;
-      if (sg.shade.built) (void)hipEventDestroy(sg.shade.built);  // (waited for above)
-      sg.shade.built = nullptr;
-      sg.shade.buf = nb;
-      sg.shade.bytes = bytes;
-    } else {
-      // the retired version's buffer stays valid to read: only a later renew hands it out, and that update's kernel
-      // runs after this one on the same stream
-      const hipError_t e = sg.shade.renew(bytes);
-      if (e != hipSuccess) {
-        // renew retired the current version and found none: the scene's next draw decodes it again (get_scene frees
-        // the versions first), from texels and a mirror this call has not touched
-        sg.tri_ver = 0;
-        return hip_err(e, "pt_materials_update: a new version of the shading records");
-      }
+    SharedBuf& sb = sg.shade.sb;
+    if (kv.first.first != tri_tex || !sg.geom || !sb.buf || sg.tri_ver != t->version || sg.ntris != n) continue;
+    // the version written last stays valid to read once retired: only a later update is handed it, and that one's
+    // kernel runs after this one on the same stream
+    const float4* old = (const float4*)sb.buf;
+    const bool decoded = !sg.shade.edited();  // it is the decode's buffer
+    if (const hipError_t e = sg.shade.next(sb.buf, (size_t)n * 9 * sizeof(float4))) {
+      // the current version was retired and none found: the scene's next draw decodes it again (get_scene frees the
+      // versions first), from texels and a mirror this call has not touched
+      if (!sb.buf) sg.tri_ver = 0;
+      return hip_err(e, "pt_materials_update: a new version of the shading records");
     }
-    const int rc = ptk::materials_shade_launch(old, (float4*)sg.shade.buf, n, slot->dev, first_obj, count, up);
+    if (decoded && sb.built) {  // the decode's event (waited for above) does not describe the new version
+      (void)hipEventDestroy(sb.built);
+      sb.built = nullptr;
+    }
+    const int rc = ptk::materials_shade_launch(old, (float4*)sb.buf, n, slot->dev, first_obj, count, up);
     if (rc) return hip_err((hipError_t)rc, "pt_materials_update: shading records");
-    HIPCHK(sg.shade.mark_built(up));
+    HIPCHK(sb.mark_built(up));
     sg.shade_ver++;
   }
 
@@ -170,11 +163,11 @@ int pt_debug_materials_state(uint32_t tri_tex, uint32_t node_tex, uint64_t* shad
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   TRY(ensure_init());
   auto it = g.scenes.find({tri_tex, node_tex});
-  if (it == g.scenes.end() || !it->second.shade.buf)
+  if (it == g.scenes.end() || !it->second.shade.sb.buf)
     return err(PT_ERR_STATE, "pt_debug_materials_state: no scene decoded from these buffers");
   const SceneGPU& sg = it->second;
   if (shade_version) *shade_version = sg.shade_ver;
-  if (device_versions) *device_versions = (int)sg.shade.spare.size() + 1 + (sg.shade_first ? 1 : 0);
+  if (device_versions) *device_versions = sg.shade.count();
   if (staging_slots) *staging_slots = (int)g_mat.slots.size();
   return PT_OK;
 }

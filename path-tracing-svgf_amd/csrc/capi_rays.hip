@@ -38,15 +38,15 @@ int check_list(const char* fn, const void* in, int64_t n, const void* out, bool 
   return PT_OK;
 }
 
-// The query over the scene of (tri_tex, node_tex) with every check done and the spill scratch in place; *shade: the
-// version of the shading records the launch reads, to be noted after it (null: the decode's own buffer).
+// The query over the scene of (tri_tex, node_tex) with every check done and the spill scratch in place; reads: the
+// version of the shading records the launch reads, to be noted after it (none: the decode's own buffer).
 int query_for(const char* fn, uint32_t tri_tex, uint32_t node_tex, const void* rays, int64_t n, ptk::RayQuery* q,
-              SharedBuf** shade) {
+              DrawReads* reads) {
   Texture* tt = tex_of(tri_tex);
   Texture* nt = tex_of(node_tex);
   if (!tt || tt->target != PT_TEXTURE_BUFFER || !nt || nt->target != PT_TEXTURE_BUFFER)
     return err(PT_ERR_INVALID_HANDLE, std::string(fn) + ": tri_tex and node_tex must be texture buffers");
-  *shade = nullptr;
+  *reads = DrawReads{};
   memset(q, 0, sizeof(*q));
   if (n == 0) return PT_OK;
   SceneGPU* sg = nullptr;
@@ -55,11 +55,11 @@ int query_for(const char* fn, uint32_t tri_tex, uint32_t node_tex, const void* r
   q->n = n;
   ptk::SceneDev& sc = q->scene;
   sc.tri_geom = sg->geom;
-  sc.tri_shade = (const float4*)sg->shade.buf;
+  sc.tri_shade = (const float4*)sg->shade.sb.buf;
   // the records' build event: a device decode a draw queued on another stream (a query may run on the library's own),
   // or the pt_materials_update that wrote this version on its stream; such a version is read until noted
-  if (sg->shade.built) HIPCHK(sg->shade.wait_built(g.stream));
-  if (sg->shade_first) *shade = &sg->shade;
+  if (sg->shade.edited()) TRY(read_shared(*reads, sg->shade.sb));
+  else if (sg->shade.sb.built) HIPCHK(sg->shade.sb.wait_built(g.stream));
   sc.bvh = sg->bvh;
   sc.root_ref = sg->root_ref;
   sc.ntris = sg->ntris;
@@ -94,9 +94,9 @@ int query_for(const char* fn, uint32_t tri_tex, uint32_t node_tex, const void* r
   return PT_OK;
 }
 
-int after_launch(const char* what, int rc, const ptk::RayQuery& q, SharedBuf* shade, int variant) {
+int after_launch(const char* what, int rc, const ptk::RayQuery& q, const DrawReads& reads, int variant) {
   if (rc) return hip_err((hipError_t)rc, what);
-  if (shade) HIPCHK(shade->note_read(g.stream));
+  TRY(note_reads(reads));
   g_rays.last_kind = q.spill ? 2 : (q.stack_need <= ptk::kStackSmall ? 0 : 1);
   g_rays.last_variant = variant;
   return PT_OK;
@@ -120,11 +120,11 @@ int pt_rays_closest(uint32_t tri_tex, uint32_t node_tex, const void* device_rays
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   TRY(ensure_init());
   ptk::RayQuery q;
-  SharedBuf* shade = nullptr;
-  TRY(query_for("pt_rays_closest", tri_tex, node_tex, device_rays, n, &q, &shade));
+  DrawReads reads;
+  TRY(query_for("pt_rays_closest", tri_tex, node_tex, device_rays, n, &q, &reads));
   if (n == 0) return PT_OK;
   const int v = variant_now();
-  return after_launch("pt_rays_closest", ptk::launch_rays_closest(q, device_hits, v, g.stream), q, shade, v);
+  return after_launch("pt_rays_closest", ptk::launch_rays_closest(q, device_hits, v, g.stream), q, reads, v);
 }
 
 int pt_rays_occluded(uint32_t tri_tex, uint32_t node_tex, const void* device_rays, int64_t n, void* device_u8) {
@@ -132,12 +132,12 @@ int pt_rays_occluded(uint32_t tri_tex, uint32_t node_tex, const void* device_ray
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   TRY(ensure_init());
   ptk::RayQuery q;
-  SharedBuf* shade = nullptr;
-  TRY(query_for("pt_rays_occluded", tri_tex, node_tex, device_rays, n, &q, &shade));
+  DrawReads reads;
+  TRY(query_for("pt_rays_occluded", tri_tex, node_tex, device_rays, n, &q, &reads));
   if (n == 0) return PT_OK;
   const int v = variant_now();
   // (the verdict reads no shading record: nothing to note)
-  return after_launch("pt_rays_occluded", ptk::launch_rays_occluded(q, device_u8, v, g.stream), q, nullptr, v);
+  return after_launch("pt_rays_occluded", ptk::launch_rays_occluded(q, device_u8, v, g.stream), q, DrawReads{}, v);
 }
 
 int pt_rays_primary(const float* eye3, const float* cameraRotate16, int width, int height, int aspect_corrected,

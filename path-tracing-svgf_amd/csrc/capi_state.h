@@ -4,8 +4,9 @@
 // draw and the SVGF chain's, one function per pass kind), capi_geometry.hip (geometry that moves: builds, refits,
 // raster binds, poses), capi_lights.hip (point lights that move), capi_environment.hip (the environment edited in place),
 // capi_materials.hip (materials edited in place),
-// capi_rays.hip (ray queries) and capi_static.hip (the static view: keys, caches, quiet-tile sets). Internal: nothing
-// here is part of the ABI.
+// capi_rays.hip (ray queries) and capi_static.hip (the static view: keys, caches, quiet-tile sets). The three kinds of
+// edit in place share one type for the device versions they write (Versions) and, with the draws and the ray queries,
+// one way to read a buffer another stream wrote (read_shared, note_reads). Internal: nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/ptsvgf.h"
@@ -270,47 +272,84 @@ struct SharedBuf {
   }
 };
 
-// The device versions of a lights texture buffer that pt_lights_update changes (DESIGN.md "Moving point lights"). An
-// update never writes memory a queued draw may read: it takes a version that nothing in flight reads (SharedBuf::renew:
-// the draws note their reads of the current one), copies the whole host copy into it through a pinned staging buffer
-// of its own on the current stream, and makes it Texture::dev. The buffer pt_texbuffer_create made is read by draws
-// that noted nothing, so the first update sets it aside for good (`first`) and it is freed with the texture.
-struct LightVersions {
+// The versions of a device buffer that an update call edits while draws are in flight on other streams (DESIGN.md
+// "Moving point lights" describes the protocol once): a lights buffer (pt_lights_update), a scene's tri_shade records
+// (pt_materials_update), an (hdrMap, hdrCache) pair (pt_environment_update). An update never writes memory a queued
+// draw may read: it takes a version that nothing in flight reads (next), fills it on a stream of the owner's own
+// (stream; host data through the version's pinned buffer, stage), records sb.mark_built there and makes the version
+// what the owner points at. Every launch that reads it waits for that event and notes its read (read_shared,
+// note_reads). The buffer the owner held before the first update is read by draws that noted nothing, so that update
+// sets it aside for good (`first`): it is freed with the versions. No host wait anywhere.
+struct Versions {
   SharedBuf sb;
   void* first = nullptr;
-  hipStream_t upload = nullptr;     // the copies' stream (non-blocking, created by the first update)
-  std::map<void*, void*> staging;   // per device version: its pinned host buffer (free again when the version is)
+  hipStream_t upload = nullptr;    // the updates' stream (non-blocking), where the owner keeps one of its own
+  std::map<void*, void*> staging;  // per device version: its pinned host buffer (free again when the version is)
+
+  bool edited() const { return first != nullptr; }  // an update has written a version: readers wait and note
+  // a version of at least `need` bytes that nothing in flight reads, in sb.buf; `cur`: the buffer the owner holds now.
+  // A failure of the first call changes nothing; a later one has retired the current version (sb.buf is null), which
+  // stays valid to read until a later call hands it out.
+  hipError_t next(void* cur, size_t need) {
+    if (first) return sb.renew(need);
+    void* nb = nullptr;
+    if (const hipError_t e = hipMalloc(&nb, need)) return e;
+    first = cur;
+    sb.buf = nb;
+    sb.bytes = need;
+    return hipSuccess;
+  }
+  // the pinned host buffer of the current version, `bytes` long (the same for every call); null: out of memory
+  void* stage(size_t bytes) {
+    void*& s = staging[sb.buf];
+    if (!s && hipHostMalloc(&s, bytes, hipHostMallocDefault) != hipSuccess) s = nullptr;
+    return s;
+  }
+  hipStream_t stream() {  // null: it could not be created
+    if (!upload && hipStreamCreateWithFlags(&upload, hipStreamNonBlocking) != hipSuccess) upload = nullptr;
+    return upload;
+  }
+  int count() const { return (int)sb.spare.size() + (sb.buf ? 1 : 0) + (first ? 1 : 0); }  // device buffers held
+  // the set-aside buffer, given back to its owner (free_environment), which frees it
+  void* take_first() { return std::exchange(first, nullptr); }
+  // drops every buffer, the events and the stream (the caller has synchronised the device)
+  void free() {
+    sb.free();
+    if (first) (void)hipFree(first);
+    for (auto& s : staging) (void)hipHostFree(s.second);
+    if (upload) (void)hipStreamDestroy(upload);
+    *this = Versions{};
+  }
+};
+
+// The versions of a lights texture buffer that pt_lights_update changes: whole copies of the host copy. The current
+// one is Texture::dev; `first` is the buffer pt_texbuffer_create made.
+struct LightVersions : Versions {
   std::vector<uint64_t> pos_stamp;  // per light: the Texture::version at which its position last changed bitwise
 };
 
-// The device versions of an (hdrMap, hdrCache) pair that pt_environment_update changes (DESIGN.md "Environment edits").
-// One version is one buffer of three float4 planes of W x H texels: the hdr texels, the cache texels and the merged
-// plane (hdr.xyz, cache.z). An update takes a version nothing in flight reads (SharedBuf::renew), builds it on a
-// stream of its own and makes its first two planes the textures' dev. The buffers pt_texture2d_create made are read by
-// draws that noted nothing: the first update sets them aside (first_hdr, first_cache), freed with the versions.
-struct EnvVersions {
-  SharedBuf sb;
+// The versions of an (hdrMap, hdrCache) pair that pt_environment_update changes (DESIGN.md "Environment edits"). One
+// version is one buffer of three float4 planes of W x H texels: the hdr texels, the cache texels and the merged plane
+// (hdr.xyz, cache.z); its first two planes are the textures' dev. The buffers pt_texture2d_create made are set aside
+// as `first` (the hdrMap's) and first_cache.
+struct EnvVersions : Versions {
   uint32_t hdr_handle = 0, cache_handle = 0;
   int W = 0, H = 0;
-  void *first_hdr = nullptr, *first_cache = nullptr;
-  hipStream_t upload = nullptr;    // the builds' stream (non-blocking, created by the first update)
+  void* first_cache = nullptr;
   hipEvent_t src_done = nullptr;   // a device source: its expansion on the current stream, which the build waits for
-  std::map<void*, void*> staging;  // per device version: its pinned host slot of W x H RGB texels (host sources)
   float* scratch = nullptr;        // lum / pdf and the conditional CDFs (W x H each), both marginals (W each), the total
   // the textures' versions as the last update left them: while they stand, the version's merged plane is the pair's
   uint64_t vh = 0, vc = 0;
   size_t plane() const { return (size_t)W * H * sizeof(float4); }
 };
 
-// What the draw being issued reads of the shared buffers (pt_params, point_bins_for), noted on its stream after a
-// successful launch (note_reads). Local to the draw call, which holds g_mu throughout.
+// What the draw or ray query being issued reads of the shared buffers (read_shared), noted on its stream after a
+// successful launch (note_reads). Local to the call, which holds g_mu throughout.
 struct DrawReads {
-  SharedBuf* hdr = nullptr;
-  SharedBuf* pbins = nullptr;
-  SharedBuf* lights = nullptr;  // the device version of an updated lights buffer (LightVersions)
-  SharedBuf* shade = nullptr;   // the device version of tri_shade records pt_materials_update wrote (SceneGPU::shade)
-  SharedBuf* env[2] = {nullptr, nullptr};  // the versions of an updated hdrMap / hdrCache (EnvVersions; [1]: another pair's)
-  const uint64_t* light_stamps = nullptr;  // its per-light position stamps (null: never updated, all 0)
+  // at most: the shade records, the lights, two environment pairs, the merged environment, the point-light bins
+  SharedBuf* bufs[6] = {};
+  int n = 0;
+  const uint64_t* light_stamps = nullptr;  // the bound lights' per-light position stamps (null: never updated, all 0)
   int light_count = 0;
   // the pointLights texture the draw bound (0: none): part of the verdict cache's key (static_key.h)
   uint32_t light_handle = 0;
@@ -338,13 +377,11 @@ struct PointBinsGPU {
 struct SceneGPU {
   PointBinsGPU pbins;
   float4* geom = nullptr;
-  // the tri_shade records. pt_materials_update (capi_materials.hip, DESIGN.md "Material edits") writes a new device
-  // version per update, as LightVersions does for the lights: the buffer the decode made is read by draws that noted
-  // nothing, so the first update sets it aside (shade_first, freed with the scene or at the next decode); later
-  // versions are renewed, waited for (wait_built) and noted in DrawReads. shade.built after a device decode: that
-  // decode's event, which the first update's kernel waits for.
-  SharedBuf shade;
-  float4* shade_first = nullptr;
+  // the tri_shade records, in shade.sb.buf: the decode's buffer, then the versions pt_materials_update writes
+  // (capi_materials.hip, DESIGN.md "Material edits"; freed with the scene or at the next decode). Draws wait for and
+  // note them once edited(). shade.sb.built after a device decode: that decode's event, which the first update's
+  // kernel waits for.
+  Versions shade;
   // bumped per update, never reset: with tri_ver in the first-hit key (a retired version taken again has the same
   // pointer and other contents)
   uint64_t shade_ver = 0;
@@ -476,6 +513,18 @@ int hip_err(hipError_t e, const char* what);
     int rc_ = (x);                \
     if (rc_ != PT_OK) return rc_; \
   } while (0)
+
+// the launch being issued on g.stream reads sb.buf: after the work that wrote it; noted after the launch (note_reads)
+inline int read_shared(DrawReads& r, SharedBuf& sb) {
+  HIPCHK(sb.wait_built(g.stream));
+  r.bufs[r.n++] = &sb;
+  return PT_OK;
+}
+// after the launch: its stream's use events on the shared buffers it read (SharedBuf::note_read)
+inline int note_reads(const DrawReads& r) {
+  for (int i = 0; i < r.n; ++i) HIPCHK(r.bufs[i]->note_read(g.stream));
+  return PT_OK;
+}
 
 Texture* tex_of(uint32_t h);
 Pass* pass_of(uint32_t h);
